@@ -19,9 +19,12 @@ both sides and the MAX over ranks is reported.  ``--scaling strong`` shards ONE 
 config's size over the ranks instead (reference chunk rule, _src/mpi_utils.py:36-41: BASELINE config 3's
 "same 1M batch sharded across 8 GPUs"); the line says which of the two was run.
 
-After every timed loop (headline and each secondary) 256 of the outputs the loop left in HBM are compared with
-the fp64 LDS workgroup kernel (an independent kernel family, plain tables) and the largest error goes into the
-line as ``check``: a number from a kernel whose results are wrong is not a number.
+A plain run sets up, warms up, times the K steps and prints the line (``check`` null).  ``--full`` adds what
+the headline does not need: the ramp convention, the pack time of the prepared tables, the secondary lines of
+other configs and routes, the CPU baseline, and after every timed loop (headline and each secondary) a spot
+check: 256 of the outputs the loop left in HBM are compared with the fp64 LDS workgroup kernel (an independent
+kernel family, plain tables) and the largest error goes into the line as ``check``.  ``--dump-outputs DIR``
+writes what the last timed step computed to DIR/*.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -487,6 +490,45 @@ def _outputs_of(cfg, w, route: str, last):
     return last[0], last[1]
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+NPY_HEADROOM_BYTES = 4096  # (the .npy headers and the objective's scalars)
+
+
+def dump_outputs(path: str, cfg, w, route: str, last):
+    """--dump-outputs: what the last timed step computed, as <path>/<name>.npy in the step's precision: mean (b, R)
+    and var (b,), and for the objective configs every scalar of the evaluation (lool, sigma_sq, ...) in fp64 next to
+    the prepared evaluation's mean / var buffers.  If mean and var together exceed 64 MB, a fixed, seeded sample of
+    their rows is written instead, and the sampled row numbers go to rows.npy."""
+    import torch
+
+    b = w["b"]
+    mean, var = _outputs_of(cfg, w, route, last)
+    arrays = {"mean": torch.as_tensor(mean).as_subclass(torch.Tensor).reshape(b, -1),
+              "var": torch.as_tensor(var).as_subclass(torch.Tensor).reshape(b)}
+    extra = {}
+    if isinstance(last, dict):
+        for key, v in last.items():
+            if key in ("rank", "world_size") or isinstance(v, bool):
+                continue
+            if isinstance(v, (int, float)):
+                extra[key] = np.asarray([v], dtype=np.float64)
+            elif isinstance(v, (list, tuple)) and v and all(isinstance(x, (int, float)) for x in v):
+                extra[key] = np.asarray(v, dtype=np.float64)
+    row_bytes = sum(t.element_size() * (t.numel() // max(b, 1)) for t in arrays.values())
+    budget = DUMP_LIMIT_BYTES - NPY_HEADROOM_BYTES
+    if b * row_bytes > budget:
+        m = budget // (row_bytes + 8)  # (+ the row number, fp64)
+        keep = np.sort(np.random.default_rng(0).choice(b, size=m, replace=False))
+        idx = torch.from_numpy(keep).to(arrays["mean"].device)
+        arrays = {key: t[idx] for key, t in arrays.items()}
+        extra["rows"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for key, t in arrays.items():
+        np.save(os.path.join(path, key + ".npy"), t.detach().cpu().numpy())
+    for key, a in extra.items():
+        np.save(os.path.join(path, key + ".npy"), a)
+
+
 def _launch_geometry():
     from muygpys_amd import _lib
 
@@ -740,12 +782,20 @@ def main():
     ap.add_argument("--objective", action="store_true",
                     help="time one LOOCV objective evaluation (fused launch + loss sums + the all-reduce)")
     ap.add_argument("--knn", action="store_true", help="exact GPU kNN neighbourhoods instead of random rows")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the ramp convention, the pack time of "
+                         "the prepared tables, the spot check against the fp64 workgroup kernel, the secondary lines "
+                         "and the CPU baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                         "a fixed, seeded sample of the rows of a larger output, whose row numbers go to DIR/rows.npy)")
     ap.add_argument("--cpu-sample", type=int, default=CPU_BATCH,
-                    help="neighbourhoods of the CPU baseline leg (default: BASELINE.md sec. 2's 65 536); 0 disables it")
+                    help="neighbourhoods of the CPU baseline leg of --full (default: BASELINE.md sec. 2's 65 536); "
+                         "0 disables it")
     ap.add_argument("--path", default="auto", choices=["auto", "generic", "rhs"], help="kernel family to time")
     ap.add_argument("--no-prepared-tables", action="store_true", help="read the plain feature / target tables")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short runs of configs 3 / 4 / 5 and of the drop-in route attached as `secondary`")
+                    help="--full: skip the short runs of configs 3 / 4 / 5 and of the drop-in route attached as `secondary`")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank its own batch of the config's size; strong: ONE global batch of that size "
                          "sharded over the ranks with the reference's chunk rule (BASELINE config 3)")
@@ -805,6 +855,7 @@ def main():
     pack_ms = pack_cold_ms = None
     if use_packed:
         pack_table(w["X"], w["y"])  # the cached table the timed steps use
+    if use_packed and args.full:
         # one more pack, timed on the stream: what a pack per step would add.  Twice: the first one also pays the
         # allocator's hipMalloc of a block this size (`cold`, what round 4 reported: 0.36-0.45 ms around a 60 us
         # kernel); a pack per step would find the block in torch's caching allocator, as the second one does
@@ -824,13 +875,16 @@ def main():
     # Two conventions, both reported (VERDICT r04 #1c).  `ramp`: W + K steps from an idle GPU -- what rounds 1-4 put in
     # `value`; with the driver's short loops (--steps 20 --warmup 5 = 40 ms) it lies inside the clock ramp (the kernel's
     # launches read 2.1, 2.0, 1.85 ... 1.5 ms over the first ~25).  `value`: the same W + K steps after the GPU has run
-    # the step for --settle-ms (150 ms: what the secondary lines have always done) -- steady state.
+    # the step for --settle-ms (150 ms: what the secondary lines have always done) -- steady state.  A plain run makes
+    # the same W + K steps from an idle GPU (they size the settle phase and warm the GPU as before); only --full
+    # reports them.
     ramp, settle_steps = None, 0
     if args.settle_ms > 0:
         r_elapsed, r_kern, _, _ = time_steps(step, args.warmup, args.steps, dist, args.backend, dev)
-        ramp = {"value": total_b * args.steps / r_elapsed, "ms_per_step": r_elapsed / args.steps * 1e3,
-                "kernel_ms": float(np.mean(r_kern)),
-                "what": f"{args.warmup} + {args.steps} steps from an idle GPU (the convention of rounds 1-4)"}
+        if args.full:
+            ramp = {"value": total_b * args.steps / r_elapsed, "ms_per_step": r_elapsed / args.steps * 1e3,
+                    "kernel_ms": float(np.mean(r_kern)),
+                    "what": f"{args.warmup} + {args.steps} steps from an idle GPU (the convention of rounds 1-4)"}
         # (a step count, the same on every rank -- r_elapsed is the maximum over the ranks --, not a clock: a step of an
         # objective config ends in a collective)
         settle_steps = int(min(2000, np.ceil(args.settle_ms * 1e-3 / max(r_elapsed / args.steps, 1e-5))))
@@ -846,10 +900,14 @@ def main():
         assert torch.isfinite(last[0]).all() and torch.isfinite(last[1]).all(), "non-finite outputs"
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, cfg, w, args.route, last)
         avg_ms = float(np.mean(kern_ms))
         roof = roofline_of(cfg, w, avg_ms, kernel_name, cfg["objective"])
-        check = spot_check(cfg, w, *_outputs_of(cfg, w, args.route, last))
-        assert check is None or check["ok"], f"timed outputs differ from the fp64 workgroup kernel: {check}"
+        check = None
+        if args.full:
+            check = spot_check(cfg, w, *_outputs_of(cfg, w, args.route, last))
+            assert check is None or check["ok"], f"timed outputs differ from the fp64 workgroup kernel: {check}"
         if ramp is not None:  # (inside `roofline`: the driver's record keeps it; the top-level `ramp` it drops)
             roof["ramp_value"], roof["ramp_ms_per_step"] = ramp["value"], ramp["ms_per_step"]
             roof["settle_ms"] = args.settle_ms
@@ -899,7 +957,7 @@ def main():
         if args.route != "fused":
             out["roofline"]["note"] = ("kernel_ms is the whole family-level call sequence of one prediction batch "
                                        "(handles, one fused launch, its host glue)")
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             # the other BASELINE configs and the drop-in route, 5 steps each (the headline keys above are
             # unaffected: these run after the timed region, on their own tables)
             del w, step, last
@@ -944,7 +1002,7 @@ def main():
                      "check_ok": None if v["check"] is None else v["check"]["ok"]},
                     **{key: v[key] for key in ("rate_vs_full_batch", "acquisition_ms", "acquisition_ms_mean") if key in v}))
                 for name, v in sec.items()}
-        if args.cpu_sample > 0 and world == 1:
+        if args.full and args.cpu_sample > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(k, d, args.cpu_sample, 20241008, points=min(n, 1_000_000))
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -11,6 +11,8 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -41,7 +43,8 @@ PER_FILE_FLAGS = {
     "mgp_fused_wide.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "mgp_fused_wide64.hip": ["-Rpass-analysis=kernel-resource-usage"],
     "mgp_backward.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
-    "mgp_backward_wave.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
+    **{f: ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"]
+       for f in ("mgp_backward_wave.hip", "mgp_backward_wave_f32_np32.hip", "mgp_backward_wave_f32_np64.hip")},
     "mgp_backward_dlt.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
 }
 
@@ -53,8 +56,25 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found: the HIP library cannot be built")
 
 
+# the translation units that take longest (minutes each with the unroll thresholds above): started first
+SLOW_FIRST = ("mgp_backward_wave_f32_np32.hip", "mgp_backward_wave_f32_np64.hip", "mgp_backward_wave.hip",
+              "mgp_fused_wave.hip", "mgp_fused_wide64.hip", "mgp_fused_wave_inst_f64.hip", "mgp_fused_wave_inst_f32.hip")
+
+
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+
+
+def _parallel_jobs() -> int:
+    """Compilers run at once: MAX_JOBS if set, else the CPUs this process may use (at most 16)."""
+    env = os.environ.get("MAX_JOBS", "")
+    if env.isdigit() and int(env) > 0:
+        return int(env)
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
 
 
 def _stale() -> bool:
@@ -110,19 +130,46 @@ def build(force: bool = False, verbose: bool = False) -> str:
         with open(res_path) as f:
             resources = json.load(f)
     extra = os.environ.get("MGP_EXTRA_HIPCC_FLAGS", "").split()
+    cmds = []
     for src in sources():
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
         if not force and not extra and not _object_stale(src, obj):
             continue
-        cmd = [hipcc, *FLAGS, *PER_FILE_FLAGS.get(os.path.basename(src), []), *extra, "-c", src, "-o", obj]
+        cmds.append([hipcc, *FLAGS, *PER_FILE_FLAGS.get(os.path.basename(src), []), *extra, "-c", src, "-o", obj])
+    rank = {name: i for i, name in enumerate(SLOW_FIRST)}
+    cmds.sort(key=lambda c: rank.get(os.path.basename(c[-3]), len(rank)))
+    jobs, t0, done = _parallel_jobs(), time.monotonic(), 0
+    running = []
+
+    def start(cmd):
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
-        procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for cmd, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + out)
+        # (the output goes to a file: a pipe nobody reads while the other compilers run could fill and stall hipcc)
+        log = tempfile.TemporaryFile(mode="w+")
+        running.append((cmd, subprocess.Popen(cmd, stdout=log, stderr=subprocess.STDOUT, text=True), log))
+
+    while cmds or running:
+        while cmds and len(running) < jobs:
+            start(cmds.pop(0))
+        finished = [r for r in running if r[1].poll() is not None]
+        if not finished:
+            time.sleep(0.2)
+            continue
+        for cmd, p, log in finished:
+            running.remove((cmd, p, log))
+            log.seek(0)
+            out = log.read()
+            log.close()
+            if p.returncode != 0:
+                for _, q, _ in running:
+                    q.kill()
+                raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + out)
+            done += 1
+            print(f"[build] {os.path.basename(cmd[-3])} compiled ({done} done, {time.monotonic() - t0:.0f} s)",
+                  file=sys.stderr, flush=True)
+            procs.append((cmd, out))
+    for cmd, out in procs:
         if "-Rpass-analysis=kernel-resource-usage" in cmd:
             resources.update(_parse_resource_remarks(out))
             out = "\n".join(ln for ln in out.splitlines() if "kernel-resource-usage" not in ln and "remark:" not in ln)
@@ -167,31 +214,53 @@ PREWARM_D = (8, 16, 32, 40, 64)
 PREWARM_BWD = ((8, 40, 8), (8, 40, 16), (8, 50, 16), (8, 32, 8), (4, 30, 16), (4, 20, 40), (4, 25, 8), (8, 30, 40), (4, 50, 8), (4, 40, 16), (4, 10, 8), (4, 30, 100))
 
 
-def _prewarm_one(job):
-    import ctypes
-
-    es, k, d, packed = job
-    lib = ctypes.CDLL(LIB)
+# one process of the cache fill: compiles the shapes it is given (JSON) into the library's cache and prints one return
+# code per shape.  A plain `python -c` child: it never re-imports the caller's main module, as a multiprocessing
+# worker started by "spawn" does (and a caller without a __main__ guard would start the build again in every worker)
+_PREWARM_WORKER = r"""
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+lib.mgp_jit_prepare.argtypes = [ctypes.c_int] * 6
+lib.mgp_jit_prepare.restype = ctypes.c_int
+lib.mgp_jit_prepare_backward.argtypes = [ctypes.c_int] * 4
+lib.mgp_jit_prepare_backward.restype = ctypes.c_int
+for es, k, d, packed in json.loads(sys.argv[2]):
     if packed == "bwd":
-        lib.mgp_jit_prepare_backward.argtypes = [ctypes.c_int] * 4
-        lib.mgp_jit_prepare_backward.restype = ctypes.c_int
-        return job, lib.mgp_jit_prepare_backward(es, k, d, 2)
-    lib.mgp_jit_prepare.argtypes = [ctypes.c_int] * 6
-    lib.mgp_jit_prepare.restype = ctypes.c_int
-    return job, lib.mgp_jit_prepare(es, k, 1, d, packed, 2)  # kernel id 2 = Matern-3/2 (any Gram-form kernel)
+        rc = lib.mgp_jit_prepare_backward(es, k, d, 2)
+    else:
+        rc = lib.mgp_jit_prepare(es, k, 1, d, packed, 2)  # kernel id 2 = Matern-3/2 (any Gram-form kernel)
+    print(rc, flush=True)
+"""
 
 
 def prewarm(verbose: bool = False) -> int:
     """Fill muygpys_amd/lib/jit/ for the common shapes (objects already there are kept: the file name
     carries a hash of the kernel sources).  Returns the number of shapes available."""
-    import multiprocessing as mp
+    import json
 
     jobs = [(4, k, d, p) for k in PREWARM_K for d in PREWARM_D for p in (1, 0)]
     jobs += [(8, k, d, 1) for k in PREWARM_K for d in PREWARM_D if d <= 32]
     jobs += [(es, k, d, "bwd") for es, k, d in PREWARM_BWD]
-    with mp.get_context("spawn").Pool(min(8, os.cpu_count() or 1)) as pool:
-        done = pool.map(_prewarm_one, jobs)
-    ok = sum(1 for _, rc in done if rc == 0)
+    print(f"[build] compiling {len(jobs)} run-time specialised shapes", file=sys.stderr, flush=True)
+    n = min(8, _parallel_jobs(), len(jobs))
+    workers = []
+    for i in range(n):
+        err = tempfile.TemporaryFile(mode="w+")
+        cmd = [sys.executable, "-c", _PREWARM_WORKER, LIB, json.dumps(jobs[i::n])]
+        workers.append((subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=err, text=True), err))
+    codes = []
+    for p, err in workers:
+        out, _ = p.communicate()
+        err.seek(0)
+        msg = err.read()
+        err.close()
+        if p.returncode != 0:
+            for q, _ in workers:
+                if q.poll() is None:
+                    q.kill()
+            raise RuntimeError(f"run-time specialisation cache: a worker exited with {p.returncode}\n{msg}")
+        codes += [int(v) for v in out.split()]
+    ok = sum(1 for rc in codes if rc == 0)
     if verbose:
         print(f"run-time specialisation cache: {ok} of {len(jobs)} shapes ready", file=sys.stderr)
     # drop objects of other builds: a file name ends in the hash of kernel sources + options + compiler, and the

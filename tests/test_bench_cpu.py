@@ -108,3 +108,30 @@ def test_supervise_ranks_success_and_timeout(tmp_path):
     t0 = time.monotonic()
     assert bench.supervise_ranks(sleeper, timeout_s=1.0, grace_s=2.0) == 124
     assert time.monotonic() - t0 < 20.0 and all(p.poll() is not None for p in sleeper)
+
+
+def test_dumped_outputs_are_the_step_outputs_or_a_fixed_sample_of_their_rows(tmp_path, monkeypatch):
+    import os
+
+    import bench
+
+    cpu = torch.device("cpu")
+    w = bench.build_workload(_cfg(), cpu, 0, False)
+    w["mean"].copy_(torch.arange(1003, dtype=torch.float32).reshape(1003, 1))
+    w["var"].copy_(torch.arange(1003, dtype=torch.float32) * 0.5)
+    bench.dump_outputs(str(tmp_path / "whole"), _cfg(), w, "fused", None)
+    mean, var = np.load(tmp_path / "whole" / "mean.npy"), np.load(tmp_path / "whole" / "var.npy")
+    assert mean.dtype == var.dtype == np.float32 and mean.shape == (1003, 1) and var.shape == (1003,)
+    assert np.array_equal(mean[:, 0], np.arange(1003)) and np.array_equal(var, np.arange(1003) * 0.5)
+    assert not (tmp_path / "whole" / "rows.npy").exists()
+    limit = bench.NPY_HEADROOM_BYTES + 1600  # 4 + 4 bytes per row and its fp64 row number: 100 of the 1003 rows
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), _cfg(), w, "fused", None)
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.dtype == np.float64 and rows.shape == (100,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "mean.npy")[:, 0], rows)
+    assert np.array_equal(np.load(tmp_path / "s1" / "var.npy"), rows * 0.5)
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= limit

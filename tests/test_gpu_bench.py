@@ -85,7 +85,7 @@ def _run(cmd, timeout=900):
 def test_every_kernel_the_default_bench_line_times_is_oracle_checked():
     """The driver's command (`python bench.py`, shortened loops): every `kernel` in the line -- headline and every
     secondary -- must be an instantiation the oracle comparison above has run, and every in-bench check must hold."""
-    out = _run([sys.executable, BENCH, "--steps", "6", "--warmup", "3", "--cpu-sample", "0"])
+    out = _run([sys.executable, BENCH, "--full", "--steps", "6", "--warmup", "3", "--cpu-sample", "0"])
     checked = {_oracle_checked_kernel(c) for c in (2, 3, 4, 5)}
     checked |= {_oracle_checked_kernel(2, "dropin"), _oracle_checked_kernel(2, "dropin_plain")}
     assert out["check"]["ok"], out["check"]
@@ -120,8 +120,8 @@ def _free_port():
         return s.getsockname()[1]
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-secondary", "--points", "60000", "--batch", "20001",
-         "--one-device", "--backend", "gloo"]
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-secondary", "--points", "60000", "--batch",
+         "20001", "--one-device", "--backend", "gloo"]
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
@@ -153,3 +153,35 @@ def test_bench_refuses_a_world_size_mismatch():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", *SMALL], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+@pytest.mark.parametrize("config", ["2", "3"])
+def test_plain_line_times_the_steps_and_dumps_the_last_outputs(tmp_path, config):
+    """`python bench.py` without --full: the headline keys, exactly --steps timed steps, no check / secondary / CPU
+    leg; --dump-outputs writes the last timed step's mean and var (and the objective's scalars), equal to the oracle's
+    on the same inputs, and two runs with the same arguments dump the same inputs' outputs."""
+    cmd = [sys.executable, BENCH, "--config", config, "--steps", "4", "--warmup", "1", "--points", "60000",
+           "--batch", "20001", "--dump-outputs", str(tmp_path / "a")]
+    out = _run(cmd)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 4 and out["check"] is None and out["ramp"] is None
+    assert "secondary" not in out and "cpu_baseline" not in out
+    assert abs(out["value"] - 20001 / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+    mean, var = np.load(tmp_path / "a" / "mean.npy"), np.load(tmp_path / "a" / "var.npy")
+    assert mean.shape == (20001, 1) and var.shape == (20001,) and mean.dtype == var.dtype == np.float32
+    if config == "3":
+        assert np.isfinite(np.load(tmp_path / "a" / "lool.npy")).all()
+    import bench
+
+    cfg = dict(bench.CONFIGS[int(config)], points=60000, batch=20001)
+    w = bench.build_workload(cfg, torch.device("cpu"), 0, False)
+    X, y = w["X"].double().numpy(), w["y"].double().numpy()
+    bi, ni = w["bi"].numpy(), w["ni"].numpy()
+    pick = np.arange(0, 20001, 97)
+    m_ref, v_ref = orc.posterior_mean_var(orc.Spec(cfg["kernel"], cfg["metric"], float(w["ls"]), cfg["noise"]), X, X,
+                                          bi[pick], ni[pick], y)
+    assert_close(mean[pick].reshape(len(pick), -1), m_ref.reshape(len(pick), -1), RTOL["float32"], "dumped mean")
+    assert_close(var[pick], v_ref, RTOL["float32"], "dumped var")
+    _run(cmd[:-1] + [str(tmp_path / "b")])
+    np.testing.assert_allclose(np.load(tmp_path / "b" / "mean.npy"), mean, rtol=1e-5, atol=1e-6)

@@ -25,9 +25,9 @@ def make_variant(spec: str, top: str) -> str:
     os.makedirs(src, exist_ok=True)
     for f in os.listdir(CSRC):
         if f.endswith(".h"):
-            shutil.copy(os.path.join(CSRC, f), src)
+            shutil.copyfile(os.path.join(CSRC, f), os.path.join(src, f))
     os.makedirs(os.path.join(d, "include"), exist_ok=True)  # (mgp_device.h includes ../../include/muygpys_hip.h)
-    shutil.copy(os.path.join(ROOT, "include", "muygpys_hip.h"), os.path.join(d, "include"))
+    shutil.copyfile(os.path.join(ROOT, "include", "muygpys_hip.h"), os.path.join(d, "include", "muygpys_hip.h"))
     if spec != "base":
         for item in spec.split(","):
             name, val = item.split("=")

@@ -16,7 +16,7 @@ rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_plain -- python3 
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $O/pmc_sq1 -- python3 bench.py --cpu-sample 0 --steps 3 --warmup 1 > $O/pmc_sq1.json 2> $O/pmc_sq1.err
 rocprofv3 --pmc SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VMEM SQ_WAVES --output-format csv -d $O/pmc_sq2 -- python3 bench.py --cpu-sample 0 --steps 3 --warmup 1 > $O/pmc_sq2.json 2> $O/pmc_sq2.err
 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_grbm -- python3 bench.py --cpu-sample 0 --steps 3 --warmup 1 > $O/pmc_grbm.json 2> $O/pmc_grbm.err
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 find $O -name "*.csv" -size +3000k -delete
 ls -la $O $O/*/* | head -80
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_wide -- python3 tools/kbench.py --k 100 --d 40 --b 200000 --paths auto,generic --rounds 3 > $O/stats_wide.log 2> $O/stats_wide.err

@@ -22,7 +22,7 @@ rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_HIT_sum TCC_MISS_sum --output-format csv -
 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $O/grbm_c2 -- $B --steps 3 --warmup 1 > $O/grbm_c2.json 2> $O/grbm_c2.err
 $B --points 8000000 > $O/bench_8M.json 2> $O/bench_8M.err
 $B --points 4000000 > $O/bench_4M.json 2> $O/bench_4M.err
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 find $O -name "*kernel_trace.csv" -size +2000k -delete
 find $O -name "*.csv" -size +3000k -delete
 ls $O | head -50
