@@ -628,6 +628,64 @@ int mgp_allreduce_partials(double* partials, int count, void* nccl_comm, void* s
 int mgp_column_sums_f32(const float* x, int64_t n, int R, double* out, double* scratch, void* stream);
 int mgp_column_sums_f64(const double* x, int64_t n, int R, double* out, double* scratch, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Weak-lensing shear model (the reference's experimental family: gp/kernels/experimental/shear.py,
+ * gp/noise/shear.py).  Features are 2-D; each point carries the components (kappa, gamma1, gamma2).
+ * `length_scale` enters as the reference writes it (_src/gp/kernels/shear/numpy.py:10-103), i.e. as a
+ * squared length.
+ * ------------------------------------------------------------------------- */
+enum mgp_shear_variant {
+  MGP_SHEAR_33 = 0,       /* (.., 3, n, 3, m): _shear_33_fn, _src/gp/kernels/shear/numpy.py:105-163        */
+  MGP_SHEAR_KIN23 = 1,    /* (.., 2, n, 2, m): _shear_Kin23_fn, :166-207 (the gamma1, gamma2 sub-blocks)   */
+  MGP_SHEAR_KCROSS23 = 2  /* (.., 2, n, 3, m): _shear_Kcross23_fn, :210-260 (gamma rows vs all three)      */
+};
+enum mgp_shear_noise {
+  MGP_SHEAR_NOISE_HOMOSCEDASTIC = 0, /* eps on every observed row: _homoscedastic_perturb 5-D, _src/gp/noise/numpy.py:15-22 */
+  MGP_SHEAR_NOISE_33 = 1             /* 2 eps on kappa, eps on gamma1 / gamma2: _shear_perturb33, :30-53 (in_count 3)     */
+};
+/* Shear covariance tensor of a difference tensor: diffs is (G, n, m, 2) (any leading batch shape
+ * flattened into G), out is (G, I, n, O, m) with (I, O) = (3, 3), (2, 2), (2, 3) by `variant`:
+ * out[g, a, i, c, j] = block(diffs[g, i, j])[a][c].  Replaces _shear_33_fn / _shear_Kin23_fn /
+ * _shear_Kcross23_fn (_src/gp/kernels/shear/numpy.py:105-260) before their np.squeeze. */
+int mgp_shear_tensor_f32(const float* diffs, int64_t G, int n, int m, int variant, double length_scale, float* out,
+                         void* stream);
+int mgp_shear_tensor_f64(const double* diffs, int64_t G, int n, int m, int variant, double length_scale, double* out,
+                         void* stream);
+/* Multi-output posterior of a materialised, already perturbed Kin (b, n, n), Kcross (b, n, m), Y (b, n, R):
+ *   mean (b, m, R) = Kcross^T Kin^-1 Y              _muygps_posterior_mean, _src/gp/muygps/numpy.py:17-41
+ *   kk (b, m, m)   = Kcross^T Kin^-1 Kcross         _muygps_diagonal_variance, :44-67 (Kout - kk on the host)
+ *   ykinvy (b, R)  = y_r^T Kin^-1 y_r
+ * from one LDS-resident Cholesky per system (packed triangle, n + m + R rows); mean / kk / ykinvy /
+ * Y may be NULL (Y only when R == 0).  info (device int, may be NULL) counts systems with a
+ * non-positive pivot, whose outputs are NaN.  MGP_EUNSUPPORTED when the system does not fit LDS. */
+int mgp_solve_multi_f32(const float* Kin, const float* Kcross, const float* Y, int64_t b, int n, int m, int R,
+                        float* mean, float* kk, float* ykinvy, int* info, void* stream);
+int mgp_solve_multi_f64(const double* Kin, const double* Kcross, const double* Y, int64_t b, int n, int m, int R,
+                        double* mean, double* kk, double* ykinvy, int* info, void* stream);
+/* Fused shear posterior, one launch from the tables.  Replaces, per neighbourhood,
+ *   crosswise_tensor / pairwise_tensor (gp/deformation/isotropy.py:214-276) + ShearKernel.__call__ /
+ *   ShearKernel2in3out.__call__ (gp/kernels/experimental/shear.py:111-129,241-264) + _shear_perturb33 /
+ *   _homoscedastic_perturb (_src/gp/noise/numpy.py:9-53) + _muygps_posterior_mean / _muygps_diagonal_variance
+ *   (_src/gp/muygps/numpy.py:17-67).
+ * feat_q (n_q, 2), feat_nn (n, 2); batch_idx (b) (NULL = 0 .. b-1), nn_idx (b, k) int64.
+ * in_count 3 observes (kappa, gamma1, gamma2), 2 observes (gamma1, gamma2); the observed rows are
+ * flattened component-major (row a * k + i).  targets: targets_batch == 0 -> a table whose row t holds
+ * the observed components at targets[t * targets_stride + a]; targets_batch != 0 -> the gathered
+ * (b, in_count, k) tensor.  Outputs: mean (b, 3), kk (b, 3, 3) = Kcross^T K^-1 Kcross (the caller
+ * forms Kout - kk with ITS Kout), ykinvy (b) (may be NULL); info as for mgp_solve_multi_*.
+ * MGP_EUNSUPPORTED for k > mgp_shear_max_nn_count(sizeof(T), in_count). */
+int mgp_shear_posterior_f32(const float* feat_q, const float* feat_nn, const int64_t* batch_idx,
+                            const int64_t* nn_idx, int64_t b, int k, int in_count, const float* targets,
+                            int64_t targets_stride, int targets_batch, double length_scale, int noise_mode,
+                            double noise, float* mean, float* kk, float* ykinvy, int* info, void* stream);
+int mgp_shear_posterior_f64(const double* feat_q, const double* feat_nn, const int64_t* batch_idx,
+                            const int64_t* nn_idx, int64_t b, int k, int in_count, const double* targets,
+                            int64_t targets_stride, int targets_batch, double length_scale, int noise_mode,
+                            double noise, double* mean, double* kk, double* ykinvy, int* info, void* stream);
+/* Largest nn_count mgp_shear_posterior_* accepts for a float width and in_count (2 or 3); -1 for bad
+ * arguments. */
+int mgp_shear_max_nn_count(int elem_size, int in_count);
+
 #ifdef __cplusplus
 }
 #endif

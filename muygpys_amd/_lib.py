@@ -78,7 +78,12 @@ _SIGS = {
                            _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "fast_coefficients": [_p, _i, _p, _l, _i, _p, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p],
     "fast_posterior_mean": [_p, _p, _i, _p, _p, _l, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p],
+    "shear_tensor": [_p, _l, _i, _i, _i, _d, _p, _p],
+    "solve_multi": [_p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p],
+    "shear_posterior": [_p, _p, _p, _p, _l, _i, _i, _p, _l, _i, _d, _i, _d, _p, _p, _p, _p, _p],
 }
+SHEAR_33, SHEAR_KIN23, SHEAR_KCROSS23 = 0, 1, 2
+SHEAR_NOISE_HOMOSCEDASTIC, SHEAR_NOISE_33 = 0, 1
 
 
 def exported_names_from_header():
@@ -142,6 +147,8 @@ def load():
     lib.mgp_jit_mode.restype = _i
     lib.mgp_jit_loaded_count.argtypes = []
     lib.mgp_jit_loaded_count.restype = _i
+    lib.mgp_shear_max_nn_count.argtypes = [_i, _i]
+    lib.mgp_shear_max_nn_count.restype = _i
     lib.mgp_packed_row_bytes.argtypes = [_i, _i, _i]
     lib.mgp_packed_row_bytes.restype = _l
     for base, sig in _SIGS.items():
@@ -192,6 +199,11 @@ def served_by(d: int, k: int, R: int, dtype, packed: bool = False, path: str = "
         return served_by(d, k, R, dtype, False, path)
     check(rc, "mgp_posterior_kernel_name")
     return buf.value.decode()
+
+
+def shear_max_nn_count(dtype, in_count: int) -> int:
+    """Largest nn_count the fused shear posterior accepts (``mgp_shear_max_nn_count``)."""
+    return load().mgp_shear_max_nn_count(4 if dtype == torch.float32 else 8, int(in_count))
 
 
 def last_kernel() -> str:

@@ -9,6 +9,8 @@ of one evaluation.
 
 from __future__ import annotations
 
+import math
+
 import torch
 
 from muygpys_amd import _lib, lazy, lazy_eval
@@ -38,8 +40,83 @@ def _solve(Kin, Kcross, Y, kout=1.0, want=("mean",)):
     return mean, var, yk, co
 
 
+def _matching_ndim(nn_targets, Kin) -> int:
+    """How many leading dimensions of the targets agree with Kin's (numpy.py:9-14)."""
+    return sum(1 for x, y in zip(nn_targets.shape, Kin.shape[: nn_targets.ndim]) if x == y)
+
+
+def _solve_multi(Kin, Kcross, Y, want=("mean",)):
+    """mgp_solve_multi_*: Kin (B, n, n), Kcross (B, n, m), Y (B, n, R) -> mean (B, m, R), Kcross^T Kin^-1 Kcross
+    (B, m, m)."""
+    _lib.require_cuda(Kin, Kcross, *(() if Y is None else (Y,)))
+    B, n, _ = Kin.shape
+    m = Kcross.shape[2]
+    dev, dt = Kin.device, Kin.dtype
+    K = Kin.contiguous()
+    Kc = Kcross.to(dt).contiguous()
+    Yc = None if Y is None else Y.to(dt).contiguous()
+    R = 0 if Yc is None else Yc.shape[2]
+    mean = torch.empty((B, m, R), device=dev, dtype=dt) if "mean" in want else None
+    kk = torch.empty((B, m, m), device=dev, dtype=dt) if "kk" in want else None
+    info = torch.zeros(1, device=dev, dtype=torch.int32)
+    rc = _lib.fn("solve_multi", dt)(
+        _lib.ptr(K), _lib.ptr(Kc), _lib.ptr(Yc), B, n, m, R, _lib.ptr(mean), _lib.ptr(kk), None, _lib.ptr(info),
+        _lib.stream_ptr(),
+    )
+    if rc == -2:
+        raise ValueError(f"a local system of {n} rows with {m} outputs does not fit the LDS-resident solve")
+    _lib.check(rc, "mgp_solve_multi")
+    _lib.raise_if_not_spd(info, "mgp_solve_multi")
+    return mean, kk
+
+
+def _multi_posterior_mean(Kin, Kcross, nn_targets):
+    """numpy.py:17-41 for any multi-output shape: flatten by the matching-dimension rule, solve, reshape."""
+    bdim = _matching_ndim(nn_targets, Kin)
+    in_shape, out_shape = tuple(Kin.shape[bdim:]), tuple(Kcross.shape[bdim:])
+    batch_shape = tuple(Kin.shape[: Kin.ndim - 2 * len(in_shape)])
+    extra_shape = tuple(nn_targets.shape[len(batch_shape) + len(in_shape):])
+    B, n, m, R = math.prod(batch_shape), math.prod(in_shape), math.prod(out_shape), math.prod(extra_shape)
+    if Kin.numel() != B * n * n or Kcross.numel() != B * n * m or nn_targets.numel() != B * n * R:
+        raise ValueError(  # (what the reference's reshape raises, numpy.py:33-35)
+            f"cannot flatten Kin {tuple(Kin.shape)}, Kcross {tuple(Kcross.shape)} and targets "
+            f"{tuple(nn_targets.shape)} into one batch of {n}-row systems"
+        )
+    mean, _ = _solve_multi(
+        Kin.reshape(B, n, n), Kcross.reshape(B, n, m), nn_targets.reshape(B, n, R), want=("mean",)
+    )
+    return mean.reshape(batch_shape + out_shape + extra_shape)
+
+
+def _multi_diagonal_variance(Kin, Kcross, Kout, batch_size: int = 1):
+    """numpy.py:44-67 for any multi-output shape: Kout - Kcross^T Kin^-1 Kcross, (batch, out, out)."""
+    in_dims = (Kin.ndim - batch_size) // 2
+    batch_shape = tuple(Kin.shape[:batch_size])
+    in_shape, out_shape = tuple(Kin.shape[batch_size + in_dims:]), tuple(Kcross.shape[batch_size + in_dims:])
+    B, n, m = math.prod(batch_shape), math.prod(in_shape), math.prod(out_shape)
+    _, kk = _solve_multi(Kin.reshape(B, n, n), Kcross.reshape(B, n, m), None, want=("kk",))
+    return _kout_minus(Kout, kk.reshape(batch_shape + out_shape + out_shape))
+
+
+def _kout_minus(Kout, kk):
+    """Kout - kk with the Kout the caller bound (a (m, m) block for the shear models, or a scalar)."""
+    if isinstance(Kout, torch.Tensor):
+        Kout = Kout.to(device=kk.device, dtype=kk.dtype)
+    elif not isinstance(Kout, (int, float)):
+        Kout = torch.as_tensor(lazy.force(Kout), device=kk.device, dtype=kk.dtype)
+    return Kout - kk
+
+
 def _muygps_posterior_mean(Kin, Kcross, nn_targets, **kwargs):
-    """numpy.py:17-41: Kcross^T Kin^-1 Y -> (b,) for (b,k) targets, (b,R) for (b,k,R)."""
+    """numpy.py:17-41: Kcross^T Kin^-1 Y -> (b,) for (b,k) targets, (b,R) for (b,k,R); multi-output shapes (the
+    shear models: Kin (b, in, k, in, k), Kcross (b, in, k, 3), targets (b, in, k)) -> (b, 3)."""
+    if isinstance(Kin, lazy.LazyShearCov) and isinstance(Kcross, lazy.LazyShearCov):
+        out = lazy_eval.shear_fused(Kin, Kcross, nn_targets)
+        if out is not None:
+            return out[0]
+    if isinstance(Kin, lazy.LazyShearCov) or (isinstance(Kin, torch.Tensor) and Kin.ndim not in (2, 3)):
+        Kin, Kcross, nn_targets = lazy.force(Kin), lazy.force(Kcross), lazy.force(nn_targets)
+        return _multi_posterior_mean(Kin, Kcross, nn_targets)
     if lazy.fused_triple(Kin, Kcross, nn_targets):
         out = lazy_eval.fused(Kin, Kcross, nn_targets)
         if out is not None:
@@ -51,7 +128,14 @@ def _muygps_posterior_mean(Kin, Kcross, nn_targets, **kwargs):
 
 
 def _muygps_diagonal_variance(Kin, Kcross, Kout, batch_size: int = 1, **kwargs):
-    """numpy.py:44-67: Kout - Kcross^T Kin^-1 Kcross -> (b,)."""
+    """numpy.py:44-67: Kout - Kcross^T Kin^-1 Kcross -> (b,); multi-output shapes -> the (b, out, out) block."""
+    if isinstance(Kin, lazy.LazyShearCov) and isinstance(Kcross, lazy.LazyShearCov):
+        kk = lazy_eval.shear_kk(Kin, Kcross)
+        if kk is not None:
+            return _kout_minus(Kout, kk)
+    if isinstance(Kin, lazy.LazyShearCov) or (isinstance(Kin, torch.Tensor) and Kin.ndim not in (2, 3)):
+        Kin, Kcross = lazy.force(Kin), lazy.force(Kcross)
+        return _multi_diagonal_variance(Kin, Kcross, Kout, batch_size)
     if isinstance(Kin, lazy.LazyCov) and isinstance(Kcross, lazy.LazyCov):
         var = lazy_eval.variance(Kin, Kcross)
         if var is not None:

@@ -93,6 +93,9 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     from muygpys_amd.fused import loocv_value_and_grad
     from muygpys_amd.optimize.loss import lool_fn, looph_fn, mse_fn, pseudo_huber_fn
 
+    if type(muygps.kernel).__name__ in ("ShearKernel", "ShearKernel2in3out"):
+        raise ValueError("analytic_gradient=True: the shear kernels have no backward kernel; optimise them with "
+                         "finite differences (analytic_gradient=False) or Bayes_optimize")
     ctx = getattr(obj_fn, "loocv_context", None)
     if ctx is None:
         raise ValueError("analytic_gradient=True: the objective was not built by make_loo_crossval_fn")

@@ -8,6 +8,11 @@ from muygpys_amd import _lib, lazy, lazy_eval
 from muygpys_amd._src.gp.muygps.hip import _solve
 
 
+def _refuse_shear(Kin):
+    if isinstance(Kin, lazy.LazyShearCov) or (isinstance(Kin, torch.Tensor) and Kin.ndim == 5):
+        raise ValueError("AnalyticScale is not implemented for the multi-output shear models; use FixedScale")
+
+
 def _ykinvy_sums(Kin, Y):
     """sum_b y_r^T Kin^-1 y_r per response column, as a device float64 vector (R,)."""
     _, _, yk, _ = _solve(Kin, None, Y, want=("ykinvy",))
@@ -16,6 +21,7 @@ def _ykinvy_sums(Kin, Y):
 
 def _analytic_scale_optim_unnormalized(Kin, nn_targets, **kwargs):
     """numpy.py:9-15: sum over batch AND response columns of y^T Kin^-1 y (0-d tensor)."""
+    _refuse_shear(Kin)
     Kin, nn_targets = lazy.force(Kin), lazy.force(nn_targets)
     _lib.require_cuda(Kin, nn_targets)
     Y = nn_targets if nn_targets.ndim == 3 else nn_targets[:, :, None]
@@ -27,6 +33,7 @@ def _analytic_scale_optim_unnormalized(Kin, nn_targets, **kwargs):
 def _analytic_scale_optim(Kin, nn_targets, batch_dim_count: int = 1, **kwargs):
     """numpy.py:18-34: / (batch_size * nn_count); like the reference, R > 1 is rejected
     (its reshape to (b, k, 1) raises ValueError)."""
+    _refuse_shear(Kin)
     if isinstance(Kin, lazy.LazyCov):
         out = lazy_eval.analytic_scale(Kin, nn_targets)
         if out is not None:

@@ -46,6 +46,8 @@ PER_FILE_FLAGS = {
     **{f: ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"]
        for f in ("mgp_backward_wave.hip", "mgp_backward_wave_f32_np32.hip", "mgp_backward_wave_f32_np64.hip")},
     "mgp_backward_dlt.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
+    # (the shear kernels' registers and LDS go into the report too: tests/test_gpu_shear.py reads them)
+    "mgp_shear.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 

@@ -154,6 +154,40 @@ int launch_fused_rhs_mf(const FusedArgs&, hipStream_t);  // fp32 prediction vari
 template <typename T> int launch_fused_wide(const FusedArgs&, hipStream_t);
 int launch_fused_wide64(const FusedArgs&, hipStream_t);  // fp64, two lanes per row
 int max_nn_count(int elem_size, int R);
+
+// mgp_shear.hip: the multi-output solve and the shear model
+struct SolveMultiArgs {
+  const void* Kin;    // (b, n, n), perturbed
+  const void* Kcross; // (b, n, m)
+  const void* Y;      // (b, n, R), or nullptr when R == 0
+  void* mean;         // (b, m, R)
+  void* kk;           // (b, m, m)
+  void* ykinvy;       // (b, R)
+  int* info;
+  int64_t b;
+  int n, m, R;
+};
+struct ShearArgs {
+  const void* feat_q;
+  const void* feat_nn;
+  const int64_t* batch_idx;
+  const int64_t* nn_idx;
+  const void* targets;
+  int64_t targets_stride;
+  int targets_batch;
+  void* mean;    // (b, 3)
+  void* kk;      // (b, 3, 3)
+  void* ykinvy;  // (b)
+  int* info;
+  int64_t b;
+  double length_scale, noise;
+  int k, in_count, noise_mode;
+};
+template <typename T>
+int launch_shear_tensor(const T* diffs, int64_t G, int n, int m, int variant, double ell, T* out, hipStream_t stream);
+template <typename T> int launch_solve_multi(const SolveMultiArgs&, hipStream_t);
+template <typename T> int launch_shear_posterior(const ShearArgs&, hipStream_t);
+int shear_max_nn_count(int elem_size, int in_count);
 int describe_fused_wave(int elem_size, int d, int k, int R, int packed, char* buf, int len);
 // the instantiation a posterior launcher actually put on the stream, per calling thread (mgp_last_kernel_name):
 // what served a call depends on more than the shape (batch thresholds of the run-time compiler, its disk cache,

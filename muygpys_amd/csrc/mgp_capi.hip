@@ -226,6 +226,37 @@ static int posterior_gen(const T* fq, const T* fn, const void* packed_q, int64_t
   return launch_fused_wave<T>(a, static_cast<hipStream_t>(stream));
 }
 
+template <typename T>
+static int shear_tensor(const T* diffs, int64_t G, int n, int m, int variant, double ls, T* out, void* stream) {
+  if (G < 0 || n < 0 || m < 0 || !(ls > 0.0)) return MGP_EINVAL;
+  if (variant < MGP_SHEAR_33 || variant > MGP_SHEAR_KCROSS23) return MGP_EINVAL;
+  if (G == 0 || n == 0 || m == 0) return MGP_OK;
+  if (!diffs || !out) return MGP_EINVAL;
+  return launch_shear_tensor<T>(diffs, G, n, m, variant, ls, out, S_(stream));
+}
+template <typename T>
+static int solve_multi(const T* Kin, const T* Kc, const T* Y, int64_t b, int n, int m, int R, T* mean, T* kk, T* yk,
+                       int* info, void* stream) {
+  if (b < 0 || n < 1 || m < 1 || R < 0) return MGP_EINVAL;
+  if (!Kin || !Kc || (R > 0 && !Y) || ((mean || yk) && R == 0) || (!mean && !kk && !yk)) return MGP_EINVAL;
+  if (b == 0) return MGP_OK;
+  SolveMultiArgs a{Kin, Kc, Y, mean, kk, yk, info, b, n, m, R};
+  return launch_solve_multi<T>(a, S_(stream));
+}
+template <typename T>
+static int shear_posterior(const T* fq, const T* fn, const int64_t* bi, const int64_t* ni, int64_t b, int k, int in,
+                           const T* tg, int64_t tstride, int tbatch, double ls, int noise_mode, double noise, T* mean,
+                           T* kk, T* yk, int* info, void* stream) {
+  if (b < 0 || k < 1 || (in != 2 && in != 3) || !(ls > 0.0) || !(noise >= 0.0)) return MGP_EINVAL;
+  if (noise_mode != MGP_SHEAR_NOISE_HOMOSCEDASTIC && noise_mode != MGP_SHEAR_NOISE_33) return MGP_EINVAL;
+  if (noise_mode == MGP_SHEAR_NOISE_33 && in != 3) return MGP_EINVAL;
+  if (!fq || !fn || !ni || !tg || !mean || !kk) return MGP_EINVAL;
+  if (!tbatch && tstride < in) return MGP_EINVAL;
+  if (b == 0) return MGP_OK;  // (launch_shear_posterior refuses a k beyond the LDS before any HIP call)
+  ShearArgs a{fq, fn, bi, ni, tg, tstride, tbatch, mean, kk, yk, info, b, ls, noise, k, in, noise_mode};
+  return launch_shear_posterior<T>(a, S_(stream));
+}
+
 extern "C" {
 
 const char* mgp_version(void) { return "muygpys_amd-hip 0.1 (gfx950)"; }
@@ -266,6 +297,10 @@ int mgp_posterior_kernel_name(int elem_size, int d, int k, int R, int packed, in
   else
     snprintf(buf, len, "mgp::fused_generic_kernel<%s>", t);
   return MGP_OK;
+}
+int mgp_shear_max_nn_count(int elem_size, int in_count) {
+  if ((elem_size != 4 && elem_size != 8) || (in_count != 2 && in_count != 3)) return MGP_EINVAL;
+  return shear_max_nn_count(elem_size, in_count);
 }
 int mgp_last_kernel_name(char* buf, int len) {
   if (!buf || len < 1) return MGP_EINVAL;
@@ -547,6 +582,22 @@ int mgp_max_nn_count_backward(int elem_size) { return max_nn_count_backward(elem
   }
 MGP_DEFINE_FAST(f32, float)
 MGP_DEFINE_FAST(f64, double)
+
+#define MGP_DEFINE_SHEAR(SUF, T)                                                                                    \
+  int mgp_shear_tensor_##SUF(const T* diffs, int64_t G, int n, int m, int variant, double ls, T* out, void* st) {     \
+    return shear_tensor<T>(diffs, G, n, m, variant, ls, out, st);                                                    \
+  }                                                                                                                  \
+  int mgp_solve_multi_##SUF(const T* Kin, const T* Kc, const T* Y, int64_t b, int n, int m, int R, T* mean, T* kk,   \
+                            T* yk, int* info, void* st) {                                                            \
+    return solve_multi<T>(Kin, Kc, Y, b, n, m, R, mean, kk, yk, info, st);                                           \
+  }                                                                                                                  \
+  int mgp_shear_posterior_##SUF(const T* fq, const T* fn, const int64_t* bi, const int64_t* ni, int64_t b, int k,    \
+                                int in, const T* tg, int64_t ts, int tb, double ls, int nm, double eps, T* mean,     \
+                                T* kk, T* yk, int* info, void* st) {                                                 \
+    return shear_posterior<T>(fq, fn, bi, ni, b, k, in, tg, ts, tb, ls, nm, eps, mean, kk, yk, info, st);            \
+  }
+MGP_DEFINE_SHEAR(f32, float)
+MGP_DEFINE_SHEAR(f64, double)
 
 MGP_DEFINE(f32, float)
 MGP_DEFINE(f64, double)

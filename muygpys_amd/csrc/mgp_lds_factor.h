@@ -82,17 +82,45 @@ __device__ inline void gather_tile_lds(T* X, int XP, const T* feat_q, const T* f
   }
 }
 
+// Row addressing of an LDS-resident system.  StridedRows: the padded square (row i at S + i * SP).
+// PackedRows: a packed lower triangle (row i at S + off[i], see packed_row_len) for systems whose
+// square does not fit LDS -- the multi-output (shear) systems of mgp_shear.hip.
+template <typename T>
+struct StridedRows {
+  T* S;
+  int SP;
+  __device__ __forceinline__ T* operator()(int i) const { return S + i * SP; }
+};
+template <typename T>
+struct PackedRows {
+  T* S;
+  const int* off;
+  __device__ __forceinline__ T* operator()(int i) const { return S + off[i]; }
+};
+
+// Length (elements) of row i of a packed system with k elimination columns: what factor_augmented_rows
+// touches -- a row i < k up to the end of its 4-column block (the bulk phase updates all four columns
+// of the diagonal block, the entries above the diagonal included), a trailing row its k columns -- as
+// an odd number of 16-byte slots (rows start 16-byte aligned; the odd count spreads a column of
+// consecutive rows over the banks, as lds_row_stride does for the square).
+template <typename T>
+__host__ __device__ inline int packed_row_len(int i, int k) {
+  constexpr int E = 16 / (int)sizeof(T);
+  const int len = i < k ? (i / 4 + 1) * 4 : k;
+  return (((len + E - 1) / E) | 1) * E;
+}
+
 // S: rows x SP in LDS (SP = lds_row_stride<T>(k), S 16-byte aligned).  piv: k entries of scratch.
 // All NT threads of the block call this.  Returns (to every thread) whether a non-positive / NaN
-// pivot was met.
+// pivot was met.  (factor_augmented_rows: the same on any row layout.)
 //
 // Left-looking by rows, blocked by JB = 4 columns: the bulk of a column's inner product -- the part
 // over the columns of earlier blocks -- is taken for four columns at once with 16-byte LDS reads
 // (one read of the thread's own row serves four columns; the four pivot rows are broadcasts), i.e.
 // 5 LDS instructions per 16 (fp32) multiply-adds instead of 32; the diagonal block is then
 // factorised redundantly by every thread (see below).
-template <typename T>
-__device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* piv, int* bad_flag, int tid, int NT) {
+template <typename T, typename Rows>
+__device__ inline bool factor_augmented_rows(Rows row, int k, int rows, T* piv, int* bad_flag, int tid, int NT) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
   constexpr int JB = 4;
@@ -102,11 +130,11 @@ __device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* pi
     const int jb = min(JB, k - j0);
     if (j0 > 0) {
       for (int i = j0 + tid; i < rows; i += NT) {
-        T* rowi = S + i * SP;
-        const T* r0 = S + (j0 + 0) * SP;
-        const T* r1 = S + (j0 + (jb > 1 ? 1 : 0)) * SP;
-        const T* r2 = S + (j0 + (jb > 2 ? 2 : 0)) * SP;
-        const T* r3 = S + (j0 + (jb > 3 ? 3 : 0)) * SP;
+        T* rowi = row(i);
+        const T* r0 = row(j0 + 0);
+        const T* r1 = row(j0 + (jb > 1 ? 1 : 0));
+        const T* r2 = row(j0 + (jb > 2 ? 2 : 0));
+        const T* r3 = row(j0 + (jb > 3 ? 3 : 0));
         // vector accumulators (packed FMAs, one horizontal sum at the end) and two 16-byte steps per
         // iteration with all ten reads issued before the first FMA: the one-step scalar form waited a
         // full LDS round trip for 20 plain VALU instructions
@@ -157,7 +185,7 @@ __device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* pi
 #pragma unroll
     for (int r = 0; r < JB; ++r)
 #pragma unroll
-      for (int c = 0; c <= r; ++c) D[r][c] = (r < jb) ? S[(j0 + r) * SP + j0 + c] : (r == c ? T(1) : T(0));
+      for (int c = 0; c <= r; ++c) D[r][c] = (r < jb) ? row(j0 + r)[j0 + c] : (r == c ? T(1) : T(0));
     bool bad = false;
     T inv[JB];
 #pragma unroll
@@ -182,7 +210,7 @@ __device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* pi
       for (int c = 0; c < jb; ++c) piv[j0 + c] = inv[c];
     }
     for (int i = j0 + tid; i < rows; i += NT) {
-      T* rowi = S + i * SP;
+      T* rowi = row(i);
       if (i < j0 + jb) {
         const int r = i - j0;
 #pragma unroll
@@ -212,6 +240,11 @@ __device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* pi
   return *bad_flag != 0;
 }
 
+template <typename T>
+__device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* piv, int* bad_flag, int tid, int NT) {
+  return factor_augmented_rows<T>(StridedRows<T>{S, SP}, k, rows, piv, bad_flag, tid, NT);
+}
+
 // mean (R), var, ykinvy (R) from the factored S: 1 + 2 R inner products of length k, each taken by
 // the whole first wave (lanes stride over the k entries, one cross-lane sum) -- one thread per output
 // walked its k entries alone, a serial chain of k LDS round trips at the end of every neighbourhood.
@@ -238,6 +271,56 @@ __device__ inline void emit_outputs_lds(const T* S, int SP, int k, int R, T kout
     for (int m = tid; m < k; m += MGP_WAVE) s += x[m] * y[m];
     s = wave_sum(s);
     if (tid == 0) *dst = bad ? num<T>::nan() : (o == 0 ? kout - s : s);
+  }
+}
+
+}  // namespace mgp
+
+namespace mgp {
+
+// The multi-output step after factor_augmented_rows(k = n, rows = n + m + R) on the system
+//   rows 0 .. n-1: K;  rows n .. n+m-1: the m columns of Kcross (transposed);  rows n+m ..: the R responses
+// Row n + a then holds z_a = L^-1 Kcross[:, a] and row n + m + r holds w_r = L^-1 y_r, so
+//   kk (m x m)    = Kcross^T K^-1 Kcross:  z_a . z_c     (both triangles written)
+//   mean (m x R)  = Kcross^T K^-1 Y:       z_a . w_r
+//   ykinvy (R)    = y_r^T K^-1 y_r:        w_r . w_r
+// One inner product of length n per wave at a time (lanes stride over n, one cross-lane sum); NaN
+// everywhere when the factorisation met a bad pivot.  Any output pointer may be NULL.
+template <typename T, typename Rows>
+__device__ inline void emit_block_outputs(Rows row, int n, int m, int R, bool bad, T* kk, T* mean, T* ykinvy, int tid,
+                                          int NT) {
+  const int wave = tid / MGP_WAVE, lane = tid - wave * MGP_WAVE, nw = NT / MGP_WAVE;
+  const int nkk = m * (m + 1) / 2, total = nkk + m * R + R;
+  for (int o = wave; o < total; o += nw) {
+    int x, y;
+    T* dst = nullptr;
+    T* dst2 = nullptr;
+    if (o < nkk) {
+      int a = 0;
+      while ((a + 1) * (a + 2) / 2 <= o) ++a;
+      const int c = o - a * (a + 1) / 2;
+      x = n + a, y = n + c;
+      if (kk != nullptr) dst = kk + a * m + c, dst2 = a != c ? kk + c * m + a : nullptr;
+    } else if (o < nkk + m * R) {
+      const int t = o - nkk, a = t / R, r = t - a * R;
+      x = n + a, y = n + m + r;
+      if (mean != nullptr) dst = mean + a * R + r;
+    } else {
+      const int r = o - nkk - m * R;
+      x = y = n + m + r;
+      if (ykinvy != nullptr) dst = ykinvy + r;
+    }
+    if (dst == nullptr) continue;  // uniform across the wave
+    const T* px = row(x);
+    const T* py = row(y);
+    T s = T(0);
+    for (int j = lane; j < n; j += MGP_WAVE) s += px[j] * py[j];
+    s = wave_sum(s);
+    if (lane == 0) {
+      const T v = bad ? num<T>::nan() : s;
+      *dst = v;
+      if (dst2 != nullptr) *dst2 = v;
+    }
   }
 }
 

@@ -24,6 +24,7 @@ matern_gen_fn = _K._matern_gen_fn
 
 homoscedastic_perturb = _N._homoscedastic_perturb
 heteroscedastic_perturb = _N._heteroscedastic_perturb
+shear_perturb33 = _N._shear_perturb33
 
 posterior_mean = _M._muygps_posterior_mean
 diagonal_variance = _M._muygps_diagonal_variance

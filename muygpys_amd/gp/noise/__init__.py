@@ -58,6 +58,20 @@ class HomoscedasticNoise(NamedParam, NoiseFn):
         NamedParam.append_lists(self, names, params, bounds)
 
 
+class ShearNoise33(HomoscedasticNoise):
+    """The shear models' nugget (gp/noise/shear.py): 2 eps on the convergence rows, eps on the two shears; applies
+    to the (b, 3, k, 3, k) Kin of ``ShearKernel`` (and to its lazy handle).  A trial ``noise=`` works as for
+    :class:`HomoscedasticNoise`."""
+
+    def __init__(
+        self,
+        val: Union[str, float],
+        bounds: Union[str, Tuple[float, float]] = "fixed",
+        _backend_fn: Callable = _ld.shear_perturb33,
+    ):
+        super().__init__(val, bounds, _backend_fn=_backend_fn)
+
+
 class HeteroscedasticNoise(TensorParam, NoiseFn):
     """Per-observation nugget: a (batch, nn) tensor aligned with the batch's neighbourhoods
     (build it with ``make_heteroscedastic_tensor``), never optimised."""
@@ -100,4 +114,4 @@ class NullNoise(ScalarParam, NoiseFn):
         return fn
 
 
-__all__ = ["HeteroscedasticNoise", "HomoscedasticNoise", "NoiseFn", "NullNoise"]
+__all__ = ["HeteroscedasticNoise", "HomoscedasticNoise", "NoiseFn", "NullNoise", "ShearNoise33"]

@@ -11,7 +11,7 @@ reference tree:
     hip_backend.install()               # before the first `import MuyGPyS.gp ...`
     from MuyGPyS.gp import MuyGPS       # now backed by the HIP kernels
 
-What a maintainer would commit instead is shown in INTEGRATION.md: eight three-line
+What a maintainer would commit instead is shown in INTEGRATION.md: nine three-line
 ``hip.py`` files and one ``elif`` in util.py.
 
 With ``lazy=True`` (the default) the tensor family returns the light handles of
@@ -29,7 +29,8 @@ import importlib
 import sys
 
 FAMILIES = (
-    "math", "gp.tensors", "gp.kernels", "gp.muygps", "gp.noise", "optimize.loss", "optimize.scale", "optimize.chassis",
+    "math", "gp.tensors", "gp.kernels", "gp.kernels.shear", "gp.muygps", "gp.noise", "optimize.loss", "optimize.scale",
+    "optimize.chassis",
 )
 
 

@@ -120,6 +120,7 @@ class LazyDiffs(_Lazy):
     data: Optional[torch.Tensor] = None
     data_indices: Optional[torch.Tensor] = None
     length_scale: Any = None  # float, or (d,) sequence / tensor
+    unit_axis: bool = False  # crosswise differences as (b, k, 1, d): ``diffs[..., None, :]`` of the shear functors
 
     @property
     def shape(self) -> Tuple[int, ...]:
@@ -128,7 +129,7 @@ class LazyDiffs(_Lazy):
         if self.reduced:
             return base
         d = 1 if self.nn_data.ndim == 1 else self.nn_data.shape[1]
-        return base + (d,)
+        return base + ((1, d) if self.unit_axis else (d,))
 
     @property
     def ndim(self) -> int:
@@ -144,6 +145,16 @@ class LazyDiffs(_Lazy):
 
     def with_length_scale(self, length_scale) -> "LazyDiffs":
         return replace(self, length_scale=length_scale)
+
+    def __getitem__(self, item):
+        # ``crosswise[..., None, :]``: the unit axis ShearKernel.__call__ inserts (experimental/shear.py:125-128)
+        if (
+            self.kind == "crosswise" and not self.reduced and self.length_scale is None and not self.unit_axis
+            and isinstance(item, tuple) and len(item) == 3 and item[0] is Ellipsis and item[1] is None
+            and item[2] == slice(None)
+        ):
+            return replace(self, unit_axis=True)
+        return self.materialize()[item]
 
     def reduce(self, metric: str) -> "LazyDiffs":
         """``_l2`` / ``_F2`` of a difference handle."""
@@ -186,6 +197,8 @@ class LazyDiffs(_Lazy):
         from muygpys_amd._src.gp.tensors import hip as T
 
         lsv = self._ls_vector()
+        if self.unit_axis:
+            return replace(self, unit_axis=False).materialize()[..., None, :]
         if not self.reduced:
             raw = self._raw()
             if self.length_scale is None:
@@ -265,21 +278,98 @@ class LazyTargets(_Lazy):
 
     targets: torch.Tensor
     nn_indices: torch.Tensor
+    swapped: bool = False  # (b, R, k) instead of (b, k, R): the shear models' layout
 
     @property
     def shape(self):
-        return tuple(self.nn_indices.shape) + tuple(self.targets.shape[1:])
+        s = tuple(self.nn_indices.shape) + tuple(self.targets.shape[1:])
+        return (s[0], s[2], s[1]) if self.swapped else s
 
     @property
     def ndim(self):
         return len(self.shape)
 
+    def swapaxes(self, a, b):
+        """``swapaxes(-2, -1)`` of (b, k, R) responses stays a handle (the shear models' (b, R, k) targets,
+        tests/experimental/shear.py of the reference); anything else is done on the gathered tensor."""
+        if self.ndim == 3 and {a % 3, b % 3} == {1, 2}:
+            return replace(self, swapped=not self.swapped)
+        return self.materialize().swapaxes(a, b)
+
     def materialize(self) -> torch.Tensor:
-        return torch.Tensor.__getitem__(self.targets.as_subclass(torch.Tensor), self.nn_indices)
+        out = torch.Tensor.__getitem__(self.targets.as_subclass(torch.Tensor), self.nn_indices)
+        return out.swapaxes(-2, -1) if self.swapped else out
+
+
+@dataclass(eq=False)
+class LazyShearCov(_Lazy):
+    """What a shear kernel (``_shear_33_fn`` / ``_shear_Kin23_fn`` / ``_shear_Kcross23_fn``) of a
+    difference handle stands for: the (b, in, k, in, k) Kin of a pairwise handle or the (b, in, k, 3)
+    Kcross of a crosswise one (squeezed like the reference).  ``model`` "33" observes (kappa, gamma1,
+    gamma2), "23" (gamma1, gamma2).  ``noise_mode`` "shear33" / "homoscedastic" is attached by the
+    noise family; the cache dict is shared by the decorated copies of one Kin (one fused launch per
+    evaluation, ``lazy_eval.shear_fused``)."""
+
+    diffs: LazyDiffs
+    model: str
+    length_scale: float
+    noise: Any = None
+    noise_mode: Optional[str] = None
+    cache: Dict = field(default_factory=dict, repr=False, compare=False)
+
+    @property
+    def in_count(self) -> int:
+        return 3 if self.model == "33" else 2
+
+    @property
+    def kind(self) -> str:
+        return self.diffs.kind
+
+    @property
+    def shape(self):
+        b, k = self.diffs.nn_indices.shape
+        i = self.in_count
+        full = (b, i, k, i, k) if self.kind == "pairwise" else (b, i, k, 3)
+        return tuple(v for v in full if v != 1)
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+    @property
+    def dtype(self):
+        return self.diffs.dtype
+
+    @property
+    def device(self):
+        return self.diffs.device
+
+    def perturbed(self, noise, noise_mode: str) -> "LazyShearCov":
+        return LazyShearCov(self.diffs, self.model, self.length_scale, noise, noise_mode, self.cache)
+
+    def materialize(self) -> torch.Tensor:
+        """The shear tensor kernels on the materialised differences [+ nugget]."""
+        from muygpys_amd._lib import SHEAR_33, SHEAR_KCROSS23, SHEAR_KIN23
+        from muygpys_amd._src.gp.kernels.shear import hip as K
+        from muygpys_amd._src.gp.noise import hip as N
+
+        d = replace(self.diffs, unit_axis=False).materialize()
+        if self.kind == "crosswise":
+            d = d[..., None, :]
+            variant = SHEAR_33 if self.model == "33" else SHEAR_KCROSS23
+        else:
+            variant = SHEAR_33 if self.model == "33" else SHEAR_KIN23
+        out = K._tensor(d, variant, self.length_scale)
+        if self.noise is not None and self.kind == "pairwise":
+            if self.noise_mode == "shear33":
+                out = N._shear_perturb33(out, float(self.noise))
+            else:
+                out = N._homoscedastic_perturb(out, float(self.noise))
+        return out
 
 
 def is_lazy(x) -> bool:
-    return isinstance(x, (LazyDiffs, LazyCov, LazyTargets))
+    return isinstance(x, (LazyDiffs, LazyCov, LazyTargets, LazyShearCov))
 
 
 def force(x):
@@ -303,7 +393,7 @@ def fused_triple(Kin, Kcross, nn_targets) -> bool:
     a, c = Kin.diffs, Kcross.diffs
     b, k = a.nn_indices.shape
     if isinstance(nn_targets, LazyTargets):
-        if not _same_tensor(a.nn_indices, nn_targets.nn_indices):
+        if nn_targets.swapped or not _same_tensor(a.nn_indices, nn_targets.nn_indices):
             return False
     elif not (isinstance(nn_targets, torch.Tensor) and tuple(nn_targets.shape[:2]) == (b, k)):
         return False

@@ -195,3 +195,105 @@ def analytic_scale(Kin: lazy.LazyCov, nn_targets):
     # under integration.install() the value goes to the reference's AnalyticScale._set, which calls
     # len() on it (gp/hyperparameter/scale.py:47-52): a 0-d tensor refuses that, a (1,) tensor passes
     return val.reshape(1) if config.state.lazy_tensors else val
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The shear models: one mgp_shear_posterior_* launch per (noise, Kcross, responses), shared by the mean and the
+# variance of one evaluation through the Kin cache, as above.
+
+
+def _shear_pair(Kin: lazy.LazyShearCov, Kcross: lazy.LazyShearCov) -> bool:
+    a, c = Kin.diffs, Kcross.diffs
+    return (
+        a.kind == "pairwise" and c.kind == "crosswise" and Kin.model == Kcross.model
+        and Kin.length_scale == Kcross.length_scale
+        and lazy._same_tensor(a.nn_indices, c.nn_indices) and lazy._same_tensor(a.nn_data, c.nn_data)
+    )
+
+
+def _shear_targets(Kin: lazy.LazyShearCov, nn_targets):
+    """(tensor, row stride, column offset, gathered) the kernel reads the observed responses from, or None."""
+    a = Kin.diffs
+    b, k = a.nn_indices.shape
+    i = Kin.in_count
+    if isinstance(nn_targets, lazy.LazyTargets):
+        # the (b, in, k) responses of a table with exactly the observed columns, as the reference requires
+        # (a (n, 3) table of a 2-in model is refused here and by the materialised route alike)
+        t = nn_targets.targets
+        if not (nn_targets.swapped and t.ndim == 2 and t.shape[1] == i
+                and lazy._same_tensor(nn_targets.nn_indices, a.nn_indices)):
+            return None
+        return t, t.stride(0), 0, False
+    if isinstance(nn_targets, torch.Tensor) and tuple(nn_targets.shape) == (b, i, k):
+        return nn_targets, 0, 0, True
+    return None
+
+
+def _shear_launch(Kin, Kcross, tg, stride, col, gathered):
+    from . import _lib
+    from ._src.gp.tensors import hip as T
+
+    a, c = Kin.diffs, Kcross.diffs
+    for table in (a.nn_data, c.data):  # (the kernel reads both tables as (rows, 2))
+        if table.ndim != 2 or table.shape[1] != 2:
+            raise ValueError(f"shear kernels need 2-D features; got a feature table of shape {tuple(table.shape)}")
+    dt, dev = a.dtype, a.device
+    b, k = a.nn_indices.shape
+    fq, fn = c.data.to(dt).contiguous(), a.nn_data.contiguous()
+    bi, ni = T._idx(c.data_indices), T._idx(a.nn_indices)
+    if gathered:
+        tg = tg.to(dt).contiguous()
+    elif tg.dtype != dt or tg.stride(1) != 1:
+        tg = tg.to(dt).contiguous()
+        stride = tg.stride(0)
+    tptr = _lib.C.c_void_p(tg.data_ptr() + col * tg.element_size())
+    noise = 0.0 if Kin.noise is None else float(Kin.noise)
+    mode = _lib.SHEAR_NOISE_33 if Kin.noise_mode == "shear33" else _lib.SHEAR_NOISE_HOMOSCEDASTIC
+    mean = torch.empty((b, 3), device=dev, dtype=dt)
+    kk = torch.empty((b, 3, 3), device=dev, dtype=dt)
+    yk = torch.empty((b,), device=dev, dtype=dt)
+    info = torch.zeros(1, device=dev, dtype=torch.int32)
+    rc = _lib.fn("shear_posterior", dt)(
+        _lib.ptr(fq), _lib.ptr(fn), _lib.ptr(bi), _lib.ptr(ni), b, k, Kin.in_count, tptr, stride, int(gathered),
+        float(Kin.length_scale), mode, noise, _lib.ptr(mean), _lib.ptr(kk), _lib.ptr(yk), _lib.ptr(info),
+        _lib.stream_ptr(),
+    )
+    if rc == -2:
+        limit = _lib.shear_max_nn_count(dt, Kin.in_count)
+        raise ValueError(f"the fused shear posterior serves nn_count <= {limit} at {dt} with {Kin.in_count} inputs; got {k}")
+    _lib.check(rc, "mgp_shear_posterior")
+    _lib.raise_if_not_spd(info, "fused shear posterior")
+    return mean, kk, yk, info
+
+
+def shear_fused(Kin: lazy.LazyShearCov, Kcross: lazy.LazyShearCov, nn_targets):
+    """(mean (b, 3), Kcross^T K^-1 Kcross (b, 3, 3), y^T K^-1 y (b), info) of a lazy shear triple, computed once per
+    (noise, Kcross, responses); None when the handles do not describe one launch (the caller materialises)."""
+    if not _shear_pair(Kin, Kcross):
+        return None
+    spec = _shear_targets(Kin, nn_targets)
+    if spec is None:
+        return None
+    tg = spec[0]
+    nk = (Kin.noise_mode, 0.0 if Kin.noise is None else float(Kin.noise))
+    entries = Kin.cache.setdefault("shear", [])
+    for e in entries:
+        if e[0] == nk and e[1] is Kcross.diffs and e[2] is tg and e[3] == _version(tg) and e[4] == spec[1:]:
+            return e[5]
+    value = _shear_launch(Kin, Kcross, *spec)
+    Kin.cache["shear"] = [(nk, Kcross.diffs, tg, _version(tg), spec[1:], value)]  # one evaluation at a time
+    return value
+
+
+def shear_kk(Kin: lazy.LazyShearCov, Kcross: lazy.LazyShearCov):
+    """Kcross^T K^-1 Kcross (b, 3, 3) of a lazy shear pair: from the evaluation's launch when the mean has run, else a
+    launch of its own on zero responses; None when the pair does not describe one launch."""
+    if not _shear_pair(Kin, Kcross):
+        return None
+    nk = (Kin.noise_mode, 0.0 if Kin.noise is None else float(Kin.noise))
+    for e in Kin.cache.get("shear", []):
+        if e[0] == nk and e[1] is Kcross.diffs:
+            return e[5][1]
+    b, k = Kin.diffs.nn_indices.shape
+    zeros = torch.zeros((b, Kin.in_count, k), device=Kin.device, dtype=Kin.dtype)
+    return _shear_launch(Kin, Kcross, zeros, 0, 0, True)[1]
