@@ -686,6 +686,62 @@ int mgp_shear_posterior_f64(const double* feat_q, const double* feat_nn, const i
  * arguments. */
 int mgp_shear_max_nn_count(int elem_size, int in_count);
 
+/* ---------------------------------------------------------------------------
+ * Classification (one-hot responses, R >= 2 classes).
+ * ------------------------------------------------------------------------- */
+enum mgp_class_loss { MGP_CLASS_LOSS_CROSS_ENTROPY = 0, MGP_CLASS_LOSS_MSE = 1 };
+
+/* The classification loss sums of a (b, R) prediction, in fp64.  Replaces _cross_entropy_fn
+ * (_src/optimize/loss/numpy.py:12-19: scipy softmax + sklearn log_loss(normalize=False)), _mse_fn (:22-31) and
+ * _pseudo_huber_fn (:64-72) on several response columns; sharded, the six numbers all-reduce as
+ * _src/optimize/loss/mpi.py:20-44 does.
+ *   pred (b, R).  The target row of neighbourhood i is target + row * target_stride_bytes with row = batch_idx[i]
+ *   (batch_idx NULL: row = i): a (b, R) tensor (stride R * sizeof(T)), or the label table with the batch's rows
+ *   (as mgp_loocv_tree_* takes its responses).
+ *   partials[6] = { sum cross-entropy, sum r^2 over the b R entries, b R, b,
+ *                   rows whose argmax equals the target's argmax, sum pseudo-Huber(r) },  r = pred - target.
+ *   Cross-entropy of a row: one_hot = target > 0; p = softmax(row), max-subtracted, in fp64; p clipped to
+ *   [eps, 1 - eps], eps the machine epsilon of T (what log_loss does); - sum_c one_hot_c log p_c.
+ *   grad_pred (b, R) or NULL: grad_scale times the cotangent of the row term of `loss_id`:
+ *     cross-entropy  sum over the one-hot classes c whose p_c the clip left alone of (p_j - delta_cj)
+ *     mse            2 r   (grad_scale = 1 / (b R) for the mean, with the GLOBAL count when sharded)
+ *   scratch: device double[mgp_reduce_scratch_doubles()], required: per-workgroup sums added in workgroup
+ *   order by a second launch, no float atomics -- equal inputs give equal bits.
+ *   b = 0 is served: the six sums are zero, and the per-row pointers may then be NULL.
+ * MGP_EUNSUPPORTED for R < 2 (the loss is defined for two or more labels) and R > 62. */
+int mgp_class_sums_f32(const float* pred, const void* target, int64_t target_stride_bytes, const int64_t* batch_idx,
+                       int64_t b, int R, int loss_id, double grad_scale, double huber_delta, float* grad_pred,
+                       double* partials, double* scratch, void* stream);
+int mgp_class_sums_f64(const double* pred, const void* target, int64_t target_stride_bytes, const int64_t* batch_idx,
+                       int64_t b, int R, int loss_id, double grad_scale, double huber_delta, double* grad_pred,
+                       double* partials, double* scratch, void* stream);
+
+/* Label agreement and compaction: which neighbourhoods still need the solve.  Replaces
+ * examples/classify.py:577-591 (classify_any) and examples/two_class_classify_uq.py:389-407 (classify_two_class_uq).
+ *   labels (n, R) label table, nn_idx (b, k) (an index outside [0, n) is clamped into it).
+ *   pred (b, R): the FIRST neighbour's label row, for every neighbourhood.
+ *   nonconstant (b) bytes: 1 iff max != min of label COLUMN 0 over the k neighbours -- the reference's rule,
+ *     literally: with three or more classes a neighbourhood that mixes classes 1 and 2 counts as constant.
+ *   count (1): m, the number of non-constant neighbourhoods; sel (capacity b): their indices, ascending, in
+ *   sel[0 .. m); nn_sel (capacity b x k): nn_sel[i, :] = nn_idx[sel[i], :].
+ *   scratch: device buffer of mgp_reduce_scratch_doubles() doubles.
+ *   b = 0 writes count = 0 only; the (b, ...) pointers may then be NULL.
+ * Three launches (flags + per-chunk counts, one scan workgroup, write); kernel boundaries are the only
+ * synchronisation. */
+int mgp_class_partition_f32(const float* labels, int64_t n, int R, const int64_t* nn_idx, int64_t b, int k,
+                            float* pred, unsigned char* nonconstant, int64_t* count, int64_t* sel, int64_t* nn_sel,
+                            void* scratch, void* stream);
+int mgp_class_partition_f64(const double* labels, int64_t n, int R, const int64_t* nn_idx, int64_t b, int k,
+                            double* pred, unsigned char* nonconstant, int64_t* count, int64_t* sel, int64_t* nn_sel,
+                            void* scratch, void* stream);
+/* dst_mean[sel[i], :] = src_mean[i, :] for i < m, and dst_var[sel[i]] = src_var[i] when both are given: the
+ * solved rows back into the (b, R) prediction (examples/classify.py:592-599, two_class_classify_uq.py:408-421).
+ * m = 0 does nothing. */
+int mgp_class_scatter_f32(const float* src_mean, const float* src_var, const int64_t* sel, int64_t m, int64_t b,
+                          int R, float* dst_mean, float* dst_var, void* stream);
+int mgp_class_scatter_f64(const double* src_mean, const double* src_var, const int64_t* sel, int64_t m, int64_t b,
+                          int R, double* dst_mean, double* dst_var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

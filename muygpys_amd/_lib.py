@@ -81,7 +81,11 @@ _SIGS = {
     "shear_tensor": [_p, _l, _i, _i, _i, _d, _p, _p],
     "solve_multi": [_p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p],
     "shear_posterior": [_p, _p, _p, _p, _l, _i, _i, _p, _l, _i, _d, _i, _d, _p, _p, _p, _p, _p],
+    "class_sums": [_p, _p, _l, _p, _l, _i, _i, _d, _d, _p, _p, _p, _p],
+    "class_partition": [_p, _l, _i, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p],
+    "class_scatter": [_p, _p, _p, _l, _l, _i, _p, _p, _p],
 }
+CLASS_LOSS_IDS = {"cross_entropy": 0, "mse": 1}
 SHEAR_33, SHEAR_KIN23, SHEAR_KCROSS23 = 0, 1, 2
 SHEAR_NOISE_HOMOSCEDASTIC, SHEAR_NOISE_33 = 0, 1
 
@@ -345,6 +349,60 @@ def loss_sums(pred, target, var, scale_dev, huber_delta: float, looph_delta: flo
         "mgp_loss_sums",
     )
     return out
+
+
+def class_sums(pred, target, target_stride_bytes: int, batch_idx, loss: str = "cross_entropy", grad_scale: float = 1.0,
+               want_grad: bool = False, huber_delta: float = 1.5):
+    """(partials, grad_pred or None) of ``mgp_class_sums_*``: the six fp64 classification sums of a contiguous (b, R)
+    prediction -- [sum cross-entropy, sum r^2, b R, b, argmax agreements, sum pseudo-Huber] -- and, on request,
+    ``grad_scale`` times the cotangent of ``loss``.  The target rows sit ``target_stride_bytes`` apart, selected by
+    ``batch_idx`` (None: row i)."""
+    b, R = pred.shape
+    out = torch.empty(6, device=pred.device, dtype=torch.float64)
+    grad = torch.empty_like(pred) if want_grad else None
+    scratch = reduce_scratch(pred.device)
+    rc = fn("class_sums", pred.dtype)(
+        ptr(pred), ptr(target), int(target_stride_bytes), ptr(batch_idx), b, R, CLASS_LOSS_IDS[loss], float(grad_scale),
+        float(huber_delta), ptr(grad), ptr(out), ptr(scratch), stream_ptr(),
+    )
+    if rc == -2:
+        raise NotImplementedError(f"the classification sums serve 2 to 62 response columns; got {R}")
+    check(rc, "mgp_class_sums")
+    return out, grad
+
+
+def class_partition(labels, nn_idx):
+    """``mgp_class_partition_*`` on a contiguous (n, R) label table and (b, k) int64 neighbour indices: (pred (b, R) =
+    the first neighbour's label row, nonconstant (b) bool, count (1) int64 on the device, sel (b) int64, nn_sel (b, k)
+    int64); the first ``count`` entries of ``sel`` / rows of ``nn_sel`` are the non-constant neighbourhoods, ascending."""
+    n, R = labels.shape
+    b, k = nn_idx.shape
+    dev = labels.device
+    pred = torch.empty((b, R), device=dev, dtype=labels.dtype)
+    flags = torch.empty(b, device=dev, dtype=torch.uint8)
+    count = torch.zeros(1, device=dev, dtype=torch.int64)
+    sel = torch.empty(b, device=dev, dtype=torch.int64)
+    nn_sel = torch.empty((b, k), device=dev, dtype=torch.int64)
+    scratch = reduce_scratch(dev)
+    check(
+        fn("class_partition", labels.dtype)(
+            ptr(labels), n, R, ptr(nn_idx), b, k, ptr(pred), ptr(flags), ptr(count), ptr(sel), ptr(nn_sel), ptr(scratch),
+            stream_ptr(),
+        ),
+        "mgp_class_partition",
+    )
+    return pred, flags.view(torch.bool), count, sel, nn_sel
+
+
+def class_scatter(src_mean, src_var, sel, dst_mean, dst_var) -> None:
+    """``dst_mean[sel] = src_mean`` (and the variances, when given) through ``mgp_class_scatter_*``."""
+    m, R = src_mean.shape
+    check(
+        fn("class_scatter", src_mean.dtype)(
+            ptr(src_mean), ptr(src_var), ptr(sel), m, dst_mean.shape[0], R, ptr(dst_mean), ptr(dst_var), stream_ptr()
+        ),
+        "mgp_class_scatter",
+    )
 
 
 def require_cuda(*tensors):

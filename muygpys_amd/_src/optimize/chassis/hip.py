@@ -73,7 +73,9 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     """``x -> (loss, d loss / d x)`` for scipy's ``jac=True``: one fused LOOCV evaluation and one backward launch
     (``muygpys_amd.fused.loocv_value_and_grad``) instead of ``len(x) + 1`` evaluations per iteration.  The objective
     must be what ``make_loo_crossval_fn`` builds on lazy handles (``obj_fn.loocv_context``); the loss any of
-    ``lool_fn``, ``mse_fn``, ``pseudo_huber_fn``, ``looph_fn`` (with their ``boundary_scale``); the free parameters
+    ``lool_fn``, ``mse_fn``, ``pseudo_huber_fn``, ``looph_fn`` (with their ``boundary_scale``) on one response, or
+    ``cross_entropy_fn`` / ``mse_fn`` on the one-hot columns of a classifier (``fused.class_value_and_grad``: the
+    posterior, one ``mgp_class_sums_*`` launch, one backward launch); the free parameters
     length scales (``length_scale`` / ``length_scale{i}``) of a closed-form kernel and / or the homoscedastic ``noise``
     -- anything else raises (there is no silent fall-back to finite differences: the caller asked for an analytic
     gradient).  What the reference's torch autograd route differentiates (torch/muygps_layer.py:129-164), here for the
@@ -90,8 +92,8 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     ``y^T K^-1 y``).  A ``scale_fn`` that is neither of the two closures ``ScaleFn.get_opt_fn`` returns is refused."""
     from muygpys_amd import distributed as D
     from muygpys_amd import lazy, lazy_eval
-    from muygpys_amd.fused import loocv_value_and_grad
-    from muygpys_amd.optimize.loss import lool_fn, looph_fn, mse_fn, pseudo_huber_fn
+    from muygpys_amd.fused import class_value_and_grad, loocv_value_and_grad
+    from muygpys_amd.optimize.loss import cross_entropy_fn, lool_fn, looph_fn, mse_fn, pseudo_huber_fn
 
     if type(muygps.kernel).__name__ in ("ShearKernel", "ShearKernel2in3out"):
         raise ValueError("analytic_gradient=True: the shear kernels have no backward kernel; optimise them with "
@@ -99,7 +101,8 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     ctx = getattr(obj_fn, "loocv_context", None)
     if ctx is None:
         raise ValueError("analytic_gradient=True: the objective was not built by make_loo_crossval_fn")
-    loss = {id(lool_fn): "lool", id(mse_fn): "mse", id(pseudo_huber_fn): "pseudo_huber", id(looph_fn): "looph"}.get(id(ctx["loss_fn"]))
+    loss = {id(lool_fn): "lool", id(mse_fn): "mse", id(pseudo_huber_fn): "pseudo_huber", id(looph_fn): "looph",
+            id(cross_entropy_fn): "cross_entropy"}.get(id(ctx["loss_fn"]))
     if loss is None or ctx["target_mask"] is not None:
         raise ValueError("analytic_gradient=True: the gradient is written out for lool_fn, mse_fn, pseudo_huber_fn and "
                          "looph_fn (no target mask)")
@@ -129,6 +132,11 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
         raise ValueError("analytic_gradient=True: homoscedastic noise")
     stored = float(stored.item()) if hasattr(stored, "item") else float(stored)
     reduce_fn = D.reduce_if_sharded_ if D.reductions_active() else None
+    labels = nn_t.targets
+    # classification objectives: the cross-entropy, and the mse of several one-hot columns (fused.class_value_and_grad)
+    classify = loss == "cross_entropy" or (loss == "mse" and labels.ndim == 2 and labels.shape[1] > 1)
+    if loss == "cross_entropy" and (labels.ndim != 2 or labels.shape[1] < 2):
+        raise ValueError("analytic_gradient=True: cross_entropy_fn is only defined for two or more labels")
 
     def value_and_grad(x_array, *args):
         hyper = {h: float(x_array[i]) for i, h in enumerate(x0_names) if i != noise_at}
@@ -137,6 +145,11 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
             raise ValueError("analytic_gradient=True: the kernel did not stay a lazy handle")
         spec = lazy_eval._spec(Kin)
         spec.noise = stored if noise_at is None else float(x_array[noise_at])
+        if classify:  # (no sigma^2 in these losses: the trial noise is the only noise)
+            value, g_ls, g_noise = class_value_and_grad(spec, pair.nn_data, labels, cross.data_indices, pair.nn_indices,
+                                                        loss=loss, reduce_fn=reduce_fn)
+            grad = [g_noise if j == noise_at else g_ls[index[j]] for j in range(len(x0_names))]
+            return value, np.array(grad, dtype=np.float64)
         value, g_ls, g_noise = loocv_value_and_grad(spec, pair.nn_data, nn_t.targets, cross.data_indices, pair.nn_indices,
                                                     loss=loss, reduce_fn=reduce_fn, scale=scale_mode,
                                                     boundary_scale=boundary_scale,

@@ -1,7 +1,7 @@
 """hip implementation of the loss family (reference: _src/optimize/loss/numpy.py).
 
-One fp64 reduction kernel (``mgp_loss_sums_*``) produces every sum the losses need; each
-function below picks its entry.  Results are 0-d device tensors of the input dtype, like
+One fp64 reduction kernel (``mgp_loss_sums_*``) produces every sum the regression losses need; each
+function below picks its entry.  The cross-entropy of a classifier comes from ``mgp_class_sums_*``.  Results are 0-d device tensors of the input dtype, like
 the torch backend returns.
 """
 
@@ -87,9 +87,56 @@ class _MseMean(torch.autograd.Function):
         return g * 2.0 * (p - t.to(p.dtype).reshape(p.shape)) / ctx.count, None
 
 
+def _class_sums_and_count(predictions, targets, want_grad=False):
+    """(the six fp64 classification sums, cotangent or None): the sums global when the batch is sharded over ranks,
+    through the path ``_sums_and_count`` uses."""
+    _lib.require_cuda(predictions, targets)
+    if predictions.ndim != 2 or predictions.shape[1] < 2:
+        raise NotImplementedError(
+            "The cross-entropy loss is only defined for two or more labels: predictions must have shape "
+            f"(batch_count, class_count >= 2), got {tuple(predictions.shape)}."
+        )
+    p = predictions.contiguous()
+    t = targets.to(p.dtype).contiguous()
+    if t.shape != p.shape:
+        raise ValueError(f"predictions {tuple(p.shape)} and targets {tuple(t.shape)} do not conform")
+    out, grad = _lib.class_sums(p, t, p.shape[1] * p.element_size(), None, "cross_entropy", 1.0, want_grad)
+    from muygpys_amd import distributed as _D
+
+    if _D.reductions_active():
+        # sharded batch: the sum is global, like the reference's mpi backend (_src/optimize/loss/mpi.py:37-44)
+        _D.reduce_if_sharded_(out)
+    return out, grad
+
+
+class _CrossEntropySum(torch.autograd.Function):
+    """The summed cross-entropy with ``mgp_class_sums_*`` as forward and the kernel's own cotangent as backward (the
+    same launch writes both), so a deep-kernel loop can call ``loss.backward()`` on it like on ``_LoolSum``."""
+
+    @staticmethod
+    def forward(ctx, predictions, targets):
+        sums, grad = _class_sums_and_count(predictions.detach(), targets, want_grad=True)
+        ctx.save_for_backward(grad)
+        return sums[0].to(predictions.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return g * grad, None
+
+
 def _cross_entropy_fn(predictions, targets, **kwargs):
-    """numpy.py:12-19 calls sklearn.metrics.log_loss (classification only): out of scope."""
-    raise NotImplementedError("The hip backend does not implement the cross-entropy loss.")
+    """numpy.py:12-19, the NUMPY form to the letter: ``one_hot = targets > 0``, ``p = softmax(predictions, axis=1)``,
+    ``log_loss(one_hot, p, normalize=False)`` = ``-sum one_hot * log(clip(p, eps, 1 - eps))`` with eps the machine
+    epsilon of the prediction dtype.  (The reference's torch backend computes another quantity -- it adds
+    ``(1 - y) log(1 - p)`` and averages over the classes; it is not what is followed here.)  The sum is a 0-d device
+    tensor of the input dtype.  Fewer than two response columns raise NotImplementedError: the reference documents
+    the loss as only defined for two or more labels."""
+    if _wants_grad(predictions):
+        if predictions.ndim != 2 or predictions.shape[1] < 2:
+            _class_sums_and_count(predictions, targets)  # (raises)
+        return _CrossEntropySum.apply(predictions, targets)
+    return _class_sums_and_count(predictions, targets)[0][0].to(predictions.dtype)
 
 
 def _mse_fn(predictions, targets, **kwargs):

@@ -48,6 +48,8 @@ PER_FILE_FLAGS = {
     "mgp_backward_dlt.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
     # (the shear kernels' registers and LDS go into the report too: tests/test_gpu_shear.py reads them)
     "mgp_shear.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the classification kernels': tests/test_gpu_classify.py checks that none of them spills)
+    "mgp_classify.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 

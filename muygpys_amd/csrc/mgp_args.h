@@ -188,6 +188,18 @@ int launch_shear_tensor(const T* diffs, int64_t G, int n, int m, int variant, do
 template <typename T> int launch_solve_multi(const SolveMultiArgs&, hipStream_t);
 template <typename T> int launch_shear_posterior(const ShearArgs&, hipStream_t);
 int shear_max_nn_count(int elem_size, int in_count);
+// mgp_classify.hip: classification loss sums, label agreement + compaction, scatter of the solved rows
+static const int kClassMaxR = 62;  // the most responses a forward kernel carries (k + 1 + R <= 64 slots at k = 1)
+template <typename T>
+int launch_class_sums(const T* pred, const void* target, int64_t tstride, const int64_t* batch_idx, int64_t b, int R,
+                      int loss_id, double grad_scale, double hd, T* grad_pred, double* out, double* scratch, hipStream_t);
+template <typename T>
+int launch_class_partition(const T* labels, int64_t n, int R, const int64_t* nn_idx, int64_t b, int k, T* pred,
+                           unsigned char* nonconstant, int64_t* count, int64_t* sel, int64_t* nn_sel, void* scratch,
+                           hipStream_t);
+template <typename T>
+int launch_class_scatter(const T* src_mean, const T* src_var, const int64_t* sel, int64_t m, int64_t b, int R, T* dst_mean,
+                         T* dst_var, hipStream_t);
 int describe_fused_wave(int elem_size, int d, int k, int R, int packed, char* buf, int len);
 // the instantiation a posterior launcher actually put on the stream, per calling thread (mgp_last_kernel_name):
 // what served a call depends on more than the shape (batch thresholds of the run-time compiler, its disk cache,

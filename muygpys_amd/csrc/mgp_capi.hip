@@ -599,6 +599,35 @@ MGP_DEFINE_FAST(f64, double)
 MGP_DEFINE_SHEAR(f32, float)
 MGP_DEFINE_SHEAR(f64, double)
 
+#define MGP_DEFINE_CLASS(SUF, T)                                                                                    \
+  int mgp_class_sums_##SUF(const T* pred, const void* target, int64_t ts, const int64_t* bi, int64_t b, int R,       \
+                           int loss_id, double grad_scale, double hd, T* grad_pred, double* partials,                \
+                           double* scratch, void* st) {                                                              \
+    if (b < 0 || R < 0 || !(hd > 0)) return MGP_EINVAL;                                                              \
+    if (loss_id != MGP_CLASS_LOSS_CROSS_ENTROPY && loss_id != MGP_CLASS_LOSS_MSE) return MGP_EINVAL;                 \
+    if (!partials || !scratch || (b > 0 && (!pred || !target))) return MGP_EINVAL;                                   \
+    if (ts % (int64_t)sizeof(T) != 0 || (!bi && ts < (int64_t)(R * sizeof(T)))) return MGP_EINVAL;                   \
+    return launch_class_sums<T>(pred, target, ts, bi, b, R, loss_id, grad_scale, hd, grad_pred, partials, scratch,   \
+                                S_(st));                                                                             \
+  }                                                                                                                  \
+  int mgp_class_partition_##SUF(const T* labels, int64_t n, int R, const int64_t* ni, int64_t b, int k, T* pred,     \
+                                unsigned char* nonconstant, int64_t* count, int64_t* sel, int64_t* nn_sel,           \
+                                void* scratch, void* st) {                                                           \
+    if (n < 1 || R < 1 || b < 0 || k < 1) return MGP_EINVAL;                                                         \
+    if (!labels || !count || !scratch) return MGP_EINVAL;                                                            \
+    if (b > 0 && (!ni || !pred || !nonconstant || !sel || !nn_sel)) return MGP_EINVAL;                               \
+    return launch_class_partition<T>(labels, n, R, ni, b, k, pred, nonconstant, count, sel, nn_sel, scratch, S_(st)); \
+  }                                                                                                                  \
+  int mgp_class_scatter_##SUF(const T* src_mean, const T* src_var, const int64_t* sel, int64_t m, int64_t b, int R,  \
+                              T* dst_mean, T* dst_var, void* st) {                                                   \
+    if (m < 0 || b < 0 || m > b || R < 1) return MGP_EINVAL;                                                         \
+    if (m > 0 && (!src_mean || !sel || !dst_mean || ((src_var != nullptr) != (dst_var != nullptr))))                 \
+      return MGP_EINVAL;                                                                                             \
+    return launch_class_scatter<T>(src_mean, src_var, sel, m, b, R, dst_mean, dst_var, S_(st));                      \
+  }
+MGP_DEFINE_CLASS(f32, float)
+MGP_DEFINE_CLASS(f64, double)
+
 MGP_DEFINE(f32, float)
 MGP_DEFINE(f64, double)
 

@@ -738,6 +738,70 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     return value, np.asarray(g[:-1], dtype=np.float64), float(g[-1])
 
 
+def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_labels: torch.Tensor,
+                         batch_indices: torch.Tensor, nn_indices: torch.Tensor, loss: str = "cross_entropy",
+                         packed: Union[str, bool] = "auto", reduce_fn=None):
+    """A classification LOOCV loss on ``R >= 2`` one-hot response columns and its ANALYTIC gradient with respect to
+    the length scale(s) and a homoscedastic noise: the fused posterior (``posterior_mean_var``), one
+    ``mgp_class_sums_*`` launch that returns the loss sums and the cotangent of the (b, R) mean, and one
+    ``mgp_posterior_backward_*`` launch fed with that cotangent (``grad_var`` = NULL: neither loss reads the variance,
+    so no sigma^2 enters and the trial / stored noise split of :func:`loocv_value_and_grad` does not arise).
+
+        cross_entropy  -sum one_hot log clip(softmax(mean))      (reference: _src/optimize/loss/numpy.py:12-19)
+        mse            sum r^2 / (b R),  d/dm = 2 r / (b R)       (:22-31, ``np.prod(predictions.shape)``)
+
+    ``reduce_fn`` (sharded batches): sums a float64 device vector over the ranks in place -- applied to the sums (so
+    the mse count is the global one) and to the gradient.
+
+    Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS."""
+    import numpy as np
+
+    if loss not in ("cross_entropy", "mse"):
+        raise NotImplementedError(f"classification gradients are written out for cross_entropy and mse, not {loss!r}")
+    if isinstance(spec.noise, torch.Tensor) and spec.noise.ndim >= 1:
+        raise NotImplementedError("analytic gradients: homoscedastic noise")
+    if spec.kernel == "matern_gen":
+        raise NotImplementedError("analytic gradients: closed-form kernels (fixed smoothness)")
+    dtype = train_features.dtype
+    fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
+    tg = train_labels.contiguous()
+    if tg.ndim != 2 or tg.shape[1] < 2:
+        raise NotImplementedError("the classification losses are defined for two or more response columns")
+    d, R = fn.shape[1], tg.shape[1]
+    ni = nn_indices.to(torch.int64).contiguous()
+    bi = batch_indices.to(torch.int64).contiguous()
+    b, k = ni.shape
+    info = torch.zeros(1, device=fn.device, dtype=torch.int32)
+    mean, _ = posterior_mean_var(spec, fn, fn, bi, ni, tg, info=info, packed=packed)
+    _lib.raise_if_not_spd(info, "classification objective")
+    stride = R * tg.element_size()
+    if loss == "mse" and reduce_fn is not None:  # the global element count first: the cotangent is scaled by it
+        sums, _ = _lib.class_sums(mean, tg, stride, bi, "mse")
+        reduce_fn(sums)
+        _, gm = _lib.class_sums(mean, tg, stride, bi, "mse", 1.0 / float(sums[2]), True)
+    else:
+        sums, gm = _lib.class_sums(mean, tg, stride, bi, loss, 1.0 / (b * R) if loss == "mse" else 1.0, True)
+        if reduce_fn is not None:
+            reduce_fn(sums)
+    ce, r2sum, count = (float(v) for v in sums[:3].tolist())
+    value = ce if loss == "cross_entropy" else r2sum / count
+    ls = _length_scale_tensor(spec.length_scale, d, fn)
+    g_l = torch.zeros((b, ls.numel()), device=fn.device, dtype=dtype)
+    g_n = torch.zeros((b, k), device=fn.device, dtype=dtype)
+    rc = _lib.fn("posterior_backward", dtype)(
+        _lib.ptr(fn), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), R,
+        _lib.NOISE_SCALAR, float(spec.noise), None, spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(),
+        _lib.ptr(gm), None, None, None, None, _lib.ptr(g_l), _lib.ptr(g_n), _lib.ptr(info), _lib.stream_ptr(),
+    )
+    _lib.check(rc, "mgp_posterior_backward")
+    _lib.raise_if_not_spd(info, "classification gradient")
+    grad = torch.cat([_lib.column_sums(g_l), _lib.column_sums(g_n.reshape(-1, 1))])  # fp64, deterministic
+    if reduce_fn is not None:
+        reduce_fn(grad)
+    g = grad.cpu().numpy()
+    return value, np.asarray(g[:-1], dtype=np.float64), float(g[-1])
+
+
 def loocv_tree_sums(mean: torch.Tensor, var: torch.Tensor, ykinvy: torch.Tensor, train_targets: torch.Tensor,
                     batch_indices: Optional[torch.Tensor], huber_delta: float = 1.5, leaves=(0, 0)) -> torch.Tensor:
     """The LOOCV partial sums from finished outputs (``mgp_loocv_tree_*``): the reduction tree ``mgp_loocv_*`` walks
