@@ -15,7 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .fused import KernelSpec, _length_scale_tensor
+from .fused import KernelSpec, _noise_args, _normalize
 
 
 def _column_sums(x2: torch.Tensor) -> torch.Tensor:
@@ -31,12 +31,7 @@ class _FusedPosterior(torch.autograd.Function):
         ls = length_scale.contiguous()
         b, k = nn_indices.shape
         d, R = fn.shape[1], tg.shape[1]
-        if noise.ndim == 0:
-            mode, eps, nz = _lib.NOISE_SCALAR, float(noise), None
-        elif noise.ndim == 1:
-            mode, eps, nz = _lib.NOISE_TABLE, 0.0, noise.contiguous()
-        else:
-            mode, eps, nz = _lib.NOISE_BATCH, 0.0, noise.contiguous()
+        mode, eps, nz = _noise_args(noise, b, k, fn)  # (also checks a noise table / batch against the shapes)
         mean = torch.empty((b, R), device=fn.device, dtype=fn.dtype)
         var = torch.empty((b,), device=fn.device, dtype=fn.dtype)
         info = torch.zeros(1, device=fn.device, dtype=torch.int32)
@@ -117,41 +112,15 @@ def posterior(
     ``spec.noise`` when those are tensors that require grad.  Passing the *same tensor* as
     ``test_features`` and ``train_features`` (``MuyGPs_layer.forward``: crosswise_tensor(x, x, ...),
     torch/muygps_layer.py:146-155) accumulates both roles into one gradient buffer."""
-    _lib.require_cuda(test_features, train_features, batch_indices, nn_indices, train_targets)
-    dtype = train_features.dtype
-    if test_features.dtype != dtype or train_targets.dtype != dtype:
-        raise TypeError("features and targets must share one float dtype")
-    shared = test_features is train_features
-    fq = test_features[:, None] if test_features.ndim == 1 else test_features
-    fn = fq if shared else (train_features[:, None] if train_features.ndim == 1 else train_features)
-    d = fn.shape[1]
-    if fq.shape[1] != d:
-        raise ValueError("test and train features differ in feature count")
-    ni = nn_indices.to(torch.int64).contiguous()
-    b, k = ni.shape
-    kmax = _lib.load().mgp_max_nn_count_backward(4 if dtype == torch.float32 else 8)
+    # (the length scale stays attached to the graph; the noise tensor is decoded inside the autograd function)
+    inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, want_noise=False,
+                     detach=False)
+    fq, fn, ni, tg, b, k, ls = inp.fq, inp.fn, inp.ni, inp.tg, inp.b, inp.k, inp.ls
+    kmax = _lib.load().mgp_max_nn_count_backward(4 if fn.dtype == torch.float32 else 8)
     if k > kmax:
-        raise ValueError(f"nn_count {k} exceeds the differentiable kernel's limit {kmax} for {dtype}")
-    if batch_indices is None:
-        bi = torch.arange(b, device=ni.device, dtype=torch.int64)
-    else:
-        bi = batch_indices.to(torch.int64).contiguous()
-    squeeze = train_targets.ndim == 1
-    tg = train_targets[:, None] if squeeze else train_targets
-    if isinstance(spec.length_scale, torch.Tensor):
-        ls = spec.length_scale.to(device=fn.device, dtype=dtype).reshape(-1)
-        if ls.numel() not in (1, d):
-            raise ValueError(
-                f"Difference tensor of shape (..., {d}) must have final dimension size of {ls.numel()}"
-            )
-    else:
-        ls = _length_scale_tensor(spec.length_scale, d, fn)
+        raise ValueError(f"nn_count {k} exceeds the differentiable kernel's limit {kmax} for {fn.dtype}")
+    bi = inp.bi if inp.bi is not None else torch.arange(b, device=ni.device, dtype=torch.int64)
     noise = _as_param(spec.noise, fn)
-    if noise.ndim == 2 and noise.shape != (b, k):
-        raise ValueError(f"heteroscedastic noise tensor must have shape {(b, k)}, got {tuple(noise.shape)}")
-    if noise.ndim == 1 and noise.shape[0] != fn.shape[0]:
-        raise ValueError(
-            f"per-training-point noise table holds {noise.shape[0]} entries for {fn.shape[0]} training points"
-        )
-    mean, var = _FusedPosterior.apply(fq, fn, tg, ls, noise, bi, ni, spec.kernel_id(), spec.metric_id(), shared)
-    return (mean.reshape(b) if squeeze else mean), var
+    mean, var = _FusedPosterior.apply(fq, fn, tg, ls, noise, bi, ni, spec.kernel_id(), spec.metric_id(),
+                                      test_features is train_features)
+    return (mean.reshape(b) if inp.squeeze else mean), var

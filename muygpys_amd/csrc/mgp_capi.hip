@@ -47,36 +47,67 @@ extern int g_bwd_stage;  // mgp_backward.hip
 // caller (mgp_posterior_generic_* / mgp_posterior_rhs_*: tests and A/B timing)
 enum { PATH_AUTO = 0, PATH_GENERIC = 1, PATH_RHS = 2 };
 
+// ---- the one path from the C arguments of a fused entry to FusedArgs -------------------------------------------------
+// What an entry asks of the arguments the fused entries share.  Prepared tables need no flag (an entry that does not
+// take them passes none), and neither does the response count: every entry needs R >= 1 (mgp_fast_coefficients_*
+// passes its own 1).  A new model parameter is validated and assigned in fused_args, once.
+enum {
+  NEED_RESPONSES = 1,  // `tg` is read: the (n, R) table, or the gathered (b, k, R) tensor next to prepared tables
+  NEED_OUTPUTS = 2,    // `mean` and `var` are written
+  KERNEL_IS_GEN = 4    // the entry serves MGP_KERNEL_MATERN_GEN alone: `kernel_id` is not looked at
+};
+enum { ARGS_READY = 1 };  // fused_args: valid arguments and a batch to serve; any other value is the entry's status
+
+// Validates in the order every fused entry has always used -- sizes (MGP_EINVAL), the empty batch (MGP_OK: pointers and
+// enum ids are not looked at, outputs may be NULL), then pointers, strides and ids (MGP_EINVAL) -- and fills `a`.
+// Checks of one entry alone stay with that entry: in front of the call where they come before the empty-batch return
+// (mgp_loocv_*, the smoothness sign of mgp_posterior_gen_*), behind it otherwise.
+template <typename T>
+int fused_args(FusedArgs& a, int needs, const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b,
+               int k, const T* tg, int R, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id,
+               const T* ls, int ls_count, T* mean, T* var, T* yk, int* info, const void* packed_q = nullptr,
+               int64_t q_stride = 0, const void* packed_nn = nullptr, int64_t nn_stride = 0, int targets_batch = 0) {
+  if (b < 0 || k < 1 || d < 1 || R < 1) return MGP_EINVAL;
+  if (b == 0) return MGP_OK;  // empty shard: nothing to read or write
+  if (packed_nn) {
+    // both strides cover the features and the 16-byte response slot the gather reads with every row
+    const int64_t need = (int64_t)(d * sizeof(T)) + 16;
+    if (!packed_q || q_stride < need || nn_stride < need) return MGP_EINVAL;
+    // the neighbour table carries the responses, unless they come already gathered (b, k, R)
+    if (targets_batch ? tg == nullptr : nn_stride < (int64_t)((d + R) * sizeof(T))) return MGP_EINVAL;
+  } else if (!fq || !fn || ((needs & NEED_RESPONSES) && !tg)) {
+    return MGP_EINVAL;
+  }
+  if (!ni || !ls) return MGP_EINVAL;
+  if ((needs & NEED_OUTPUTS) && (!mean || !var)) return MGP_EINVAL;
+  if (needs & KERNEL_IS_GEN) kernel_id = MGP_KERNEL_MATERN_GEN;
+  else if (!valid_kernel(kernel_id)) return MGP_EINVAL;
+  if (!valid_metric(metric_id)) return MGP_EINVAL;
+  if (noise_mode < MGP_NOISE_SCALAR || noise_mode > MGP_NOISE_BATCH) return MGP_EINVAL;
+  if (noise_mode != MGP_NOISE_SCALAR && !nd) return MGP_EINVAL;
+  if (ls_count != 1 && ls_count != d) return MGP_EINVAL;
+  a = FusedArgs();
+  a.feat_q = fq, a.feat_nn = fn, a.batch_idx = bi, a.nn_idx = ni, a.targets = tg, a.targets_batch = targets_batch;
+  a.packed_q = packed_q, a.q_stride = q_stride, a.packed_nn = packed_nn, a.nn_stride = nn_stride;
+  a.b = b, a.d = d, a.k = k, a.R = R;
+  a.noise_mode = noise_mode, a.noise_scalar = eps, a.noise_dev = nd;
+  a.kernel_id = kernel_id, a.metric_id = metric_id, a.length_scale = ls, a.ls_count = ls_count;
+  a.mean = mean, a.var = var, a.ykinvy = yk, a.info = info;
+  return ARGS_READY;
+}
+
 template <typename T>
 int posterior(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
               int R, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id, const T* ls,
               int ls_count, T* mean, T* var, T* yk, int* info, void* stream, int path = PATH_AUTO,
               const void* packed_q = nullptr, int64_t q_stride = 0, const void* packed_nn = nullptr,
               int64_t nn_stride = 0, int targets_batch = 0, const LoocvTree* tree = nullptr, bool* tree_served = nullptr) {
-  if (b < 0 || k < 1 || d < 1 || R < 1) return MGP_EINVAL;
-  if (b == 0) return MGP_OK;  // empty shard: nothing to read or write (outputs may be NULL)
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS, fq, fn, d, bi, ni, b, k, tg, R, noise_mode, eps, nd,
+                                  kernel_id, metric_id, ls, ls_count, mean, var, yk, info, packed_q, q_stride, packed_nn,
+                                  nn_stride, targets_batch);
+  if (ready != ARGS_READY) return ready;
   const bool packed = packed_nn != nullptr;
-  if (packed) {
-    // both strides cover the features and the 16-byte response slot the gather reads with every row
-    const int64_t need = (int64_t)(d * sizeof(T)) + 16;
-    if (!packed_q || q_stride < need || nn_stride < need) return MGP_EINVAL;
-    // the neighbour table carries the responses, unless they come already gathered (b, k, R)
-    if (targets_batch ? tg == nullptr : nn_stride < (int64_t)((d + R) * sizeof(T))) return MGP_EINVAL;
-  } else if (!fq || !fn || !tg) {
-    return MGP_EINVAL;
-  }
-  if (!ni || !ls || !mean || !var) return MGP_EINVAL;
-  if (!valid_kernel(kernel_id) || !valid_metric(metric_id)) return MGP_EINVAL;
-  if (noise_mode < MGP_NOISE_SCALAR || noise_mode > MGP_NOISE_BATCH) return MGP_EINVAL;
-  if (noise_mode != MGP_NOISE_SCALAR && !nd) return MGP_EINVAL;
-  if (ls_count != 1 && ls_count != d) return MGP_EINVAL;
-  FusedArgs a{fq, fn, bi, ni, tg, nd, ls, mean, var, yk, info, b, eps, d, k, R, noise_mode, kernel_id, metric_id,
-              ls_count, 0};
-  a.targets_batch = targets_batch;
-  a.packed_q = packed_q;
-  a.packed_nn = packed_nn;
-  a.q_stride = q_stride;
-  a.nn_stride = nn_stride;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // a LOOCV evaluation (mgp_loocv_*): the wave kernels walk the reduction tree themselves (one launch); behind the
   // other families the caller does
@@ -117,18 +148,28 @@ template <typename T>
 int fast_coefficients(const T* fn, int d, const int64_t* ni, int64_t b, int k, const T* tg, int noise_mode, double eps,
                       const T* nd, int kernel_id, int metric_id, const T* ls, int ls_count, T* coeffs, int* info,
                       void* stream) {
-  if (b < 0 || k < 1 || d < 1) return MGP_EINVAL;
-  if (b == 0) return MGP_OK;
-  if (!fn || !ni || !tg || !ls || !coeffs) return MGP_EINVAL;
-  if (!valid_kernel(kernel_id) || !valid_metric(metric_id)) return MGP_EINVAL;
-  if (noise_mode < MGP_NOISE_SCALAR || noise_mode > MGP_NOISE_BATCH) return MGP_EINVAL;
-  if (noise_mode != MGP_NOISE_SCALAR && !nd) return MGP_EINVAL;
-  if (ls_count != 1 && ls_count != d) return MGP_EINVAL;
+  FusedArgs a;
   // the query slot is fed the first neighbour of each row: its outputs are not stored
-  FusedArgs a{fn, fn, nullptr, ni, tg, nd, ls, nullptr, nullptr, nullptr, info, b, eps, d, k, 1, noise_mode, kernel_id,
-              metric_id, ls_count, 0};
+  const int ready = fused_args<T>(a, NEED_RESPONSES, fn, fn, d, nullptr, ni, b, k, tg, 1, noise_mode, eps, nd, kernel_id,
+                                  metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (!coeffs) return MGP_EINVAL;
   a.coeffs = coeffs;
   return launch_fused_wave<T>(a, static_cast<hipStream_t>(stream));
+}
+
+// prediction from precomputed coefficients: no responses, no noise (both are inside `coeffs`)
+template <typename T>
+int fast_posterior_mean(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                        const T* coeffs, const int64_t* crow, int R, int kernel_id, int metric_id, const T* ls,
+                        int ls_count, T* mean, void* stream) {
+  FusedArgs a;
+  const int ready = fused_args<T>(a, 0, fq, fn, d, bi, ni, b, k, nullptr, R, MGP_NOISE_SCALAR, 0.0, nullptr, kernel_id,
+                                  metric_id, ls, ls_count, mean, nullptr, nullptr, nullptr);
+  if (ready != ARGS_READY) return ready;
+  if (!coeffs || !crow || !mean) return MGP_EINVAL;
+  return launch_fast_mean<T>(fq, fn, d, bi, ni, b, k, coeffs, crow, R, kernel_id, metric_id, ls, ls_count, mean,
+                             static_cast<hipStream_t>(stream));
 }
 
 template <typename T>
@@ -136,19 +177,14 @@ int posterior_backward(const T* fq, const T* fn, int d, const int64_t* bi, const
                        const T* tg, int R, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id,
                        const T* ls, int ls_count, const T* gmean, const T* gvar, T* gfq, T* gfn, T* gtg, T* gls,
                        T* gnz, int* info, void* stream, const T* gyk = nullptr) {
-  if (b < 0 || k < 1 || d < 1 || R < 1) return MGP_EINVAL;
-  if (b == 0) return MGP_OK;
-  if (!fq || !fn || !ni || !tg || !ls) return MGP_EINVAL;
+  BackwardArgs g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES, fq, fn, d, bi, ni, b, k, tg, R, noise_mode, eps, nd, kernel_id,
+                                  metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
   if (!gmean && !gvar && !gyk) return MGP_EINVAL;
   if (gyk && R != 1) return MGP_EINVAL;  // (the LOOCV losses are defined for one response)
-  if (!valid_kernel(kernel_id) || !valid_metric(metric_id)) return MGP_EINVAL;
-  if (noise_mode < MGP_NOISE_SCALAR || noise_mode > MGP_NOISE_BATCH) return MGP_EINVAL;
-  if (noise_mode != MGP_NOISE_SCALAR && !nd) return MGP_EINVAL;
-  if (ls_count != 1 && ls_count != d) return MGP_EINVAL;
-  BackwardArgs g{{fq, fn, bi, ni, tg, nd, ls, nullptr, nullptr, nullptr, info, b, eps, d, k, R, noise_mode, kernel_id,
-                  metric_id, ls_count, 0},
-                 gmean, gvar, gfq, gfn, gtg, gls, gnz};
-  g.grad_yk = gyk;
+  g.grad_mean = gmean, g.grad_var = gvar, g.grad_yk = gyk;
+  g.grad_feat_q = gfq, g.grad_feat_nn = gfn, g.grad_targets = gtg, g.grad_ls = gls, g.grad_noise = gnz;
   static const bool lds_only = getenv("MGP_BACKWARD_LDS") != nullptr;  // A/B switch (timing only)
   // hyper-parameter gradients on the forward kernel itself (round 6: the dealt-triangle shapes of BASELINE config 4 and
   // the 32-slot shapes of config 3)
@@ -200,28 +236,13 @@ static int posterior_gen(const T* fq, const T* fn, const void* packed_q, int64_t
                          int64_t nn_stride, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
                          int R, int targets_batch, int noise_mode, double eps, const T* nd, double smoothness,
                          int metric_id, const T* ls, int ls_count, T* mean, T* var, T* yk, int* info, void* stream) {
-  if (b < 0 || k < 1 || d < 1 || R < 1 || !(smoothness > 0.0)) return MGP_EINVAL;
-  if (b == 0) return MGP_OK;
-  const bool packed = packed_nn != nullptr;
-  if (packed) {
-    const int64_t need = (int64_t)(d * sizeof(T)) + 16;
-    if (!packed_q || q_stride < need || nn_stride < need) return MGP_EINVAL;
-    if (targets_batch ? tg == nullptr : nn_stride < (int64_t)((d + R) * sizeof(T))) return MGP_EINVAL;
-  } else if (!fq || !fn || !tg) {
-    return MGP_EINVAL;
-  }
-  if (!ni || !ls || !mean || !var || !valid_metric(metric_id)) return MGP_EINVAL;
-  if (noise_mode < MGP_NOISE_SCALAR || noise_mode > MGP_NOISE_BATCH) return MGP_EINVAL;
-  if (noise_mode != MGP_NOISE_SCALAR && !nd) return MGP_EINVAL;
-  if (ls_count != 1 && ls_count != d) return MGP_EINVAL;
+  if (!(smoothness > 0.0)) return MGP_EINVAL;  // (in front of the empty-batch return, like the sizes)
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_IS_GEN, fq, fn, d, bi, ni, b, k, tg, R,
+                                  noise_mode, eps, nd, MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, mean, var, yk,
+                                  info, packed_q, q_stride, packed_nn, nn_stride, targets_batch);
+  if (ready != ARGS_READY) return ready;
   if (smoothness > 30.0) return MGP_EUNSUPPORTED;  // beyond nu = 30 the RBF limit is the better model anyway
-  FusedArgs a{fq, fn, bi, ni, tg, nd, ls, mean, var, yk, info, b, eps, d, k, R, noise_mode, MGP_KERNEL_MATERN_GEN, metric_id,
-              ls_count, 0};
-  a.targets_batch = targets_batch;
-  a.packed_q = packed_q;
-  a.packed_nn = packed_nn;
-  a.q_stride = q_stride;
-  a.nn_stride = nn_stride;
   a.smoothness = smoothness;
   return launch_fused_wave<T>(a, static_cast<hipStream_t>(stream));
 }
@@ -574,11 +595,7 @@ int mgp_max_nn_count_backward(int elem_size) { return max_nn_count_backward(elem
   int mgp_fast_posterior_mean_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, \
                                     int k, const T* coeffs, const int64_t* crow, int R, int kid, int mid,            \
                                     const T* ls, int lsc, T* mean, void* st) {                                       \
-    if (b < 0 || k < 1 || d < 1 || R < 1) return MGP_EINVAL;                                                         \
-    if (b == 0) return MGP_OK;                                                                                       \
-    if (!fq || !fn || !ni || !coeffs || !crow || !ls || !mean) return MGP_EINVAL;                                    \
-    if (!valid_kernel(kid) || !valid_metric(mid) || (lsc != 1 && lsc != d)) return MGP_EINVAL;                       \
-    return launch_fast_mean<T>(fq, fn, d, bi, ni, b, k, coeffs, crow, R, kid, mid, ls, lsc, mean, S_(st));           \
+    return fast_posterior_mean<T>(fq, fn, d, bi, ni, b, k, coeffs, crow, R, kid, mid, ls, lsc, mean, st);            \
   }
 MGP_DEFINE_FAST(f32, float)
 MGP_DEFINE_FAST(f64, double)

@@ -12,7 +12,7 @@ from __future__ import annotations
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
-from typing import Optional, Sequence, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -68,9 +68,9 @@ _LS_CACHE: "OrderedDict[tuple, torch.Tensor]" = OrderedDict()
 _LS_CACHE_SIZE = 64
 
 
-def _length_scale_tensor(ls, d: int, like: torch.Tensor) -> torch.Tensor:
+def _length_scale_tensor(ls, d: int, like: torch.Tensor, detach: bool = True) -> torch.Tensor:
     if isinstance(ls, torch.Tensor):
-        t = ls.detach().to(device=like.device, dtype=like.dtype).reshape(-1).contiguous()
+        t = (ls.detach() if detach else ls).to(device=like.device, dtype=like.dtype).reshape(-1).contiguous()
     else:
         vals = (float(ls),) if isinstance(ls, (int, float)) else tuple(float(v) for v in ls)
         key = (vals, like.device, like.dtype)
@@ -215,6 +215,119 @@ def _noise_args(noise, b: int, k: int, like: torch.Tensor):
     return _lib.NOISE_SCALAR, float(noise), None
 
 
+class _Inputs(NamedTuple):
+    """The arguments of a fused call as the library takes them (:func:`_normalize`)."""
+
+    fq: torch.Tensor            # (n_q, d) query features, contiguous (`fn` itself when both sides are one tensor)
+    fn: torch.Tensor            # (n, d) neighbour features, contiguous
+    bi: Optional[torch.Tensor]  # (b,) int64, or None: neighbourhood i belongs to query row i
+    ni: torch.Tensor            # (b, k) int64
+    tg: Optional[torch.Tensor]  # (n, R) responses, (b, k, R) when gathered, None when the call reads none
+    b: int
+    k: int
+    d: int
+    R: int
+    squeeze: bool               # the caller's responses had no response axis: results drop theirs
+    ls: torch.Tensor            # (1,) or (d,) length scale(s) on the device
+    mode: Optional[int]         # the noise triple of _noise_args (None where the call takes no noise)
+    eps: Optional[float]
+    nz: Optional[torch.Tensor]
+
+
+def _normalize(spec: KernelSpec, test_features, train_features, batch_indices, nn_indices, targets=None, *,
+               gathered: bool = False, responses: str = "any", want_noise: bool = True, detach: bool = True) -> _Inputs:
+    """The one place where the public arguments of a fused function become what the library reads: 2-D contiguous
+    tables, int64 indices, the shape and dtype checks, the length scale(s) and the noise triple.  A new model parameter
+    is validated and converted here, once.
+
+    ``responses``: "any", "single" (the LOOCV losses) or "labels" (two or more columns: classification).
+    ``want_noise=False`` / ``detach=False``: the differentiable path decodes its noise tensor inside the autograd
+    function and keeps a length-scale tensor attached to the graph."""
+    _lib.require_cuda(test_features, train_features, batch_indices, nn_indices, targets)
+    dtype = train_features.dtype
+    if test_features.dtype != dtype or (targets is not None and targets.dtype != dtype):
+        raise TypeError("features and targets must share one float dtype")
+    fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
+    fq = fn if test_features is train_features else (test_features[:, None] if test_features.ndim == 1 else test_features).contiguous()
+    d = fn.shape[1]
+    if fq.shape[1] != d:
+        raise ValueError("test and train features differ in feature count")
+    ni = nn_indices.to(torch.int64).contiguous()
+    b, k = ni.shape
+    bi = None if batch_indices is None else batch_indices.to(torch.int64).contiguous()
+    if bi is not None and bi.shape != (b,):
+        raise ValueError("batch_indices must have shape (batch_count,)")
+    if bi is None and fq.shape[0] < b:
+        raise ValueError(f"{b} neighbourhoods but only {fq.shape[0]} query rows (batch_indices is None)")
+    tg, R, squeeze = None, 1, False
+    if gathered:
+        if tuple(targets.shape[:2]) != (b, k):
+            raise ValueError(f"gathered responses must have shape ({b}, {k}[, R]), got {tuple(targets.shape)}")
+        squeeze = targets.ndim == 2
+        tg = targets.reshape(b, k, -1).contiguous()
+        R = tg.shape[2]
+    elif targets is not None:
+        squeeze = targets.ndim == 1
+        tg = (targets[:, None] if squeeze else targets).contiguous()
+        R = tg.shape[1]
+        if responses == "single" and (tg.ndim != 2 or R != 1):
+            raise NotImplementedError("the LOOCV losses are defined for a single response (reference: loss/numpy.py:34-61)")
+        if responses == "labels" and (tg.ndim != 2 or R < 2):
+            raise NotImplementedError("the classification losses are defined for two or more response columns")
+        if tg.shape[0] != fn.shape[0]:
+            raise ValueError("train_features and train_targets differ in row count")
+    ls = _length_scale_tensor(spec.length_scale, d, fn, detach)
+    mode, eps, nz = _noise_args(spec.noise, b, k, fn) if want_noise else (None, None, None)
+    return _Inputs(fq, fn, bi, ni, tg, b, k, d, R, squeeze, ls, mode, eps, nz)
+
+
+def _debug_check_indices(inp: _Inputs) -> None:
+    if os.environ.get("MUYGPYS_HIP_CHECK_INDICES") == "1":
+        _check_indices("nn_indices", inp.ni, inp.fn.shape[0])
+        _check_indices("batch_indices", inp.bi, inp.fq.shape[0])
+
+
+def _use_packed(packed, inp: _Inputs, features, targets, rows: int, gathered: bool = False, threshold: bool = True) -> bool:
+    """Whether a call reads its tables through prepared copies (:class:`PackedTable`): never with ``packed=False``,
+    an empty batch or a shape the prepared-table kernels do not serve; ``packed="auto"`` additionally asks that the
+    pack pays off -- the table is cached already, or the batch gathers at least a quarter of the ``rows`` a pack
+    passes over.  ``threshold=False``: a prepared evaluation (:class:`LoocvPlan`) repeats, so "auto" always packs.
+    Gathered responses: the FEATURE rows still come from a prepared table (packed without responses)."""
+    R, k = (0, inp.k + inp.R) if gathered else (inp.R, inp.k)
+    if packed is False or inp.b <= 0 or not PackedTable.supported(inp.d, R, k, inp.fn.dtype):
+        return False
+    if packed == "auto" and threshold:
+        key = (_tensor_key(features), None if gathered else _tensor_key(targets))
+        return key in _PACK_CACHE or inp.b * (inp.k + 1) >= rows // 4
+    return True
+
+
+def _posterior_call(spec: KernelSpec, inp: _Inputs, gathered: bool, path: str, pq, pn, outs: tuple):
+    """(entry point, arguments) of one posterior launch: ``mgp_posterior_gen_*`` for the general-smoothness Matern,
+    else by table form -- prepared (``pn`` / ``pq``: the packed neighbour / query tables) or plain, responses in the
+    table or gathered.  ``outs``: the pointers of mean, var, ykinvy, info and the stream, in the ABI's order."""
+    P = _lib.ptr
+    ls = inp.ls if pn is None else pn.kernel_length_scale(inp.ls)
+    plain = (None, None) if pn is not None else (P(inp.fq), P(inp.fn))
+    tables = (None, 0, None, 0) if pn is None else (P(pq.data), pq.stride, P(pn.data), pn.stride)
+    shape = (inp.d if pn is None else pn.d_kernel, P(inp.bi), P(inp.ni), inp.b, inp.k)
+    noise = (inp.mode, inp.eps, P(inp.nz))
+    tail = (spec.metric_id(), P(ls), ls.numel()) + outs
+    if spec.kernel == "matern_gen":
+        # (`tg` goes along even when the prepared table carries the responses: the library does not read it then)
+        args = plain + tables + shape + (P(inp.tg), inp.R, int(gathered)) + noise + (float(spec.smoothness),) + tail
+        return _lib.fn("posterior_gen", inp.fn.dtype), args
+    tail = (spec.kernel_id(),) + tail
+    if pn is None:
+        base = "posterior_gathered" if gathered else {"auto": "posterior", "generic": "posterior_generic", "rhs": "posterior_rhs"}[path]
+        args = plain + shape + (P(inp.tg), inp.R) + noise + tail
+    elif gathered:
+        base, args = "posterior_packed_gathered", tables + shape + (P(inp.tg), inp.R) + noise + tail
+    else:
+        base, args = "posterior_packed", tables + shape + (inp.R,) + noise + tail
+    return _lib.fn(base, inp.fn.dtype), args
+
+
 def posterior_mean_var(
     spec: KernelSpec,
     test_features: torch.Tensor,
@@ -245,125 +358,58 @@ def posterior_mean_var(
     ``gathered``: ``train_targets`` is the already gathered ``(b, k[, R])`` tensor ``targets[nn_indices]``
     (what the reference's ``make_*_tensors`` return) instead of the ``(n[, R])`` table.
     """
-    _lib.require_cuda(test_features, train_features, batch_indices, nn_indices, train_targets)
-    dtype = train_features.dtype
-    if test_features.dtype != dtype or train_targets.dtype != dtype:
-        raise TypeError("features and targets must share one float dtype")
-    fq = test_features.contiguous()
-    fn = train_features.contiguous()
-    if fq.ndim == 1:
-        fq = fq[:, None]
-    if fn.ndim == 1:
-        fn = fn[:, None]
-    d = fn.shape[1]
-    if fq.shape[1] != d:
-        raise ValueError("test and train features differ in feature count")
-    ni = nn_indices.to(torch.int64).contiguous()
-    b, k = ni.shape
-    bi = None if batch_indices is None else batch_indices.to(torch.int64).contiguous()
-    if bi is not None and bi.shape != (b,):
-        raise ValueError("batch_indices must have shape (batch_count,)")
-    if bi is None and fq.shape[0] < b:
-        raise ValueError(f"{b} neighbourhoods but only {fq.shape[0]} query rows (batch_indices is None)")
-    if gathered:
-        if tuple(train_targets.shape[:2]) != (b, k):
-            raise ValueError(f"gathered responses must have shape ({b}, {k}[, R]), got {tuple(train_targets.shape)}")
-        squeeze = train_targets.ndim == 2
-        tg = train_targets.reshape(b, k, -1).contiguous()
-        R = tg.shape[2]
-    else:
-        squeeze = train_targets.ndim == 1
-        tg = (train_targets[:, None] if squeeze else train_targets).contiguous()
-        if tg.shape[0] != fn.shape[0]:
-            raise ValueError("train_features and train_targets differ in row count")
-        R = tg.shape[1]
-    if os.environ.get("MUYGPYS_HIP_CHECK_INDICES") == "1":
-        _check_indices("nn_indices", ni, fn.shape[0])
-        _check_indices("batch_indices", bi, fq.shape[0])
-    ls = _length_scale_tensor(spec.length_scale, d, fn)
-    mode, eps, nz = _noise_args(spec.noise, b, k, fn)
-
+    inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, gathered=gathered)
+    _debug_check_indices(inp)
+    fn, b, R, dtype = inp.fn, inp.b, inp.R, inp.fn.dtype
     mean = out_mean if out_mean is not None else torch.empty((b, R), device=fn.device, dtype=dtype)
     var = out_var if out_var is not None else torch.empty((b,), device=fn.device, dtype=dtype)
     yk = torch.empty((b, R), device=fn.device, dtype=dtype) if want_ykinvy else None
     if path not in ("auto", "generic", "rhs"):
         raise ValueError(f"unknown kernel path {path!r}")
-    if spec.kernel == "matern_gen":
-        if path != "auto":
-            raise ValueError("the general-smoothness Matern goes through the dispatcher (path='auto')")
-        if spec.smoothness is None or not float(spec.smoothness) > 0.0:
-            raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
-        # one entry point for every table form (mgp_posterior_gen_*): prepared tables when they pay off
-        use_packed = (packed is not False and b > 0
-                      and PackedTable.supported(d, 0 if gathered else R, k + (R if gathered else 0), dtype))
-        if use_packed and packed == "auto":
-            key = (_tensor_key(train_features), None if gathered else _tensor_key(train_targets))
-            rows = fn.shape[0] + (0 if test_features is train_features else fq.shape[0])
-            use_packed = key in _PACK_CACHE or b * (k + 1) >= rows // 4
-        pn = pq = None
-        if use_packed:
-            pn = pack_table(train_features, None if gathered else train_targets, query=False)
-            pq = pn if test_features is train_features else pack_table(test_features, None)
-        lsk = pn.kernel_length_scale(ls) if use_packed else ls
-        rc = _lib.fn("posterior_gen", dtype)(
-            None if use_packed else _lib.ptr(fq), None if use_packed else _lib.ptr(fn),
-            _lib.ptr(pq.data) if use_packed else None, pq.stride if use_packed else 0,
-            _lib.ptr(pn.data) if use_packed else None, pn.stride if use_packed else 0,
-            pn.d_kernel if use_packed else d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), R, 1 if gathered else 0, mode, eps,
-            _lib.ptr(nz), float(spec.smoothness), spec.metric_id(), _lib.ptr(lsk), lsk.numel(),
-            _lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr(),
-        )
-        if rc == -2:
-            raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={k}, R={R}, d={d}")
-        _lib.check(rc, "mgp_posterior_gen")
-        mean_out = mean.reshape(b) if squeeze else mean.reshape(b, R)
-        if want_ykinvy:
-            return mean_out, var, (yk.reshape(b) if squeeze else yk)
-        return mean_out, var
+    gen = spec.kernel == "matern_gen"  # one entry point for every table form (mgp_posterior_gen_*)
+    if gen and path != "auto":
+        raise ValueError("the general-smoothness Matern goes through the dispatcher (path='auto')")
+    if gen and (spec.smoothness is None or not float(spec.smoothness) > 0.0):
+        raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
+    if gathered and path != "auto":
+        raise ValueError("gathered responses go through the dispatcher (path='auto')")
+    # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
+    rows = fn.shape[0] + (0 if test_features is train_features else inp.fq.shape[0])
+    use_packed = path == "auto" and _use_packed(packed, inp, train_features, train_targets, rows, gathered)
+    outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
     rc = -2
-    # gathered responses: the FEATURE rows still come from a prepared table (packed without responses)
-    use_packed = (path == "auto" and packed is not False and b > 0
-                  and PackedTable.supported(d, 0 if gathered else R, k + (R if gathered else 0), dtype))
-    if use_packed and packed == "auto":
-        # a pack is one pass over the table; worth it once the batch gathers a comparable number of rows
-        key = (_tensor_key(train_features), None if gathered else _tensor_key(train_targets))
-        # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
-        rows = fn.shape[0] + (0 if test_features is train_features else fq.shape[0])
-        use_packed = key in _PACK_CACHE or b * (k + 1) >= rows // 4
-    if use_packed and gathered:
-        pn = pack_table(train_features, None, query=False)
+    if use_packed:
+        pn = pack_table(train_features, None if gathered else train_targets, query=False)
         pq = pn if test_features is train_features else pack_table(test_features, None)
-        lsk = pn.kernel_length_scale(ls)
-        rc = _lib.fn("posterior_packed_gathered", dtype)(
-            _lib.ptr(pq.data), pq.stride, _lib.ptr(pn.data), pn.stride, pn.d_kernel, _lib.ptr(bi), _lib.ptr(ni), b, k,
-            _lib.ptr(tg), R, mode, eps, _lib.ptr(nz), spec.kernel_id(), spec.metric_id(), _lib.ptr(lsk), lsk.numel(),
-            _lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr(),
-        )
-    elif use_packed:
-        pn = pack_table(train_features, train_targets)
-        pq = pn if test_features is train_features else pack_table(test_features, None)
-        lsk = pn.kernel_length_scale(ls)
-        rc = _lib.fn("posterior_packed", dtype)(
-            _lib.ptr(pq.data), pq.stride, _lib.ptr(pn.data), pn.stride, pn.d_kernel, _lib.ptr(bi), _lib.ptr(ni), b, k, R,
-            mode, eps, _lib.ptr(nz), spec.kernel_id(), spec.metric_id(), _lib.ptr(lsk), lsk.numel(),
-            _lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr(),
-        )
-    if rc == -2:  # MGP_EUNSUPPORTED on the prepared tables (or not tried): the plain tables
-        base = {"auto": "posterior", "generic": "posterior_generic", "rhs": "posterior_rhs"}[path]
-        if gathered:
-            if path != "auto":
-                raise ValueError("gathered responses go through the dispatcher (path='auto')")
-            base = "posterior_gathered"
-        rc = _lib.fn(base, dtype)(
-            _lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), R,
-            mode, eps, _lib.ptr(nz), spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(),
-            _lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr(),
-        )
-    _lib.check(rc, "mgp_posterior")
-    mean_out = mean.reshape(b) if squeeze else mean.reshape(b, R)
+        call, args = _posterior_call(spec, inp, gathered, path, pq, pn, outs)
+        rc = call(*args)
+    # MGP_EUNSUPPORTED on the prepared tables (or not tried): the plain tables -- for the closed-form kernels only
+    # (matern_gen does NOT retry on the plain tables: the caller gets FusedUnsupported)
+    if rc == -2 and not (gen and use_packed):
+        call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
+        rc = call(*args)
+    if gen and rc == -2:
+        raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={inp.k}, R={R}, d={inp.d}")
+    _lib.check(rc, "mgp_posterior_gen" if gen else "mgp_posterior")
+    mean_out = mean.reshape(b) if inp.squeeze else mean.reshape(b, R)
     if want_ykinvy:
-        return mean_out, var, (yk.reshape(b) if squeeze else yk)
+        return mean_out, var, (yk.reshape(b) if inp.squeeze else yk)
     return mean_out, var
+
+
+def _loocv_call(table, inp: _Inputs, spec: KernelSpec, ls: torch.Tensor, *, eps, mean, var, yk, info, huber_delta: float,
+                partials, scratch, stream):
+    """(entry point, arguments) of one LOOCV evaluation: ``mgp_loocv_packed_*`` on the prepared ``table``, or
+    ``mgp_loocv_*`` on the plain tables (``table`` None).  ``ls``: the length scale(s) the kernel reads -- padded to the
+    table's ``d_kernel`` by the caller; ``eps``: a float, or the ctypes double a prepared evaluation updates in place."""
+    P = _lib.ptr
+    if table is not None:
+        base, head = "loocv_packed", (P(table.data), table.stride, table.d_kernel, P(inp.bi), P(inp.ni), inp.b, inp.k)
+    else:
+        base, head = "loocv", (P(inp.fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg))
+    args = head + (inp.mode, eps, P(inp.nz), spec.kernel_id(), spec.metric_id(), P(ls), ls.numel(), P(mean), P(var), P(yk),
+                   P(info), float(huber_delta), P(partials), P(scratch), stream)
+    return _lib.fn(base, inp.fn.dtype), args
 
 
 def loocv_partials(
@@ -383,48 +429,23 @@ def loocv_partials(
     (_src/optimize/loss/numpy.py:22-61) and the analytic scale (scale/numpy.py:11-18) are built
     from -- no host work between the two.  Returns ``(partials float64 (6,), mean (b,), var (b,))``,
     all on the device.  One response."""
-    _lib.require_cuda(train_features, train_targets, batch_indices, nn_indices)
-    dtype = train_features.dtype
-    if train_targets.dtype != dtype:
-        raise TypeError("features and targets must share one float dtype")
-    fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
-    tg = train_targets.reshape(train_targets.shape[0], -1).contiguous()
-    if tg.shape[1] != 1:
-        raise NotImplementedError("the LOOCV losses are defined for a single response (reference: loss/numpy.py:34-61)")
-    if tg.shape[0] != fn.shape[0]:
-        raise ValueError("train_features and train_targets differ in row count")
-    d = fn.shape[1]
-    ni = nn_indices.to(torch.int64).contiguous()
-    b, k = ni.shape
-    bi = batch_indices.to(torch.int64).contiguous()
-    if bi.shape != (b,):
-        raise ValueError("batch_indices must have shape (batch_count,)")
-    if os.environ.get("MUYGPYS_HIP_CHECK_INDICES") == "1":
-        _check_indices("nn_indices", ni, fn.shape[0])
-        _check_indices("batch_indices", bi, fn.shape[0])
-    ls = _length_scale_tensor(spec.length_scale, d, fn)
-    mode, eps, nz = _noise_args(spec.noise, b, k, fn)
+    inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_targets, responses="single")
+    _debug_check_indices(inp)
+    fn, b, dtype = inp.fn, inp.b, inp.fn.dtype
     mean = torch.empty((b,), device=fn.device, dtype=dtype)
     var = torch.empty((b,), device=fn.device, dtype=dtype)
     yk = torch.empty((b,), device=fn.device, dtype=dtype)
     partials = torch.empty(6, device=fn.device, dtype=torch.float64)
-    scratch = _lib.loocv_scratch(fn.device, b)
-    tail = (mode, eps, _lib.ptr(nz), spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(mean),
-            _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), float(huber_delta), _lib.ptr(partials), _lib.ptr(scratch),
-            _lib.stream_ptr())
+    rest = dict(eps=inp.eps, mean=mean, var=var, yk=yk, info=info, huber_delta=huber_delta, partials=partials,
+                scratch=_lib.loocv_scratch(fn.device, b), stream=_lib.stream_ptr())
     rc = -2
-    use_packed = packed is not False and PackedTable.supported(d, 1, k, dtype) and b > 0
-    if use_packed and packed == "auto":
-        key = (_tensor_key(train_features), _tensor_key(train_targets))
-        use_packed = key in _PACK_CACHE or b * (k + 1) >= fn.shape[0] // 4
-    if use_packed:
+    if _use_packed(packed, inp, train_features, train_targets, fn.shape[0]):
         pn = pack_table(train_features, train_targets)
-        lsk = pn.kernel_length_scale(ls)
-        tail_packed = tail[:5] + (_lib.ptr(lsk), lsk.numel()) + tail[7:]  # (`tail` stays the plain-table call's)
-        rc = _lib.fn("loocv_packed", dtype)(_lib.ptr(pn.data), pn.stride, pn.d_kernel, _lib.ptr(bi), _lib.ptr(ni), b, k,
-                                            *tail_packed)
+        call, args = _loocv_call(pn, inp, spec, pn.kernel_length_scale(inp.ls), **rest)
+        rc = call(*args)
     if rc == -2:
-        rc = _lib.fn("loocv", dtype)(_lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), *tail)
+        call, args = _loocv_call(None, inp, spec, inp.ls, **rest)
+        rc = call(*args)
     if rc != 0:
         _lib.loocv_scratch_reset()
     _lib.check(rc, "mgp_loocv")
@@ -464,24 +485,15 @@ class LoocvPlan:
         _lib.require_cuda(train_features, train_targets, batch_indices, nn_indices, noise_tensor)
         _lib.loocv_tree_selfcheck(train_features.device)  # (once per process: in-kernel walk vs the walk by kernels)
         self.spec = KernelSpec(kernel, metric, 1.0, 0.0)
-        dtype = train_features.dtype
-        if train_targets.dtype != dtype:
-            raise TypeError("features and targets must share one float dtype")
-        fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
-        tg = train_targets.reshape(train_targets.shape[0], -1).contiguous()
-        if tg.shape[1] != 1:
-            raise NotImplementedError("the LOOCV losses are defined for a single response (reference: loss/numpy.py:34-61)")
-        self.d = d = fn.shape[1]
-        self.ni = nn_indices.to(torch.int64).contiguous()
-        self.b, self.k = b, k = self.ni.shape
-        self.bi = batch_indices.to(torch.int64).contiguous()
-        if self.bi.shape != (b,):
-            raise ValueError("batch_indices must have shape (batch_count,)")
-        dev = fn.device
+        # (the noise mode and table are fixed per plan; the length scale is the plan's own buffer below)
+        inp = _normalize(KernelSpec(kernel, metric, 1.0, 0.0 if noise_tensor is None else noise_tensor), train_features,
+                         train_features, batch_indices, nn_indices, train_targets, responses="single")
+        fn, dtype, dev = inp.fn, inp.fn.dtype, inp.fn.device
+        self.d, self.b, self.k, self.ni, self.bi = inp.d, inp.b, inp.k, inp.ni, inp.bi
+        b = inp.b
         self.dtype, self.device, self.anisotropic = dtype, dev, bool(anisotropic)
-        self._keep = (train_features, train_targets, batch_indices, nn_indices, fn, tg, noise_tensor)
-        mode, _, nz = _noise_args(0.0 if noise_tensor is None else noise_tensor, b, k, fn)
-        self._nz = nz
+        self._keep = (train_features, train_targets, batch_indices, nn_indices, fn, inp.tg, noise_tensor)
+        self._nz = inp.nz
         self.mean = torch.empty((b,), device=dev, dtype=dtype)
         self.var = torch.empty((b,), device=dev, dtype=dtype)
         self.ykinvy = torch.empty((b,), device=dev, dtype=dtype)
@@ -496,33 +508,25 @@ class LoocvPlan:
             self.partials = self._res_t
         else:
             self.partials = torch.zeros(6, device=dev, dtype=torch.float64)
-        use_packed = packed is not False and PackedTable.supported(d, 1, k, dtype) and b > 0
+        use_packed = _use_packed(packed, inp, train_features, train_targets, fn.shape[0], threshold=False)
         self._table = pack_table(train_features, train_targets) if use_packed else None
-        dk = self._table.d_kernel if use_packed else d
+        dk = self._table.d_kernel if use_packed else inp.d
         # length scales: Isotropy -- one value in pinned host memory, read once per workgroup; Anisotropy -- the kernels
         # read them per task: a device buffer refreshed by an asynchronous copy from pinned memory
         self._ls_host = torch.ones(dk if anisotropic else 1, dtype=dtype).pin_memory()
         self._ls_np = self._ls_host.numpy()
         self._ls_dev = torch.ones(dk, device=dev, dtype=dtype) if anisotropic else None
-        ls_ptr = _lib.ptr(self._ls_dev if anisotropic else self._ls_host)
-        ls_count = dk if anisotropic else 1
         self._eps = _lib.C.c_double(0.0)  # (the one argument that changes per evaluation: set in place)
-        tail = [mode, self._eps, _lib.ptr(nz), self.spec.kernel_id(), self.spec.metric_id(), ls_ptr, ls_count, _lib.ptr(self.mean),
-                _lib.ptr(self.var), _lib.ptr(self.ykinvy), _lib.ptr(self.info), float(huber_delta), _lib.ptr(self.partials),
-                _lib.ptr(self.scratch)]
-        if use_packed:
-            self._fn = _lib.fn("loocv_packed", dtype)
-            head = [_lib.ptr(self._table.data), self._table.stride, dk, _lib.ptr(self.bi), _lib.ptr(self.ni), b, k]
-        else:
-            self._fn = _lib.fn("loocv", dtype)
-            head = [_lib.ptr(fn), d, _lib.ptr(self.bi), _lib.ptr(self.ni), b, k, _lib.ptr(tg)]
         # (every argument converted once: an evaluation is one foreign call on ready-made objects; the stream is the
         # one current when the plan was made -- the plan's scratch must not serve two streams anyway)
         self._stream = _lib.stream_ptr()
         self._raw_stream = _lib.raw_stream()
         self._in_flight = None  # an event behind the last launch whose completion nobody has observed yet
-        sig = self._fn.argtypes
-        self._args = tuple(a if isinstance(a, _lib.C._SimpleCData) or a is None else t(a) for a, t in zip(head + tail + [self._stream], sig))
+        self._fn, args = _loocv_call(self._table, inp, self.spec, self._ls_dev if anisotropic else self._ls_host,
+                                     eps=self._eps, mean=self.mean, var=self.var, yk=self.ykinvy, info=self.info,
+                                     huber_delta=huber_delta, partials=self.partials, scratch=self.scratch,
+                                     stream=self._stream)
+        self._args = tuple(a if isinstance(a, _lib.C._SimpleCData) or a is None else t(a) for a, t in zip(args, self._fn.argtypes))
         self._np = np
         self._launched = False
 
@@ -600,6 +604,42 @@ class LoocvPlan:
         return self.wait()
 
 
+
+def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want_noise: bool = True):
+    """One backward launch for the hyper-parameters: the per-neighbourhood partials ``(g_l (b, ls_count), g_n (b, k) or
+    None)`` of the cotangents ``gm`` / ``gv`` (either may be None) -- and ``gyk`` of ``y^T K^-1 y``: given, the launch is
+    the LOOCV objective's (``mgp_loocv_backward_*``, one response), else ``mgp_posterior_backward_*`` with no feature or
+    response cotangents.  The noise is ``spec``'s (homoscedastic); everything else comes from ``inp``."""
+    P = _lib.ptr
+    fn, ls = inp.fn, inp.ls
+    g_l = torch.zeros((inp.b, ls.numel()), device=fn.device, dtype=fn.dtype)
+    g_n = torch.zeros((inp.b, inp.k), device=fn.device, dtype=fn.dtype) if want_noise else None
+    gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
+    model = (_lib.NOISE_SCALAR, float(spec.noise), None, spec.kernel_id(), spec.metric_id(), P(ls), ls.numel())
+    shape = (inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg))
+    out = (P(g_l), P(g_n), P(info), _lib.stream_ptr())
+    if gyk is not None:
+        rc = _lib.fn("loocv_backward", fn.dtype)(P(fn), *shape, *model, P(gm), P(gv), P(gyk), *out)
+        _lib.check(rc, "mgp_loocv_backward")
+    else:
+        rc = _lib.fn("posterior_backward", fn.dtype)(P(fn), P(fn), *shape, inp.R, *model, P(gm), P(gv), None, None, None, *out)
+        _lib.check(rc, "mgp_posterior_backward")
+    return g_l, g_n
+
+
+def _hyper_gradient(g_l, g_n, info, what: str, reduce_fn):
+    """The tail of an analytic gradient: the SPD check of the backward launches, deterministic fp64 column sums of
+    their partials, the sum over the ranks -- ``(grad_length_scale (numpy, ls_count), grad_noise (float))``."""
+    import numpy as np
+
+    _lib.raise_if_not_spd(info, what)
+    grad = torch.cat([_lib.column_sums(g_l), _lib.column_sums(g_n.reshape(-1, 1))])  # fp64, deterministic
+    if reduce_fn is not None:
+        reduce_fn(grad)
+    g = grad.cpu().numpy()
+    return np.asarray(g[:-1], dtype=np.float64), float(g[-1])
+
+
 def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_targets: torch.Tensor,
                          batch_indices: torch.Tensor, nn_indices: torch.Tensor, loss: str = "lool",
                          packed: Union[str, bool] = "auto", reduce_fn=None, scale=("analytic", 1),
@@ -639,23 +679,14 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     import copy
     import math
 
-    import numpy as np
-
     if loss not in ("lool", "mse", "pseudo_huber", "looph"):
         raise NotImplementedError(f"analytic gradients are written out for lool, mse, pseudo_huber and looph, not {loss!r}")
     if isinstance(spec.noise, torch.Tensor) and spec.noise.ndim >= 1:
         raise NotImplementedError("analytic gradients: homoscedastic noise")
     if spec.kernel == "matern_gen":
         raise NotImplementedError("analytic gradients: closed-form kernels (fixed smoothness)")
-    dtype = train_features.dtype
-    fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
-    tg = train_targets.reshape(train_targets.shape[0], -1).contiguous()
-    if tg.shape[1] != 1:
-        raise NotImplementedError("the LOOCV losses are defined for a single response (reference: loss/numpy.py:34-61)")
-    d = fn.shape[1]
-    ni = nn_indices.to(torch.int64).contiguous()
-    bi = batch_indices.to(torch.int64).contiguous()
-    b, k = ni.shape
+    inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_targets, responses="single")
+    dtype, tg, ni, bi, k = inp.fn.dtype, inp.tg, inp.ni, inp.bi, inp.k
     needs_scale = loss in ("lool", "looph")
     delta = float(boundary_scale) if boundary_scale is not None else (3.0 if loss == "looph" else 1.5)
     partials, mean, var, yk = loocv_partials(spec, train_features, train_targets, bi, ni, packed=packed, return_ykinvy=True,
@@ -710,32 +741,13 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     zeros = torch.zeros_like(var)
     gv = zeros if gv is None else gv
     gyk_value = dL_ds * ds / (n * k) if needs_scale else 0.0
-    ls = _length_scale_tensor(spec.length_scale, d, fn)
-    info = torch.zeros(1, device=fn.device, dtype=torch.int32)
-
-    def backward(spec_b, gm_b, gv_b, gyk_b, want_noise):
-        g_l = torch.zeros((b, ls.numel()), device=fn.device, dtype=dtype)
-        g_n = torch.zeros((b, k), device=fn.device, dtype=dtype) if want_noise else None
-        rc = _lib.fn("loocv_backward", dtype)(
-            _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), _lib.NOISE_SCALAR, float(spec_b.noise), None,
-            spec_b.kernel_id(), spec_b.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(gm_b.contiguous()), _lib.ptr(gv_b.contiguous()),
-            _lib.ptr(gyk_b), _lib.ptr(g_l), _lib.ptr(g_n), _lib.ptr(info), _lib.stream_ptr(),
-        )
-        _lib.check(rc, "mgp_loocv_backward")
-        return g_l, g_n
-
+    info = torch.zeros(1, device=inp.fn.device, dtype=torch.int32)
     if split_bwd:
-        g_l, g_n = backward(spec, gm, gv, zeros, True)
-        g_l2, _ = backward(spec_s, zeros, zeros, torch.full_like(var, gyk_value), False)
-        g_l = g_l + g_l2
+        g_l, g_n = _hyper_partials(spec, inp, info, gm, gv, zeros)
+        g_l = g_l + _hyper_partials(spec_s, inp, info, zeros, zeros, torch.full_like(var, gyk_value), want_noise=False)[0]
     else:
-        g_l, g_n = backward(spec, gm, gv, torch.full_like(var, gyk_value) if gyk_value != 0.0 else zeros, True)
-    _lib.raise_if_not_spd(info, "LOOCV gradient")
-    grad = torch.cat([_lib.column_sums(g_l), _lib.column_sums(g_n.reshape(-1, 1))])  # fp64, deterministic
-    if reduce_fn is not None:
-        reduce_fn(grad)
-    g = grad.cpu().numpy()
-    return value, np.asarray(g[:-1], dtype=np.float64), float(g[-1])
+        g_l, g_n = _hyper_partials(spec, inp, info, gm, gv, torch.full_like(var, gyk_value) if gyk_value != 0.0 else zeros)
+    return (value, *_hyper_gradient(g_l, g_n, info, "LOOCV gradient", reduce_fn))
 
 
 def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_labels: torch.Tensor,
@@ -754,25 +766,16 @@ def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_l
     the mse count is the global one) and to the gradient.
 
     Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS."""
-    import numpy as np
-
     if loss not in ("cross_entropy", "mse"):
         raise NotImplementedError(f"classification gradients are written out for cross_entropy and mse, not {loss!r}")
     if isinstance(spec.noise, torch.Tensor) and spec.noise.ndim >= 1:
         raise NotImplementedError("analytic gradients: homoscedastic noise")
     if spec.kernel == "matern_gen":
         raise NotImplementedError("analytic gradients: closed-form kernels (fixed smoothness)")
-    dtype = train_features.dtype
-    fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
-    tg = train_labels.contiguous()
-    if tg.ndim != 2 or tg.shape[1] < 2:
-        raise NotImplementedError("the classification losses are defined for two or more response columns")
-    d, R = fn.shape[1], tg.shape[1]
-    ni = nn_indices.to(torch.int64).contiguous()
-    bi = batch_indices.to(torch.int64).contiguous()
-    b, k = ni.shape
+    inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_labels, responses="labels")
+    fn, tg, bi, b, R = inp.fn, inp.tg, inp.bi, inp.b, inp.R
     info = torch.zeros(1, device=fn.device, dtype=torch.int32)
-    mean, _ = posterior_mean_var(spec, fn, fn, bi, ni, tg, info=info, packed=packed)
+    mean, _ = posterior_mean_var(spec, fn, fn, bi, inp.ni, tg, info=info, packed=packed)
     _lib.raise_if_not_spd(info, "classification objective")
     stride = R * tg.element_size()
     if loss == "mse" and reduce_fn is not None:  # the global element count first: the cotangent is scaled by it
@@ -785,21 +788,8 @@ def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_l
             reduce_fn(sums)
     ce, r2sum, count = (float(v) for v in sums[:3].tolist())
     value = ce if loss == "cross_entropy" else r2sum / count
-    ls = _length_scale_tensor(spec.length_scale, d, fn)
-    g_l = torch.zeros((b, ls.numel()), device=fn.device, dtype=dtype)
-    g_n = torch.zeros((b, k), device=fn.device, dtype=dtype)
-    rc = _lib.fn("posterior_backward", dtype)(
-        _lib.ptr(fn), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), R,
-        _lib.NOISE_SCALAR, float(spec.noise), None, spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(),
-        _lib.ptr(gm), None, None, None, None, _lib.ptr(g_l), _lib.ptr(g_n), _lib.ptr(info), _lib.stream_ptr(),
-    )
-    _lib.check(rc, "mgp_posterior_backward")
-    _lib.raise_if_not_spd(info, "classification gradient")
-    grad = torch.cat([_lib.column_sums(g_l), _lib.column_sums(g_n.reshape(-1, 1))])  # fp64, deterministic
-    if reduce_fn is not None:
-        reduce_fn(grad)
-    g = grad.cpu().numpy()
-    return value, np.asarray(g[:-1], dtype=np.float64), float(g[-1])
+    g_l, g_n = _hyper_partials(spec, inp, info, gm, None)
+    return (value, *_hyper_gradient(g_l, g_n, info, "classification gradient", reduce_fn))
 
 
 def loocv_tree_sums(mean: torch.Tensor, var: torch.Tensor, ykinvy: torch.Tensor, train_targets: torch.Tensor,
@@ -838,21 +828,15 @@ def fast_posterior_mean(
     training point ``closest_neighbor (b,)`` and ``coeffs (n_train, k[, R])`` the coefficient
     table (reference workflow: examples/fast_posterior_mean.py:373-400; maths
     _src/gp/muygps/numpy.py:70-77).  Returns ``(b,)`` or ``(b, R)``."""
-    _lib.require_cuda(test_features, train_features, test_indices, closest_set, coeffs, closest_neighbor)
-    dtype = train_features.dtype
-    fq = (test_features[:, None] if test_features.ndim == 1 else test_features).contiguous()
-    fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
-    d = fn.shape[1]
-    ni = closest_set.to(torch.int64).contiguous()
-    b, k = ni.shape
-    bi = None if test_indices is None else test_indices.to(torch.int64).contiguous()
+    _lib.require_cuda(coeffs, closest_neighbor)
+    inp = _normalize(spec, test_features, train_features, test_indices, closest_set, want_noise=False)
+    fq, fn, bi, ni, b, k, d, ls, dtype = inp.fq, inp.fn, inp.bi, inp.ni, inp.b, inp.k, inp.d, inp.ls, inp.fn.dtype
     squeeze = coeffs.ndim == 2
     co = (coeffs[:, :, None] if squeeze else coeffs).to(dtype).contiguous()
     if co.shape[1] != k:
         raise ValueError(f"coefficient rows hold {co.shape[1]} entries but the neighbourhoods have {k}")
     R = co.shape[2]
     crow = closest_neighbor.to(torch.int64).contiguous()
-    ls = _length_scale_tensor(spec.length_scale, d, fn)
     mean = out if out is not None else torch.empty((b, R), device=fn.device, dtype=dtype)
     rc = _lib.fn("fast_posterior_mean", dtype)(
         _lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(co), _lib.ptr(crow), R,
@@ -885,10 +869,8 @@ def fast_coefficients(spec: KernelSpec, train_features: torch.Tensor, train_targ
     R = 1 if squeeze else train_targets.shape[1]
     if R == 1 and fused:
         # one launch: mgp_fast_coefficients_* (fused gather .. LDL^T .. back-substitution)
-        fn = (train_features[:, None] if train_features.ndim == 1 else train_features).contiguous()
-        tg = train_targets.reshape(-1).to(fn.dtype).contiguous()
-        ls = _length_scale_tensor(spec.length_scale, d, fn)
-        mode, eps, nz = _noise_args(spec.noise, n, k, fn)
+        inp = _normalize(spec, train_features, train_features, None, nn_fast, train_targets.to(train_features.dtype))
+        fn, tg, ls, mode, eps, nz = inp.fn, inp.tg, inp.ls, inp.mode, inp.eps, inp.nz
         out = torch.empty((n, k), device=fn.device, dtype=fn.dtype)
         info = torch.zeros(1, device=fn.device, dtype=torch.int32)
         rc = _lib.fn("fast_coefficients", fn.dtype)(

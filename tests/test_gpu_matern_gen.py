@@ -90,6 +90,32 @@ def test_fp64_free_smoothness_is_fused_and_matches_the_reference_fixture():
         posterior_mean_var(KernelSpec("matern_gen", "l2", 2.0, 1e-3, smoothness=0.7), X, X, bi, ni, y)
 
 
+@pytest.mark.parametrize("form", ["plain", "prepared", "gathered"])
+def test_free_smoothness_through_every_table_form(form):
+    """mgp_posterior_gen_* takes all three table forms through one entry point: the plain tables, prepared tables
+    (``packed=True``) and already gathered responses -- each against the reference-generated fp64 model with
+    nu = 0.42, at the tolerance the fixture is held to above."""
+    from muygpys_amd import _lib
+    from muygpys_amd.fused import KernelSpec, posterior_mean_var
+    from tests.conftest import load_golden
+
+    g = load_golden("gen_m042_iso_k10_d6")
+    meta = g["meta"]
+    X, y = to_dev(g["features"], torch.float64), to_dev(g["targets"], torch.float64)
+    bi, ni = to_dev(g["batch_idx"]), to_dev(g["nn_idx"])
+    spec = KernelSpec("matern_gen", meta["metric"], meta["length_scale"], meta["noise"], smoothness=meta["smoothness"])
+    how = {"plain": dict(packed=False), "prepared": dict(packed=True), "gathered": dict(gathered=True)}[form]
+    mean, var = posterior_mean_var(spec, X, X, bi, ni, y[ni] if form == "gathered" else y, **how)
+    torch.cuda.synchronize()
+    served = _lib.last_kernel()
+    assert "gen64" in served, served
+    if form != "gathered":
+        # template arguments <T, NP, KFIX, RFIX, DFIX, PIPED, COEFF, PACKED, GRAM, gen64>: the table form that really ran
+        assert served.split("<")[1].split(",")[7] == ("true" if form == "prepared" else "false"), served
+    assert_close(mean.cpu().numpy(), g["mean"], 1e-5, f"mean [{form}]")
+    assert_close(var.cpu().numpy(), g["var_unscaled"], 1e-5, f"var [{form}]")
+
+
 def test_free_smoothness_objective_is_one_fused_launch_and_close_to_fixed_smoothness_speed(capsys):
     """The point of the exercise: an objective evaluation with a FREE smoothness (the general Bessel form)
     at the BASELINE config-2 shape, against the same evaluation at the fixed nu = 3/2 closed form.  Before
