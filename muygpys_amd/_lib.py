@@ -14,14 +14,25 @@ import re
 
 import torch  # noqa: F401  (must precede the dlopen below)
 
+from muygpys_amd import _abi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # MUYGPYS_HIP_LIB points at an alternative build of the same ABI (kernel A/B experiments)
 LIB_PATH = os.environ.get("MUYGPYS_HIP_LIB") or os.path.join(HERE, "lib", "libmuygpys_hip.so")
-HEADER = os.path.join(HERE, "..", "include", "muygpys_hip.h")
+HEADER = _abi.HEADER
 
-KERNEL_IDS = {"rbf": 0, "matern05": 1, "matern15": 2, "matern25": 3, "maternInf": 4, "matern_gen": 5}
-METRIC_IDS = {"l2": 0, "F2": 1}
-NOISE_SCALAR, NOISE_TABLE, NOISE_BATCH = 0, 1, 2
+# the header's enums under Python's names (a name the header lacks is a KeyError at import)
+_E = _abi.enums()
+KERNEL_IDS = {name: _E["MGP_KERNEL_" + enum] for name, enum in (
+    ("rbf", "RBF"), ("matern05", "MATERN_05"), ("matern15", "MATERN_15"), ("matern25", "MATERN_25"),
+    ("maternInf", "MATERN_INF"), ("matern_gen", "MATERN_GEN"),
+)}
+METRIC_IDS = {"l2": _E["MGP_METRIC_L2"], "F2": _E["MGP_METRIC_F2"]}
+NOISE_SCALAR, NOISE_TABLE, NOISE_BATCH = _E["MGP_NOISE_SCALAR"], _E["MGP_NOISE_TABLE"], _E["MGP_NOISE_BATCH"]
+CLASS_LOSS_IDS = {"cross_entropy": _E["MGP_CLASS_LOSS_CROSS_ENTROPY"], "mse": _E["MGP_CLASS_LOSS_MSE"]}
+SHEAR_33, SHEAR_KIN23, SHEAR_KCROSS23 = _E["MGP_SHEAR_33"], _E["MGP_SHEAR_KIN23"], _E["MGP_SHEAR_KCROSS23"]
+SHEAR_NOISE_HOMOSCEDASTIC, SHEAR_NOISE_33 = _E["MGP_SHEAR_NOISE_HOMOSCEDASTIC"], _E["MGP_SHEAR_NOISE_33"]
+OK, EINVAL, EUNSUPPORTED, EHIP = _E["MGP_OK"], _E["MGP_EINVAL"], _E["MGP_EUNSUPPORTED"], _E["MGP_EHIP"]
 
 _lib = None
 
@@ -31,63 +42,18 @@ class HipLibraryError(RuntimeError):
 
 
 def _status_message(rc: int) -> str:
-    if rc == -1:
+    if rc == EINVAL:
         return "MGP_EINVAL (null pointer / bad size / unknown enum)"
-    if rc == -2:
+    if rc == EUNSUPPORTED:
         return "MGP_EUNSUPPORTED (shape outside what the kernels were built for)"
-    if rc <= -1000:
-        return f"HIP runtime error {-rc - 1000}"
+    if rc <= EHIP:
+        return f"HIP runtime error {EHIP - rc}"
     return f"status {rc}"
 
 
 def check(rc: int, what: str) -> None:
-    if rc != 0:
+    if rc != OK:
         raise HipLibraryError(f"{what} failed: {_status_message(rc)}")
-
-
-_p = C.c_void_p
-_i = C.c_int
-_l = C.c_int64
-_d = C.c_double
-
-_SIGS = {
-    "posterior": [_p, _p, _i, _p, _p, _l, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p],
-    "crosswise_diffs": [_p, _p, _i, _p, _p, _l, _i, _p, _p],
-    "pairwise_diffs": [_p, _i, _p, _l, _i, _p, _p],
-    "crosswise_dists": [_p, _p, _i, _p, _p, _l, _i, _i, _p, _p],
-    "pairwise_dists": [_p, _i, _p, _l, _i, _i, _p, _p],
-    "reduce_diffs": [_p, _l, _i, _p, _i, _p, _p],
-    "kernel_apply": [_p, _l, _i, _d, _p, _p],
-    "perturb": [_p, _l, _i, _i, _d, _p, _p, _p],
-    "matern_gen": [_p, _l, _d, _d, _p, _p],
-    "solve": [_p, _p, _p, _l, _i, _i, _d, _p, _p, _p, _p, _p, _p],
-    "posterior_generic": [_p, _p, _i, _p, _p, _l, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p],
-    "posterior_rhs": [_p, _p, _i, _p, _p, _l, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p],
-    "posterior_gathered": [_p, _p, _i, _p, _p, _l, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p],
-    "posterior_packed": [_p, _l, _p, _l, _i, _p, _p, _l, _i, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p],
-    "posterior_packed_gathered": [_p, _l, _p, _l, _i, _p, _p, _l, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p],
-    "posterior_gen": [_p, _p, _p, _l, _p, _l, _i, _p, _p, _l, _i, _p, _i, _i, _i, _d, _p, _d, _i, _p, _i, _p, _p, _p, _p, _p],
-    "table_pack": [_p, _p, _l, _i, _i, _p, _l, _p],
-    "loocv": [_p, _i, _p, _p, _l, _i, _p, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _d, _p, _p, _p],
-    "loocv_packed": [_p, _l, _i, _p, _p, _l, _i, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _d, _p, _p, _p],
-    "loocv_tree": [_p, _p, _p, _p, _l, _p, _l, _d, _i, _i, _p, _p, _p],
-    "loss_sums": [_p, _p, _p, _l, _p, _d, _d, _p, _p, _p],
-    "column_sums": [_p, _l, _i, _p, _p, _p],
-    "loocv_backward": [_p, _i, _p, _p, _l, _i, _p, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p],
-    "posterior_backward": [_p, _p, _i, _p, _p, _l, _i, _p, _i, _i, _d, _p, _i, _i, _p, _i,
-                           _p, _p, _p, _p, _p, _p, _p, _p, _p],
-    "fast_coefficients": [_p, _i, _p, _l, _i, _p, _i, _d, _p, _i, _i, _p, _i, _p, _p, _p],
-    "fast_posterior_mean": [_p, _p, _i, _p, _p, _l, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p],
-    "shear_tensor": [_p, _l, _i, _i, _i, _d, _p, _p],
-    "solve_multi": [_p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p],
-    "shear_posterior": [_p, _p, _p, _p, _l, _i, _i, _p, _l, _i, _d, _i, _d, _p, _p, _p, _p, _p],
-    "class_sums": [_p, _p, _l, _p, _l, _i, _i, _d, _d, _p, _p, _p, _p],
-    "class_partition": [_p, _l, _i, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p],
-    "class_scatter": [_p, _p, _p, _l, _l, _i, _p, _p, _p],
-}
-CLASS_LOSS_IDS = {"cross_entropy": 0, "mse": 1}
-SHEAR_33, SHEAR_KIN23, SHEAR_KCROSS23 = 0, 1, 2
-SHEAR_NOISE_HOMOSCEDASTIC, SHEAR_NOISE_33 = 0, 1
 
 
 def exported_names_from_header():
@@ -98,7 +64,7 @@ def exported_names_from_header():
 
 
 def load():
-    """dlopen the library (once) and attach argtypes.  Raises if it is not built."""
+    """dlopen the library (once) and bind every function the header declares.  Raises if it is not built."""
     global _lib
     if _lib is not None:
         return _lib
@@ -107,61 +73,8 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(there is no CPU fallback for the hip backend)"
         )
-    lib = C.CDLL(LIB_PATH)
-    lib.mgp_version.restype = C.c_char_p
-    lib.mgp_max_nn_count.argtypes = [_i, _i]
-    lib.mgp_max_nn_count.restype = _i
-    lib.mgp_max_nn_count_backward.argtypes = [_i]
-    lib.mgp_max_nn_count_backward.restype = _i
-    lib.mgp_knn_scan_f32.argtypes = [_p, _p, _l, _i, _p, _p, _p, _l, _i, _l, _p, _p, _p, _p]
-    lib.mgp_knn_scan_f32.restype = _i
-    lib.mgp_knn_scan_bf16x3.argtypes = [_p, _p, _p, _l, _i, _p, _p, _p, _p, _l, _i, _l, _p, _p, _p, _p]
-    lib.mgp_knn_scan_bf16x3.restype = _i
-    lib.mgp_knn_scan_bf16x2_d8.argtypes = lib.mgp_knn_scan_bf16x3.argtypes
-    lib.mgp_knn_scan_bf16x2_d8.restype = _i
-    lib.mgp_topk_rows_f32.argtypes = [_p, _l, _i, _l, _i, _p, _p, _p]
-    lib.mgp_topk_rows_f32.restype = _i
-    lib.mgp_knn_finish_f32.argtypes = [_p, _p, _i, _p, _l, _i, _p, _p, _p, _p]
-    lib.mgp_knn_finish_f32.restype = _i
-    lib.mgp_posterior_kernel_name.argtypes = [_i, _i, _i, _i, _i, _i, C.c_char_p, _i]
-    lib.mgp_posterior_kernel_name.restype = _i
-    lib.mgp_allreduce_partials.argtypes = [_p, _i, _p, _p]
-    lib.mgp_allreduce_partials.restype = _i
-    lib.mgp_last_kernel_name.argtypes = [C.c_char_p, _i]
-    lib.mgp_last_kernel_name.restype = _i
-    lib.mgp_reduce_scratch_doubles.restype = _i
-    for name in ("mgp_loocv_scratch_bytes", "mgp_loocv_scratch_zero_bytes"):
-        getattr(lib, name).argtypes = []
-        getattr(lib, name).restype = _l
-    lib.mgp_last_launch_geometry.argtypes = [C.POINTER(_l), C.POINTER(_i)]
-    lib.mgp_last_launch_geometry.restype = _i
-    lib.mgp_last_loocv_geometry.argtypes = [C.POINTER(_i), C.POINTER(_i)]
-    lib.mgp_last_loocv_geometry.restype = _i
-    lib.mgp_loocv_tree_mode_get.argtypes = []
-    lib.mgp_loocv_tree_mode_get.restype = _i
-    lib.mgp_loocv_tree_mode_set.argtypes = [_i]
-    lib.mgp_loocv_tree_mode_set.restype = _i
-    lib.mgp_matern_gen_constants.argtypes = [_d, C.POINTER(C.c_double)]
-    lib.mgp_matern_gen_constants.restype = _i
-    lib.mgp_jit_prepare.argtypes = [_i, _i, _i, _i, _i, _i]
-    lib.mgp_jit_prepare.restype = _i
-    lib.mgp_jit_prepare_backward.argtypes = [_i, _i, _i, _i]
-    lib.mgp_jit_prepare_backward.restype = _i
-    lib.mgp_jit_mode.argtypes = []
-    lib.mgp_jit_mode.restype = _i
-    lib.mgp_jit_loaded_count.argtypes = []
-    lib.mgp_jit_loaded_count.restype = _i
-    lib.mgp_shear_max_nn_count.argtypes = [_i, _i]
-    lib.mgp_shear_max_nn_count.restype = _i
-    lib.mgp_packed_row_bytes.argtypes = [_i, _i, _i]
-    lib.mgp_packed_row_bytes.restype = _l
-    for base, sig in _SIGS.items():
-        for suf in ("f32", "f64"):
-            fn = getattr(lib, f"mgp_{base}_{suf}")
-            fn.argtypes = sig
-            fn.restype = _i
-    _lib = lib
-    return lib
+    _lib = _abi.bind(C.CDLL(LIB_PATH))
+    return _lib
 
 
 def suffix(dtype) -> str:
@@ -199,7 +112,7 @@ def served_by(d: int, k: int, R: int, dtype, packed: bool = False, path: str = "
     buf = C.create_string_buffer(256)
     es = 4 if dtype == torch.float32 else 8
     rc = load().mgp_posterior_kernel_name(es, d, k, R, int(bool(packed)), {"auto": 0, "generic": 1, "rhs": 2}[path], buf, 256)
-    if rc == -2 and packed:
+    if rc == EUNSUPPORTED and packed:
         return served_by(d, k, R, dtype, False, path)
     check(rc, "mgp_posterior_kernel_name")
     return buf.value.decode()
@@ -365,7 +278,7 @@ def class_sums(pred, target, target_stride_bytes: int, batch_idx, loss: str = "c
         ptr(pred), ptr(target), int(target_stride_bytes), ptr(batch_idx), b, R, CLASS_LOSS_IDS[loss], float(grad_scale),
         float(huber_delta), ptr(grad), ptr(out), ptr(scratch), stream_ptr(),
     )
-    if rc == -2:
+    if rc == EUNSUPPORTED:
         raise NotImplementedError(f"the classification sums serve 2 to 62 response columns; got {R}")
     check(rc, "mgp_class_sums")
     return out, grad

@@ -63,7 +63,7 @@ def _solve_multi(Kin, Kcross, Y, want=("mean",)):
         _lib.ptr(K), _lib.ptr(Kc), _lib.ptr(Yc), B, n, m, R, _lib.ptr(mean), _lib.ptr(kk), None, _lib.ptr(info),
         _lib.stream_ptr(),
     )
-    if rc == -2:
+    if rc == _lib.EUNSUPPORTED:
         raise ValueError(f"a local system of {n} rows with {m} outputs does not fit the LDS-resident solve")
     _lib.check(rc, "mgp_solve_multi")
     _lib.raise_if_not_spd(info, "mgp_solve_multi")

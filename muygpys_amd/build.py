@@ -220,14 +220,13 @@ PREWARM_BWD = ((8, 40, 8), (8, 40, 16), (8, 50, 16), (8, 32, 8), (4, 30, 16), (4
 
 # one process of the cache fill: compiles the shapes it is given (JSON) into the library's cache and prints one return
 # code per shape.  A plain `python -c` child: it never re-imports the caller's main module, as a multiprocessing
-# worker started by "spawn" does (and a caller without a __main__ guard would start the build again in every worker)
+# worker started by "spawn" does (and a caller without a __main__ guard would start the build again in every worker).
+# It binds the library from the header (_abi imports neither torch nor anything else of the package)
 _PREWARM_WORKER = r"""
 import ctypes, json, sys
-lib = ctypes.CDLL(sys.argv[1])
-lib.mgp_jit_prepare.argtypes = [ctypes.c_int] * 6
-lib.mgp_jit_prepare.restype = ctypes.c_int
-lib.mgp_jit_prepare_backward.argtypes = [ctypes.c_int] * 4
-lib.mgp_jit_prepare_backward.restype = ctypes.c_int
+sys.path.insert(0, sys.argv[3])
+from muygpys_amd import _abi
+lib = _abi.bind(ctypes.CDLL(sys.argv[1]))
 for es, k, d, packed in json.loads(sys.argv[2]):
     if packed == "bwd":
         rc = lib.mgp_jit_prepare_backward(es, k, d, 2)
@@ -250,7 +249,7 @@ def prewarm(verbose: bool = False) -> int:
     workers = []
     for i in range(n):
         err = tempfile.TemporaryFile(mode="w+")
-        cmd = [sys.executable, "-c", _PREWARM_WORKER, LIB, json.dumps(jobs[i::n])]
+        cmd = [sys.executable, "-c", _PREWARM_WORKER, LIB, json.dumps(jobs[i::n]), os.path.dirname(HERE)]
         workers.append((subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=err, text=True), err))
     codes = []
     for p, err in workers:
@@ -274,7 +273,9 @@ def prewarm(verbose: bool = False) -> int:
     if ok and os.path.isdir(jit):
         import ctypes
 
-        lib = ctypes.CDLL(LIB)
+        from muygpys_amd import _abi
+
+        lib = _abi.bind(ctypes.CDLL(LIB))
         buf = ctypes.create_string_buffer(32)
         if lib.mgp_jit_source_hash(buf, 32) == 0:
             current = buf.value.decode() + ".hsaco"

@@ -385,10 +385,10 @@ def posterior_mean_var(
         rc = call(*args)
     # MGP_EUNSUPPORTED on the prepared tables (or not tried): the plain tables -- for the closed-form kernels only
     # (matern_gen does NOT retry on the plain tables: the caller gets FusedUnsupported)
-    if rc == -2 and not (gen and use_packed):
+    if rc == _lib.EUNSUPPORTED and not (gen and use_packed):
         call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
         rc = call(*args)
-    if gen and rc == -2:
+    if gen and rc == _lib.EUNSUPPORTED:
         raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={inp.k}, R={R}, d={inp.d}")
     _lib.check(rc, "mgp_posterior_gen" if gen else "mgp_posterior")
     mean_out = mean.reshape(b) if inp.squeeze else mean.reshape(b, R)
@@ -443,7 +443,7 @@ def loocv_partials(
         pn = pack_table(train_features, train_targets)
         call, args = _loocv_call(pn, inp, spec, pn.kernel_length_scale(inp.ls), **rest)
         rc = call(*args)
-    if rc == -2:
+    if rc == _lib.EUNSUPPORTED:
         call, args = _loocv_call(None, inp, spec, inp.ls, **rest)
         rc = call(*args)
     if rc != 0:
@@ -842,7 +842,7 @@ def fast_posterior_mean(
         _lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(co), _lib.ptr(crow), R,
         spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(mean), _lib.stream_ptr(),
     )
-    if rc == -2:
+    if rc == _lib.EUNSUPPORTED:
         raise FusedUnsupported(f"mgp_fast_posterior_mean serves k + 1 <= 64 slots; got nn_count = {k}")
     _lib.check(rc, "mgp_fast_posterior_mean")
     return mean.reshape(b) if squeeze else mean

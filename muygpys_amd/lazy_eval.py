@@ -258,7 +258,7 @@ def _shear_launch(Kin, Kcross, tg, stride, col, gathered):
         float(Kin.length_scale), mode, noise, _lib.ptr(mean), _lib.ptr(kk), _lib.ptr(yk), _lib.ptr(info),
         _lib.stream_ptr(),
     )
-    if rc == -2:
+    if rc == _lib.EUNSUPPORTED:
         limit = _lib.shear_max_nn_count(dt, Kin.in_count)
         raise ValueError(f"the fused shear posterior serves nn_count <= {limit} at {dt} with {Kin.in_count} inputs; got {k}")
     _lib.check(rc, "mgp_shear_posterior")

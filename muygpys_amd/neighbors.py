@@ -169,7 +169,7 @@ class NN_Wrapper:
             rc_sel = _lib.load().mgp_topk_rows_f32(_lib.ptr(d2), d2.shape[0], d2.shape[1], d2.stride(0), k,
                                                    _lib.ptr(best_d[s:s + init_chunk]), _lib.ptr(best_i[s:s + init_chunk]),
                                                    _lib.stream_ptr())
-            if rc_sel == -2:  # (more than 4 096 columns: not this path's sizes)
+            if rc_sel == _lib.EUNSUPPORTED:  # (more than 4 096 columns: not this path's sizes)
                 bd, bi = d2.topk(k, dim=1, largest=False)
                 best_d[s:s + init_chunk] = bd
                 best_i[s:s + init_chunk] = bi.to(torch.int32)
@@ -211,7 +211,7 @@ class NN_Wrapper:
                 _lib.ptr(q), _lib.ptr(qn), _lib.ptr(ex64), m, k, init_rows,
                 _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
             )
-        if rc == -2:  # MGP_EUNSUPPORTED (alignment)
+        if rc == _lib.EUNSUPPORTED:  # MGP_EUNSUPPORTED (alignment)
             return None
         _lib.check(rc, "mgp_knn_scan_f32")
         # the winners re-measured in difference form, put in order and mapped to the caller's row numbers in one launch
@@ -220,7 +220,7 @@ class NN_Wrapper:
         dist = torch.empty((m, k), dtype=q.dtype, device=q.device)
         rc_fin = _lib.load().mgp_knn_finish_f32(_lib.ptr(q), _lib.ptr(self.train), self.feature_count, _lib.ptr(best_i), m, k,
                                                 None, _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr())
-        if rc_fin == -2:
+        if rc_fin == _lib.EUNSUPPORTED:
             cand = best_i.to(torch.int64)
             for s in range(0, m, 65536):
                 c = cand[s:s + 65536]

@@ -13,7 +13,7 @@ import ctypes as C
 import pytest
 import torch
 
-from muygpys_amd import _lib, fused
+from muygpys_amd import _abi, _lib, fused
 from muygpys_amd.fused import FusedUnsupported, KernelSpec
 
 K, D, R, B, N, NQ = 5, 3, 2, 7, 40, 9
@@ -36,7 +36,7 @@ class Recorder:
             queue = self.statuses.get(base)
             return queue.pop(0) if queue else 0
 
-        call.argtypes = _lib._SIGS[base]
+        call.argtypes = _abi.signatures()[f"mgp_{base}_{_lib.suffix(dtype)}"][1]
         return call
 
     def of(self, *skip):

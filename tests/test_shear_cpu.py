@@ -81,9 +81,7 @@ def test_shear_abi_rejects_bad_arguments_without_a_gpu():
     args = lambda **kw: [kw.get(n, v) for n, v in (
         ("fq", p), ("fn", p), ("bi", i), ("ni", i), ("b", 1), ("k", 4), ("in_", 3), ("tg", p), ("ts", 3), ("tb", 0),
         ("ls", 1.0), ("nm", 1), ("eps", 1e-3), ("mean", p), ("kk", p), ("yk", p), ("info", info), ("st", None))]
-    f64 = lib.mgp_shear_posterior_f64
-    f64.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int,
-                                       C.c_double] + [C.c_void_p] * 5
+    f64 = lib.mgp_shear_posterior_f64  # (bound from the header by _lib.load, like every entry point)
     for bad in (dict(fq=None), dict(fn=None), dict(ni=None), dict(tg=None), dict(mean=None), dict(kk=None),
                 dict(in_=4), dict(nm=2), dict(in_=2, nm=1), dict(ts=2), dict(ls=-1.0), dict(k=0), dict(b=-1),
                 dict(eps=-1.0)):
