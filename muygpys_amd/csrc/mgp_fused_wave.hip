@@ -13,18 +13,6 @@ int g_grid_per_cu = 0;  // override of resident workgroups per CU
 int g_lds_pad = 0;      // extra dynamic LDS bytes per workgroup
 #endif
 
-// fp32 pipelined kernels compute the squared distances in the Gram form, except for the Matern-1/2
-// kernel (and the general Matern below nu = 1): exp(-r) has a kink at r = 0, so the absolute error a
-// cancelling Gram form leaves in a tiny squared distance (duplicated training points) would show up at
-// first order there.
-// In fp64 the Gram form is used for every kernel: its absolute error in a squared distance, ~1e-16 r^2, is
-// eleven orders below the 1e-5 the results are held to.
-template <typename T>
-static bool gram_allowed(const FusedArgs& a) {
-  if (sizeof(T) == 8) return MGP_GRAM64 != 0;
-  return a.kernel_id != MGP_KERNEL_MATERN_05 && !(a.kernel_id == MGP_KERNEL_MATERN_GEN && a.smoothness < 1.0);
-}
-
 // (launch_np_impl is instantiated in mgp_fused_wave_inst_*.hip; here only the calls)
 template <typename T, int NP, int KFIX, int RFIX, int DFIX, bool PIPED, bool COEFF, bool PACKED, bool GRAM, bool GEN64 = false>
 static int launch_inst(const FusedArgs& a, hipStream_t stream) {
@@ -42,7 +30,7 @@ static int launch_np(const FusedArgs& a, hipStream_t stream) {
     }
   }
   if constexpr (PIPED && !COEFF && MGP_GRAM && (sizeof(T) == 4 || MGP_GRAM64)) {
-    if (gram_allowed<T>(a)) return launch_inst<T, NP, KFIX, RFIX, DFIX, PIPED, COEFF, PACKED, true>(a, stream);
+    if (wave_gram(sizeof(T), a.kernel_id, a.smoothness)) return launch_inst<T, NP, KFIX, RFIX, DFIX, PIPED, COEFF, PACKED, true>(a, stream);
   }
   return launch_inst<T, NP, KFIX, RFIX, DFIX, PIPED, COEFF, PACKED, false>(a, stream);
 }
@@ -57,64 +45,21 @@ static int static_slots(int es, int d, int k, int R, bool packed, bool gathered)
 }
 
 // A static shape the library was not built with: the instantiation compiled at run time (mgp_jit.hip).
-// Same geometry code as launch_np_impl, from wave_dims() evaluated at run time.
+// Same geometry code as launch_np_impl, from the shape as run-time values.
 template <typename T>
 static int launch_jit(const FusedArgs& a, hipStream_t stream) {
   const bool packed = a.packed_nn != nullptr;
   const int NP = static_slots(sizeof(T), a.d, a.k, a.R, packed, a.targets_batch != 0);
   if (NP == 0 || a.coeffs != nullptr) return MGP_EUNSUPPORTED;
-  const uintptr_t align = packed ? ((uintptr_t)a.packed_q | (uintptr_t)a.packed_nn | (uintptr_t)a.q_stride | (uintptr_t)a.nn_stride)
-                                 : ((uintptr_t)a.feat_q | (uintptr_t)a.feat_nn);
-  if (align % 16 != 0) return MGP_EUNSUPPORTED;
   const bool gen64 = sizeof(T) == 8 && a.kernel_id == MGP_KERNEL_MATERN_GEN;
-  const bool gram = MGP_GRAM && gram_allowed<T>(a) && !gen64;
+  const WaveShape s{(int)sizeof(T), NP, a.k, a.R, a.d, true, false, packed, wave_gram(sizeof(T), a.kernel_id, a.smoothness), gen64, false, true};
+  WaveLaunch w = wave_geometry(a, s);
+  if (w.status != MGP_OK) return w.status;  // (unaligned rows: everything else static_slots has refused)
   hipFunction_t fn = nullptr;
-  const int jrc = jit_wave_function(sizeof(T), NP, a.k, a.R, a.d, packed, gram, &fn, jit_mode() == 2 || a.b >= jit_min_batch(), gen64);
+  const int jrc = jit_wave_function(s.es, NP, a.k, a.R, a.d, packed, s.gram, &fn, jit_mode() == 2 || a.b >= jit_min_batch(), gen64);
   if (jrc != MGP_OK) return jrc;
-  const WaveDims WD = wave_dims(sizeof(T), NP, a.k, a.R, a.d, false, gram);
-  WaveGeom g;
-  g.mask = 0xF;
-  g.q = a.k;
-  const int dpad = (a.d + WD.CH - 1) / WD.CH * WD.CH;
-  g.dst = dpad;
-  g.xs = g.dst + WD.E;
-  g.vec_ok = 1;
-  g.ntasks = (a.b + WD.NH - 1) / WD.NH;
-  const size_t tile_feat = (size_t)wave_tile_rows(WD, NP, a.k, g.xs) * g.xs + wave_stage_elems(WD), tile_mat = (size_t)WD.NH * WD.KMAT;
-  const size_t tile_elems = tile_feat > tile_mat ? tile_feat : tile_mat;
-  size_t lds = tile_elems * sizeof(T) + wave_colbuf_bytes(sizeof(T), NP, wave_fold(sizeof(T), NP, a.k, a.R, a.d, true, false, gram));
-  lds = (lds + 15) & ~(size_t)15;
-  gen_geometry(a, &g, &lds, (int)sizeof(T));
   static Residency res;
-  int per_cu = 0, cus = 0;
-  const int rrc = res.lookup(fn, 64, lds, &per_cu, &cus);
-  if (rrc != MGP_OK) return rrc;
-#ifdef MGP_DEBUG_HOOKS
-  if (g_grid_per_cu > 0) per_cu = g_grid_per_cu;
-#endif
-  static const int env_per_cu = getenv("MGP_JIT_PER_CU") ? atoi(getenv("MGP_JIT_PER_CU")) : 0;  // occupancy experiments
-  if (env_per_cu > 0 && env_per_cu < per_cu) per_cu = env_per_cu;
-  int64_t grid = (int64_t)cus * per_cu / 8 * 8;
-  if (grid < 8) grid = 8;
-  if (grid > g.ntasks) grid = (g.ntasks + 7) / 8 * 8;
-  if (a.tree.out && grid > kTreeMaxLeaves) return MGP_EUNSUPPORTED;  // (as launch_np_impl)
-  static const bool trace = getenv("MGP_TRACE") != nullptr;
-  if (trace)
-    fprintf(stderr, "mgp: [run-time compiled] fused_wave_kernel<%s,%d,%d,%d,%d,pipe%s%s> b=%lld grid=%lld lds=%zu\n",
-            sizeof(T) == 4 ? "float" : "double", NP, a.k, a.R, a.d, packed ? ",packed" : "", gram ? ",gram" : "", (long long)a.b,
-            (long long)grid, lds);
-  FusedArgs args = a;
-  args.tree.grid = (int)grid;  // (the leaves of the reduction tree are this launch's workgroups)
-  args.tree.nh = WD.NH;
-  if (a.tree.mode == kTreeThreeLaunch) args.tree.out = nullptr;  // (as launch_np_impl)
-  void* params[] = {&args, &g};
-  const hipError_t err = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 64, 1, 1, (unsigned)lds, stream, params, nullptr);
-  if (err != hipSuccess) return -(1000 + (int)err);
-  note_launch("mgp::fused_wave_kernel<%s,%d,%d,%d,%d,true,false,%s,%s%s> [run-time compiled]", sizeof(T) == 4 ? "float" : "double", NP,
-              a.k, a.R, a.d, packed ? "true" : "false", gram ? "true" : "false", gen64 ? ",gen64" : "");
-  note_tree_geometry(a.tree.out ? (int)grid : 0, WD.NH);
-  note_launch_geometry(grid, lds);
-  return MGP_OK;
+  return wave_launch(fn, res, a, s, w, stream);
 }
 
 template <typename T>
@@ -130,7 +75,7 @@ int launch_fused_wave(const FusedArgs& a, hipStream_t stream) {
   }
   // other static shapes: the instantiation compiled at run time, when allowed and worth it (mgp_jit.hip)
   const bool gen64 = sizeof(T) == 8 && a.kernel_id == MGP_KERNEL_MATERN_GEN;  // (no built-in static instantiation)
-  const bool builtin = !gen64 && a.R == 1 && ((a.k == 30 && a.d == 40) || (a.k == 50 && a.d == 8));
+  const bool builtin = wave_builtin(sizeof(T), a.k, a.R, a.d, false, gen64, false);
   // (calls from MUYGPYS_HIP_JIT_MIN_BATCH neighbourhoods on may compile; shorter ones, from
   // MUYGPYS_HIP_JIT_CACHED_MIN_BATCH on, take a kernel that is loaded or in the disk cache already)
   const bool try_jit = !builtin && jit_mode() != 0 && (jit_mode() == 2 || a.b >= jit_cached_min_batch());
@@ -192,11 +137,10 @@ int describe_fused_wave(int elem_size, int d, int k, int R, int packed, char* bu
 // compile the static instantiation of a shape into the disk cache (no GPU needed)
 int prepare_fused_wave(int elem_size, int d, int k, int R, int packed, int kernel_id) {
   const bool gen64 = elem_size == 8 && kernel_id == MGP_KERNEL_MATERN_GEN;  // (fp64 general Matern: an instantiation of its own)
-  if (!gen64 && R == 1 && ((k == 30 && d == 40) || (k == 50 && d == 8))) return MGP_OK;  // built into the library
+  if (wave_builtin(elem_size, k, R, d, false, gen64, false)) return MGP_OK;
   const int np = static_slots(elem_size, d, k, R, packed != 0, false);
   if (np == 0) return MGP_EUNSUPPORTED;
-  const bool gram = !gen64 && MGP_GRAM && (elem_size == 8 ? MGP_GRAM64 != 0 : kernel_id != MGP_KERNEL_MATERN_05);
-  return jit_wave_prepare(elem_size, np, k, R, d, packed != 0, gram, gen64);
+  return jit_wave_prepare(elem_size, np, k, R, d, packed != 0, wave_gram(elem_size, kernel_id, 1.0), gen64);
 }
 
 template int launch_fused_wave<float>(const FusedArgs&, hipStream_t);
