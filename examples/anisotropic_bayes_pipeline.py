@@ -5,11 +5,14 @@ d = 8, leave-one-out likelihood, full Bayes-opt hyper-parameter loop, then predi
 model is told about.)
 
     python examples/anisotropic_bayes_pipeline.py [--points 1000000] [--batch 1000000] [--optimizer bayes]
+                                                  [--nn-method exact|ivf] [--nlist N] [--nprobe P]
 
 Stages (each timed): synthetic data with planted per-feature length scales -> exact k-NN on the
 GPU (fused MFMA scan, fp32 features) -> LOOCV batch -> optimiser over the d length scales (every
 objective evaluation is ONE fused launch + a 7-scalar reduction) -> analytic sigma^2 -> posterior
-mean / variance for held-out points.  ``--points 10000000`` is the BASELINE size.
+mean / variance for held-out points.  ``--points 10000000`` is the BASELINE size.  ``--nn-method ivf`` swaps the exact
+search for the approximate inverted-cell index (fp32, d <= 64, k <= 64) and reports its recall against the exact scan
+on 4 000 sampled batch rows.
 """
 
 import argparse
@@ -63,7 +66,7 @@ def synth(n, d, true_ls, gen, noise_std=0.03, features=2048, chunk=1 << 20):
 
 
 def run(points=1_000_000, test_points=100_000, batch=1_000_000, d=8, k=50, optimizer="bayes", seed=0, n_iter=20,
-        init_points=5, verbose=True, x0=1.0, bounds=(0.1, 10.0)):
+        init_points=5, verbose=True, x0=1.0, bounds=(0.1, 10.0), nn_method="exact", nlist=None, nprobe=None):
     clock = Clock()
     gen = torch.Generator(device="cuda").manual_seed(seed)
     rng = np.random.default_rng(2)
@@ -72,7 +75,10 @@ def run(points=1_000_000, test_points=100_000, batch=1_000_000, d=8, k=50, optim
     Xtr32, Xte32, ytr, yte = X32[:points].contiguous(), X32[points:].contiguous(), y[:points].contiguous(), y[points:]
     Xtr, Xte = Xtr32.double(), Xte32.double()
 
-    nbrs = clock("k-NN index (norms)", lambda: NN_Wrapper(Xtr32, k))
+    if nn_method == "exact":
+        nbrs = clock("k-NN index (norms)", lambda: NN_Wrapper(Xtr32, k))
+    else:
+        nbrs = clock(f"k-NN index ({nn_method})", lambda: NN_Wrapper(Xtr32, k, nn_method=nn_method, nlist=nlist, nprobe=nprobe))
     batch = min(batch, points)
     bi = torch.randperm(points, generator=gen, device="cuda")[:batch].sort().values
     ni = clock(f"k-NN, {batch} batch rows x {points} points", lambda: nbrs.get_batch_nns(bi)[0])
@@ -142,6 +148,12 @@ def run(points=1_000_000, test_points=100_000, batch=1_000_000, d=8, k=50, optim
                length_scale=ls.round(3).tolist(), true_length_scale=true_ls.cpu().numpy().round(3).tolist(),
                sigma_sq=float(np.asarray(fitted.scale()).reshape(-1)[0]), rmse=rmse, target_std=float(yte.std()),
                coverage_95=cover, seconds={name: round(s, 4) for name, s in clock.rows})
+    if nn_method != "exact":  # recall of the approximate search against the exact scan, on sampled batch rows
+        rows = torch.randperm(batch, generator=gen, device="cuda")[:4000]
+        want = NN_Wrapper(Xtr32, k).get_batch_nns(bi[rows])[0]
+        hits = (ni[rows][:, :, None] == want[:, None, :]).any(2).double().mean()
+        out.update(nn_method=nn_method, nlist=nbrs.nlist, nprobe=nbrs.nprobe, recall_at_k=float(hits),
+                   recall_queries=int(rows.numel()), short_queries_of_the_test_search=int(nbrs.last_short.sum()))
     if verbose:
         for name, s in clock.rows:
             print(f"{name:55s} {s * 1e3:11.1f} ms")
@@ -156,9 +168,13 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=1_000_000)
     ap.add_argument("--optimizer", default="bayes", choices=["bayes", "bayes-log", "lbfgs", "lbfgs-analytic"])
     ap.add_argument("--n-iter", type=int, default=20)
+    ap.add_argument("--nn-method", default="exact", choices=["exact", "ivf"])
+    ap.add_argument("--nlist", type=int, default=None, help="cells of the ivf index (default: round(sqrt(points)), at most 4096)")
+    ap.add_argument("--nprobe", type=int, default=None, help="cells every query scans (default: min(nlist, 16))")
     ap.add_argument("--out", default="", help="write the result (per-stage seconds included) as JSON to this file")
     a = ap.parse_args()
-    res = run(points=a.points, test_points=a.test_points, batch=a.batch, optimizer=a.optimizer, n_iter=a.n_iter)
+    res = run(points=a.points, test_points=a.test_points, batch=a.batch, optimizer=a.optimizer, n_iter=a.n_iter,
+              nn_method=a.nn_method, nlist=a.nlist, nprobe=a.nprobe)
     if a.out:
         import json
 

@@ -453,6 +453,26 @@ int mgp_knn_scan_bf16x2_d8(const float* train, const void* packed_train, const f
                            const int64_t* self_idx, int64_t m, int k, int64_t start,
                            float* best_d, int32_t* best_i, int32_t* overflow, void* stream);
 
+/* Approximate search over an inverted-cell (IVF) index: every query scans only the rows of its probed cells.  Replaces
+ * the reference's approximate branch (hnswlib behind NN_Wrapper, src/MuyGPyS/neighbors.py:109-127 build, :213-262
+ * query); the exact scans above stay the default.
+ *   table (n, d) fp32, rows stored CELL BY CELL and 16-byte aligned, d % 4 == 0, 4 <= d <= 64, n < 2^31
+ *   cell_start (nlist + 1) int64, non-decreasing: cell j = rows [cell_start[j], cell_start[j + 1]); empty cells are legal
+ *   queries (m, d) fp32, rows 16-byte aligned
+ *   probes (m, nprobe) int32: the cells each query visits, distinct within a row; 1 <= nprobe <= nlist
+ *   self_pos (m) or NULL: the stored position a query must not return
+ *   best_d / best_i (m, k), 1 <= k <= 64, OUT: the k smallest difference-form fp32 squared distances among the rows of
+ *       the probed cells and their stored positions, UNORDERED; rows tied at the k-th distance are taken in order of
+ *       position, so the result depends on the candidate set alone.  Where the probed cells hold fewer than k
+ *       admissible rows the missing entries are best_i = -1, best_d = +inf
+ *   short_flag (m) OUT: 1 for such a query (the caller recomputes it exactly), else 0
+ * MGP_EINVAL for null pointers and sizes out of range, MGP_EUNSUPPORTED for d, k, n or an alignment outside the above:
+ * both before any HIP call.  Nothing synchronises. */
+int mgp_knn_cells_scan(const float* table, int64_t n, int d, const int64_t* cell_start, int nlist,
+                       const float* queries, int64_t m, const int32_t* probes, int nprobe,
+                       const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
+                       void* stream);
+
 /* ---------------------------------------------------------------------------
  * Backward pass of the fused hot path (vector-Jacobian product).  Replaces what
  * torch autograd derives for the reference's torch backend when a deep-kernel

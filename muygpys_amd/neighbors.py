@@ -1,4 +1,4 @@
-"""Exact brute-force k-nearest-neighbour index producer on the GPU.
+"""k-nearest-neighbour index producer on the GPU: exact brute force, or an inverted-cell index.
 
 The step immediately upstream of the hot path: the reference wraps scikit-learn's exact KNN
 (or hnswlib) on the CPU (src/MuyGPyS/neighbors.py:32-262).  ``NN_Wrapper`` here keeps that
@@ -16,11 +16,21 @@ squared-l2 distances)`` with the self-match dropped for batch queries (neighbors
 
 Either way the k winners are then re-measured in difference form and sorted, so the returned
 distances carry no cancellation error and ties resolve by distance then index order of the sort.
+
+``nn_method="ivf"`` is the approximate search (the role of the reference's ``nn_method="hnsw"``,
+neighbors.py:109-127,213-262; a graph walk suits a GPU badly): k-means cells over the table, the table stored
+cell by cell, and every query scans only its ``nprobe`` nearest cells (``mgp_knn_cells_scan``,
+``csrc/mgp_knn_cells.hip``).  fp32 only, ``d <= 64``, ``k <= 64``; the neighbours are exact within the probed
+cells and approximate over the table -- good on data with low-dimensional structure (clusters, manifolds), poor on
+data without (i.i.d. Gaussian at d = 40: recall 0.49 at 8 of 64 cells in a CPU simulation).  A query whose probed
+cells hold fewer than k rows is recomputed exactly on the dense path.
 """
 
 from __future__ import annotations
 
 import os
+
+import math
 
 from typing import Tuple
 
@@ -29,15 +39,44 @@ import torch
 from . import _lib
 
 SCAN_INIT_ROWS = 4096  # rows of the table the k-best lists are initialised from (dense path)
+CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
+CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
+
+
+def default_cells(train_count: int, nlist=None, nprobe=None) -> Tuple[int, int]:
+    """(nlist, nprobe) of the inverted-cell index where the caller names none: round(sqrt(n)) cells, clamped to
+    [1, CELLS_MAX], and min(nlist, 16) probed cells."""
+    if nlist is None:
+        nlist = min(CELLS_MAX, max(1, int(round(math.sqrt(train_count)))))
+    if nprobe is None:
+        nprobe = min(int(nlist), 16)
+    return int(nlist), int(nprobe)
+
+
+def cell_layout(assignment: torch.Tensor, nlist: int):
+    """The storage order of an assignment vector (row -> cell): ``perm`` (stored position -> row; a stable sort by
+    cell, so rows keep their order within a cell), ``inv`` (row -> stored position) and ``cell_start`` (int64,
+    nlist + 1: cell j is stored at [cell_start[j], cell_start[j + 1]); empty cells are legal).  Any device."""
+    assignment = assignment.to(torch.int64)
+    perm = torch.argsort(assignment, stable=True)
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(perm.numel(), device=perm.device)
+    cell_start = torch.zeros(nlist + 1, dtype=torch.int64, device=assignment.device)
+    cell_start[1:] = torch.bincount(assignment, minlength=nlist).cumsum(0)
+    return perm, inv, cell_start
 
 
 class NN_Wrapper:
     def __init__(self, train: torch.Tensor, nn_count: int, nn_method: str = "exact", chunk: int = 4096,
-                 use_scan: bool = True, scan_kind: str = "auto", shuffle: bool = True, **kwargs):
-        if nn_method.lower() != "exact":
+                 use_scan: bool = True, scan_kind: str = "auto", shuffle: bool = True, nlist=None, nprobe=None,
+                 kmeans_iters: int = 10, seed: int = 0, _cells=None, **kwargs):
+        if nn_method.lower() not in ("exact", "ivf"):
             raise NotImplementedError(f"Nearest Neighbor algorithm {nn_method} is not implemented.")
         if not (isinstance(train, torch.Tensor) and train.is_cuda):
             raise TypeError("NN_Wrapper takes a torch tensor on the ROCm device")
+        if nn_method.lower() == "ivf":
+            self._init_cells(train, nn_count, nlist, nprobe, kmeans_iters, seed, chunk, _cells)
+            return
         # the table is kept centred on its mean (queries are shifted alike): distances are unchanged,
         # and every Gram-form quantity below (|q|^2 + |x|^2 - 2 q.x, the split-bf16 margin) is computed
         # at the scale of the data's spread instead of its offset from the origin
@@ -90,6 +129,8 @@ class NN_Wrapper:
     def _get_nns(self, samples, nn_count, exclude=None, centred=False):
         if not centred:
             samples = samples.to(self.train.dtype) - self._mean
+        if self.nn_method == "ivf":
+            return self._cells_nns(samples, nn_count, exclude)
         out = self._scan_nns(samples, nn_count, exclude)
         idx, dist = out if out is not None else self._dense_nns(samples, nn_count, exclude)
         return (idx if self._perm is None else self._perm[idx]), dist
@@ -260,4 +301,160 @@ class NN_Wrapper:
             order = dd.argsort(dim=1, stable=True)
             idx[s:s + chunk] = cand.gather(1, order)
             dist[s:s + chunk] = dd.gather(1, order)
+        return idx, dist
+
+    # ---- the inverted-cell index (nn_method="ivf") -------------------------------------------------------------------
+
+    @classmethod
+    def _from_cells(cls, train, nn_count, centroids, assignment, nprobe=None, **kwargs):
+        """An index over the caller's cells: ``centroids`` (nlist, d) in the table's coordinates and ``assignment``
+        (n) row -> cell, taken as they are (no k-means; a row need not sit in its nearest cell)."""
+        return cls(train, nn_count, nn_method="ivf", nprobe=nprobe, _cells=(centroids, assignment), **kwargs)
+
+    def _pad_features(self, x: torch.Tensor) -> torch.Tensor:
+        """Rows zero-padded to the stored width (the next multiple of 4): distances do not change."""
+        if x.shape[1] == self._width:
+            return x.contiguous()
+        out = torch.zeros((x.shape[0], self._width), device=x.device, dtype=x.dtype)
+        out[:, :x.shape[1]] = x
+        return out
+
+    def _init_cells(self, train, nn_count, nlist, nprobe, kmeans_iters, seed, chunk, cells):
+        table = train[:, None] if train.ndim == 1 else train
+        n, d = table.shape
+        k = int(nn_count)
+        # the cell scan's contract (include/muygpys_hip.h: mgp_knn_cells_scan); no other algorithm steps in
+        if table.dtype != torch.float32:
+            raise ValueError(f"nn_method='ivf' serves float32 tables only (fp32 only), got {table.dtype}")
+        if d > 64:
+            raise ValueError(f"nn_method='ivf' serves at most 64 features (d <= 64), got d = {d}")
+        if not 1 <= k <= 64:
+            raise ValueError(f"nn_method='ivf' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+        if not 1 <= n < 2**31:
+            raise ValueError(f"nn_method='ivf' serves 1 <= n < 2^31 table rows, got n = {n}")
+        self.train_count, self.feature_count = n, d
+        self.nn_count, self.nn_method, self.chunk = k, "ivf", int(chunk)
+        self.use_scan, self.scan_kind, self.last_overflow = False, None, None
+        self.last_short = None  # per query: 1 where the probed cells held fewer than k rows (recomputed exactly)
+        self._width = max(4, -(-d // 4) * 4)
+        self._mean = table.double().mean(0).to(table.dtype)
+        x = self._pad_features(table - self._mean)
+        self._kmeans_init = self._kmeans_sample = None
+        if cells is not None:
+            centroids, assignment = cells
+            nlist = int(centroids.shape[0])
+            centroids = centroids[:, None] if centroids.ndim == 1 else centroids
+            if centroids.shape[1] != d or assignment.shape != (n,):
+                raise ValueError("_from_cells takes centroids (nlist, d) and an assignment (n)")
+            centroids = self._pad_features(centroids.to(device=x.device, dtype=x.dtype) - self._mean)
+            assignment = assignment.to(device=x.device, dtype=torch.int64)
+            if n and not (0 <= int(assignment.min()) and int(assignment.max()) < nlist):
+                raise ValueError("_from_cells: the assignment names a cell outside [0, nlist)")
+        nlist, nprobe = default_cells(n, nlist, nprobe)
+        most = CELLS_MAX if cells is not None else min(n, CELLS_MAX)  # (k-means starts from nlist distinct rows)
+        if not 1 <= nlist <= most:
+            raise ValueError(f"nn_method='ivf' serves 1 <= nlist <= min(n, {CELLS_MAX}), got nlist = {nlist}")
+        if not 1 <= nprobe <= nlist:
+            raise ValueError(f"nn_method='ivf' serves 1 <= nprobe <= nlist, got nprobe = {nprobe}, nlist = {nlist}")
+        self.nlist, self.nprobe = nlist, nprobe
+        if cells is None:
+            centroids = self._kmeans(x, nlist, int(kmeans_iters), int(seed))
+            assignment = self._nearest_cell(x, centroids)
+        self._centroids = centroids.contiguous()
+        self._csq = (self._centroids.double() ** 2).sum(1).to(x.dtype)
+        self._perm, self._inv, self.cell_start = cell_layout(assignment, nlist)
+        self.train = x[self._perm].contiguous()
+        self._sq = (self.train.double() ** 2).sum(1).to(self.train.dtype)  # (the dense path of the short queries)
+
+    @property
+    def centroids(self) -> torch.Tensor:
+        """(nlist, d) cell centres in the table's coordinates."""
+        return self._centroids[:, :self.feature_count] + self._mean
+
+    @staticmethod
+    def _nearest_cell(x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+        """argmin_j |x - c_j|^2 per row, Gram form (|x|^2 does not move the argmin), in row chunks."""
+        csq = (centroids * centroids).sum(1)
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+        rows = max(1, (1 << 26) // centroids.shape[0])
+        for s in range(0, x.shape[0], rows):
+            out[s:s + rows] = torch.addmm(csq[None, :], x[s:s + rows], centroids.T, alpha=-2.0).argmin(1)
+        return out
+
+    def _kmeans(self, x: torch.Tensor, nlist: int, iters: int, seed: int) -> torch.Tensor:
+        """``iters`` Lloyd passes from ``nlist`` distinct rows drawn by a seeded device generator, on a sample of at
+        most CELLS_SAMPLE rows per cell.  An empty cell keeps its centroid.  The sums go through index_put_ with
+        accumulate (a sort by cell, one order of addition) instead of index_add_'s atomics: the same seed gives
+        the same index bit for bit."""
+        n = x.shape[0]
+        gen = torch.Generator(device=x.device).manual_seed(seed)
+        centroids = x[torch.randperm(n, device=x.device, generator=gen)[:nlist]].clone()
+        sample = None
+        if n > CELLS_SAMPLE * nlist:
+            sample = torch.randperm(n, device=x.device, generator=gen)[:CELLS_SAMPLE * nlist]
+        xs = x if sample is None else x[sample]
+        self._kmeans_init, self._kmeans_sample = centroids.clone(), sample
+        for _ in range(iters):
+            cell = self._nearest_cell(xs, centroids)
+            sums = torch.zeros_like(centroids).index_put_((cell,), xs, accumulate=True)
+            count = torch.bincount(cell, minlength=nlist)
+            centroids = torch.where(count[:, None] > 0, sums / count.clamp(min=1)[:, None].to(sums.dtype), centroids)
+        return centroids
+
+    def _probe(self, q: torch.Tensor):
+        """(probes (m, nprobe) int32 unordered, nearest (m) int64) of centred, padded queries."""
+        m = q.shape[0]
+        probes = torch.empty((m, self.nprobe), dtype=torch.int32, device=q.device)
+        nearest = torch.empty(m, dtype=torch.int64, device=q.device)
+        vals = torch.empty((min(m, 65536), self.nprobe), dtype=torch.float32, device=q.device)
+        rows = max(1, min(65536, (1 << 26) // self.nlist))
+        for s in range(0, m, rows):
+            d2 = torch.addmm(self._csq[None, :], q[s:s + rows], self._centroids.T, alpha=-2.0)
+            nearest[s:s + rows] = d2.argmin(1)
+            _lib.check(_lib.load().mgp_topk_rows_f32(_lib.ptr(d2), d2.shape[0], d2.shape[1], d2.stride(0), self.nprobe,
+                                                     _lib.ptr(vals), _lib.ptr(probes[s:s + rows]), _lib.stream_ptr()),
+                       "mgp_topk_rows_f32")
+        return probes, nearest
+
+    def probe(self, queries: torch.Tensor) -> torch.Tensor:
+        """(m, nprobe) int64: the cells the search visits for every query row (unordered)."""
+        queries = queries[:, None] if queries.ndim == 1 else queries
+        q = self._pad_features(queries.to(self.train.dtype) - self._mean)
+        return self._probe(q)[0].to(torch.int64)
+
+    def _cells_nns(self, samples, nn_count, exclude=None):
+        """Probe selection, the cell scan, the finish kernel; queries with too few candidates go dense.  Returns the
+        caller's row numbers."""
+        q = self._pad_features(samples)
+        m, k, dev = q.shape[0], int(nn_count), q.device
+        idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+        dist = torch.empty((m, k), dtype=q.dtype, device=dev)
+        self.last_short = torch.zeros((m,), dtype=torch.int32, device=dev)
+        if m == 0:
+            return idx, dist
+        if not 1 <= k <= 64:
+            raise ValueError(f"nn_method='ivf' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+        probes, nearest = self._probe(q)
+        # queries in order of their nearest cell: consecutive workgroups meet the same cells in L2
+        order = nearest.argsort()
+        qs, ps = q[order].contiguous(), probes[order].contiguous()
+        ex = None if exclude is None else exclude.to(torch.int64)[order].contiguous()
+        best_d = torch.empty((m, k), device=dev, dtype=torch.float32)
+        best_i = torch.empty((m, k), device=dev, dtype=torch.int32)
+        short = torch.empty((m,), device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().mgp_knn_cells_scan(
+            _lib.ptr(self.train), self.train_count, self._width, _lib.ptr(self.cell_start), self.nlist, _lib.ptr(qs), m,
+            _lib.ptr(ps), self.nprobe, _lib.ptr(ex), k, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(short),
+            _lib.stream_ptr()), "mgp_knn_cells_scan")
+        best_i.clamp_(min=0)  # (the -1 of a short list: that query is recomputed below, the finish kernel reads rows)
+        si = torch.empty((m, k), dtype=torch.int64, device=dev)
+        sd = torch.empty((m, k), dtype=q.dtype, device=dev)
+        _lib.check(_lib.load().mgp_knn_finish_f32(_lib.ptr(qs), _lib.ptr(self.train), self._width, _lib.ptr(best_i), m, k,
+                                                  _lib.ptr(self._perm), _lib.ptr(si), _lib.ptr(sd), _lib.stream_ptr()),
+                   "mgp_knn_finish_f32")
+        redo = short.nonzero().reshape(-1)
+        if redo.numel():  # exactly, over the whole table (as the exact scan treats its overflow flags)
+            ri, rd = self._dense_nns(qs[redo], k, None if ex is None else ex[redo])
+            si[redo], sd[redo] = self._perm[ri], rd
+        idx[order], dist[order], self.last_short[order] = si, sd, short
         return idx, dist
