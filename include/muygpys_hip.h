@@ -395,7 +395,13 @@ int mgp_fast_coefficients_f64(const double* feat, int d, const int64_t* nn_idx, 
  *   mgp_knn_finish_f32  candidates (m, k) int32 rows of `train`: squared distances to the queries re-measured in the
  *                       difference form, each query's k candidates put in ascending order (ties: position in the
  *                       list), row numbers through row_map (int64, or NULL) -> out_idx (m, k) int64, out_dist (m, k).
- *                       d % 4 == 0, 16-byte aligned rows, k <= 64; MGP_EUNSUPPORTED otherwise. */
+ *                       d % 4 == 0, 16-byte aligned rows, k <= 64; MGP_EUNSUPPORTED otherwise.
+ * A NaN sorts behind every number, +inf included, whatever its sign bit: mgp_topk_rows_f32 takes one only once the row
+ * has nothing else left, and a candidate at a NaN distance (a NaN feature) comes last in mgp_knn_finish_f32's order
+ * (ties, as ever, by position in the list) -- every output slot is written.
+ * Both: MGP_EINVAL for sizes out of range, then MGP_OK for nothing to do (no rows / no queries; pointers not looked
+ * at), then MGP_EINVAL for a NULL pointer (row_map is optional), then MGP_EUNSUPPORTED (k > cols, cols > 4096; k > 64,
+ * d % 4, alignment): all before any HIP call. */
 int mgp_topk_rows_f32(const float* x, int64_t rows, int cols, int64_t row_stride, int k, float* out_values,
                       int32_t* out_cols, void* stream);
 int mgp_knn_finish_f32(const float* queries, const float* train, int d, const int32_t* candidates, int64_t m, int k,
@@ -409,18 +415,31 @@ int mgp_knn_finish_f32(const float* queries, const float* train, int d, const in
  *
  *   train (n, d), queries (m, d): fp32, rows 16-byte aligned, d % 4 == 0, d <= 64
  *   train_sqn (n rounded up to a multiple of 64; +inf past n), query_sqn (m):
- *       squared norms of the rows; train_sqn + start must be 16-byte aligned
- *       (start % 4 == 0)
+ *       squared norms of the rows
+ *   start: start % 64 == 0 for mgp_knn_scan_f32, which reads train_sqn in whole
+ *       64-row tiles from `start` and keeps rows past n out by their +inf norm
+ *       alone (off that grid the last tile would end past the padded array);
+ *       MGP_EUNSUPPORTED otherwise.  The packed entries below do not read
+ *       train_sqn and mask rows past n by position: they take any start.
  *   self_idx (m) or NULL: training row each query must not return (batch queries
  *       drop the self match, neighbors.py:207-211)
  *   best_d / best_i (m, k), k <= 64: IN: an exact k-best list over training rows
- *       [0, start) (Gram-form squared distances |q|^2+|x|^2-2q.x, any order);
+ *       [0, start) (Gram-form squared distances |q|^2+|x|^2-2q.x, any order),
+ *       every entry FINITE: start >= k, and start > k where self_idx names a row
+ *       below start (the packed kernels encode a k-th best of +inf as a NaN
+ *       threshold slot and then accept nothing);
  *       OUT: the exact k-best over all n rows (unordered; the caller re-measures
  *       the winners in difference form and sorts them).
  *   overflow (m), zero-filled by the caller: set to 1 for a query whose candidate
  *       queue overflowed (adversarial row order); its list is then incomplete
  *       and the caller recomputes that query on its dense path.
  *   Returns MGP_EUNSUPPORTED for shapes outside the above (caller falls back).
+ *   Order of the checks, all before any HIP call: sizes (n, m, start < 0, d, k < 1:
+ *   MGP_EINVAL), nothing to do (m == 0 or start >= n: MGP_OK, pointers not looked
+ *   at), NULL pointers (MGP_EINVAL; self_idx and the stream are optional), then
+ *   MGP_EUNSUPPORTED for k > 64, d outside {4, 8, .. 64}, alignment, n >= 2^31 and
+ *   (this entry) start % 64 != 0.  mgp_knn_scan_bf16x2_d8 refuses d > 8 right
+ *   behind the sizes, in front of the empty batch.
  * ------------------------------------------------------------------------- */
 int mgp_knn_scan_f32(const float* train, const float* train_sqn, int64_t n, int d,
                      const float* queries, const float* query_sqn, const int64_t* self_idx, int64_t m,

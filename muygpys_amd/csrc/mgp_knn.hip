@@ -252,6 +252,9 @@ int launch_knn_scan(const KnnArgs& a, hipStream_t stream) {
   if (((uintptr_t)a.train | (uintptr_t)a.queries | (uintptr_t)(a.train_sqn + a.start)) % 16 != 0)
     return MGP_EUNSUPPORTED;
   if (a.n >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;  // list indices are 32-bit
+  // the kernel reads |x|^2 in whole tiles from `start` and masks rows past n by their +inf norm alone: the padded array
+  // (n rounded up to a multiple of KNN_TN) covers the last tile only when the tiles sit on its grid
+  if (a.start % KNN_TN != 0) return MGP_EUNSUPPORTED;
   const int dp = (a.d + 7) / 8 * 8;
   switch (dp) {
     case 8: return launch_knn_dp<8>(a, stream);

@@ -17,9 +17,12 @@
 
 namespace mgp {
 
-// order-preserving map of a float to an unsigned integer (NaN sorts last)
+// order-preserving map of a float to an unsigned integer (NaN sorts last, whatever its sign bit: every NaN takes the
+// one key KEY_NAN above +inf's; KEY_PAD above that is left to entries that do not exist)
+constexpr unsigned KEY_NAN = 0xFFFFFFFEu, KEY_PAD = 0xFFFFFFFFu;
 __device__ __forceinline__ unsigned float_key(float x) {
   const unsigned u = __float_as_uint(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return KEY_NAN;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ int wave_sum_int(int v) {
@@ -43,7 +46,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* x, int64_t 
 #pragma unroll
   for (int v = 0; v < VPL; ++v) {
     const int c = v * 64 + lane;
-    key[v] = c < cols ? float_key(xr[c]) : 0xFFFFFFFFu;
+    key[v] = c < cols ? float_key(xr[c]) : KEY_PAD;
   }
   // the largest T with count(key < T) < k, i.e. T = the k-th smallest key (bit by bit from the top)
   unsigned T = 0;
@@ -123,12 +126,17 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(const float* queries, c
     }
     dd = (s0 + s1) + (s2 + s3);
   }
-  // rank = entries of the group that come before this one (smaller distance, or equal distance at an earlier position)
+  // rank = entries of the group that come before this one (smaller distance, or equal distance at an earlier position),
+  // on the keys: a total order, so the ranks of a group are a permutation whatever the distances are (a NaN distance --
+  // a NaN feature -- compares false both ways as a float, and two entries would share a rank and leave a slot unwritten).
+  // NaNs rank behind every number, lanes without a candidate behind those.  dd is a sum of squares from +0, never -0:
+  // equal keys are equal floats, and numbers rank as they did as floats
+  const unsigned key = on ? float_key(dd) : KEY_PAD;
   int rank = 0;
 #pragma unroll 8
   for (int t = 0; t < L; ++t) {
-    const float o = __shfl(dd, g * L + t, 64);
-    rank += (o < dd || (o == dd && t < j)) ? 1 : 0;
+    const unsigned o = __shfl(key, g * L + t, 64);
+    rank += (o < key || (o == key && t < j)) ? 1 : 0;
   }
   if (on) {
     out_idx[q * k + rank] = perm ? perm[ci] : (int64_t)ci;

@@ -278,3 +278,78 @@ def test_knn_finish_kernel_orders_and_maps(m, k, d):
             p0 = (idx == want[:, :1]).float().argmax(dim=1)
             p1 = (idx == want[:, 1:2]).float().argmax(dim=1)
             assert bool((p0 < p1).all())
+
+
+def test_knn_finish_kernel_ranks_nan_distances_last():
+    """Two of every query's candidates are table rows with a NaN feature: their distances are NaN, which compares false
+    both ways.  The ranks are taken on a total order (NaN behind every number, ties by list position), so they stay a
+    permutation: no output slot keeps its pre-filled sentinel, out_idx is the mapped candidates, the finite distances
+    ascend and the NaN entries close the list in list order."""
+    from muygpys_amd import _lib
+
+    m, k, d, n = 65, 17, 12, 3000
+    g = torch.Generator(device="cuda").manual_seed(65 + 17)
+    train = torch.randn((n, d), device="cuda", generator=g)
+    q = torch.randn((m, d), device="cuda", generator=g)
+    cand = torch.stack([torch.randperm(n - 2, device="cuda", generator=g)[:k] for _ in range(m)]).to(torch.int32)
+    train[n - 2, 5] = float("nan")
+    train[n - 1, 0] = -torch.tensor(float("nan"), device="cuda")
+    rows = torch.arange(m, device="cuda")
+    first, second = rows % k, (rows % k + 1 + rows % (k - 1)) % k  # two different list positions per query
+    assert bool((first != second).all())
+    late, early = torch.maximum(first, second), torch.minimum(first, second)
+    cand[rows, late], cand[rows, early] = n - 2, n - 1  # (row n - 1 at the EARLIER position: it must come out first)
+    perm = torch.randperm(n, device="cuda", generator=g)
+    for row_map in (None, perm):
+        idx = torch.full((m, k), -7, device="cuda", dtype=torch.int64)
+        dist = torch.full((m, k), -7.0, device="cuda")
+        rc = _lib.load().mgp_knn_finish_f32(_lib.ptr(q), _lib.ptr(train), d, _lib.ptr(cand), m, k, _lib.ptr(row_map),
+                                            _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr())
+        assert rc == 0
+        torch.cuda.synchronize()
+        assert not bool((idx == -7).any()) and not bool((dist == -7.0).any()), "an output slot was left unwritten"
+        want = cand.long() if row_map is None else perm[cand.long()]
+        assert torch.equal(idx.sort(dim=1).values, want.sort(dim=1).values)
+        assert bool(torch.isfinite(dist[:, :k - 2]).all()) and bool(torch.isnan(dist[:, k - 2:]).all())
+        assert bool((dist[:, 1:k - 2] >= dist[:, :k - 3]).all())
+        nan_rows = torch.tensor([n - 1, n - 2], device="cuda")
+        assert torch.equal(idx[:, k - 2:], (nan_rows if row_map is None else perm[nan_rows]).expand(m, 2))
+        dd = ((q[:, None, :] - train[cand.long()]) ** 2).sum(-1)
+        torch.testing.assert_close(dist[:, :k - 2], dd.sort(dim=1).values[:, :k - 2], rtol=2e-6, atol=1e-6)
+
+
+@pytest.mark.parametrize("extra", [1, 4])
+def test_topk_rows_kernel_takes_nan_last(extra):
+    """A row of 100 finite values, +inf, +NaN and -NaN (sign bit set through an integer view): the k smallest are the
+    finite values, then +inf, then NaNs of either sign -- at k one more than the finite count, and three more."""
+    from muygpys_amd import _lib
+
+    rows, cols = 5, 104
+    g = torch.Generator(device="cuda").manual_seed(104)
+    x = torch.randn((rows, cols), device="cuda", generator=g)
+    special = torch.stack([torch.randperm(cols, device="cuda", generator=g)[:4] for _ in range(rows)])
+    r = torch.arange(rows, device="cuda")
+    x[r, special[:, 0]] = float("inf")
+    x[r, special[:, 1]] = float("nan")
+    x[r, special[:, 2]] = float("nan")
+    x[r, special[:, 3]] = float("nan")
+    bits = x.view(torch.int32)
+    bits[r, special[:, 1]] = 0x7FC00000            # +NaN
+    bits[r, special[:, 2]] = -0x400000             # 0xFFC00000: -NaN
+    bits[r, special[:, 3]] = -1                    # 0xFFFFFFFF: -NaN, every payload bit set
+    assert int(torch.isnan(x).sum()) == 3 * rows and int(torch.isfinite(x).sum()) == 100 * rows
+    k = 100 + extra
+    vals = torch.full((rows, k), -7.0, device="cuda")
+    idx = torch.full((rows, k), -7, device="cuda", dtype=torch.int32)
+    rc = _lib.load().mgp_topk_rows_f32(_lib.ptr(x), rows, cols, x.stride(0), k, _lib.ptr(vals), _lib.ptr(idx), _lib.stream_ptr())
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert int(idx.min()) >= 0 and int(idx.max()) < cols
+    assert all(len(set(row.tolist())) == k for row in idx.cpu())
+    assert torch.equal(x.gather(1, idx.long()).view(torch.int32), vals.view(torch.int32))
+    finite = torch.isfinite(vals).sum(1)
+    assert bool((finite == 100).all()), "every finite value comes before +inf and the NaNs"
+    if extra == 1:
+        assert bool((torch.isinf(vals).sum(1) == 1).all()), "+inf comes before any NaN"
+    else:
+        assert bool((torch.isinf(vals).sum(1) == 1).all()) and bool((torch.isnan(vals).sum(1) == 3).all())
