@@ -616,6 +616,60 @@ int mgp_solve_f64(const double* Kin, const double* Kcross, const double* Y, int6
                   double* mean, double* var, double* ykinvy, double* coeffs, int* info, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Any nn_count: local systems beyond LDS.  The reference accepts any nn_count
+ * (_src/gp/muygps/numpy.py:17-67 hand whatever they are given to linalg.solve); mgp_posterior_* and
+ * mgp_solve_* stop at mgp_max_nn_count, where one system no longer fits the CU's LDS.  The entries below
+ * serve EVERY k >= 1 with k + 1 + response_count <= 1024: the augmented system lives in a slab of a
+ * caller-provided device workspace (one slab per workgroup of the persistent grid) and is factorised by a
+ * blocked Cholesky whose panel update runs on the matrix pipe in the tables' own precision (exact fp32 / fp64
+ * matrix instructions).  Outputs and failure semantics as mgp_posterior_* / mgp_solve_*.
+ *
+ *   workspace: device memory, 16-byte aligned, not shared with a call in flight on another stream; its contents
+ *       on entry do not matter and nothing is kept in it between calls.  The grid is workspace_bytes / slab
+ *       workgroups, capped by the resident capacity and by b: any workspace of at least one slab gives the same
+ *       bits (what a neighbourhood returns does not depend on its place in the batch, the batch, the grid or the
+ *       workspace), a smaller one is only slower.
+ *   mgp_large_max_nn_count: the largest k served for a response count, 1023 - response_count (the same for both
+ *       float widths); -1 for an elem_size that is not 4 or 8.
+ *   mgp_large_workspace_bytes: the recommended size for a batch of b -- one slab per workgroup of the grid the
+ *       launcher would choose, at most 512 MiB, at least one slab (b = 0); 0 for arguments the kernel does not
+ *       serve.  A slab is what one system occupies: the smallest workspace a call accepts is
+ *       mgp_large_workspace_bytes(elem_size, k, R, 1).
+ *   Order of the checks, all before any HIP call: sizes (MGP_EINVAL), the empty batch (MGP_OK, nothing else
+ *   looked at), pointers, ids and the workspace (NULL, misaligned, less than one slab: MGP_EINVAL), then
+ *   k + 1 + R > 1024 or MGP_KERNEL_MATERN_GEN: MGP_EUNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+int mgp_large_max_nn_count(int elem_size, int response_count);
+int64_t mgp_large_workspace_bytes(int elem_size, int k, int response_count, int64_t b);
+/* mgp_posterior_* (T1-T4, D1/D2, K1/K2, N1/N2, S1 _muygps_posterior_mean, S2 _muygps_diagonal_variance, S3 the
+ * summand of _analytic_scale_optim_unnormalized: see there) for any such k.  targets_batch != 0: `targets` is the
+ * gathered (b, k, R) tensor, as for mgp_posterior_gathered_*.  Separate query table, NULL batch_idx, any d >= 1,
+ * the five closed-form kernels, both metrics, scalar or per-feature length scale, the three noise modes. */
+int mgp_posterior_large_f32(const float* feat_q, const float* feat_nn, int d,
+                            const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                            const float* targets, int R, int targets_batch,
+                            int noise_mode, double noise_scalar, const float* noise_dev,
+                            int kernel_id, int metric_id, const float* length_scale, int ls_count,
+                            float* mean, float* var, float* ykinvy, int* info,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_posterior_large_f64(const double* feat_q, const double* feat_nn, int d,
+                            const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                            const double* targets, int R, int targets_batch,
+                            int noise_mode, double noise_scalar, const double* noise_dev,
+                            int kernel_id, int metric_id, const double* length_scale, int ls_count,
+                            double* mean, double* var, double* ykinvy, int* info,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+/* mgp_solve_* (S1 _muygps_posterior_mean, _src/gp/muygps/numpy.py:17-41; S2 _muygps_diagonal_variance, :44-67; S3
+ * _src/optimize/scale/numpy.py:9-15; coeffs = _muygps_fast_posterior_mean_precompute, numpy.py:88-95) for any such
+ * k, the back-substitution of the coefficient output included. */
+int mgp_solve_large_f32(const float* Kin, const float* Kcross, const float* Y, int64_t b, int k, int R, double kout,
+                        float* mean, float* var, float* ykinvy, float* coeffs, int* info,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_solve_large_f64(const double* Kin, const double* Kcross, const double* Y, int64_t b, int k, int R, double kout,
+                        double* mean, double* var, double* ykinvy, double* coeffs, int* info,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Fused fast posterior mean (prediction from precomputed coefficients).  Replaces
  *   _crosswise_tensor + metric + kernel + _muygps_fast_posterior_mean
  *   (_src/gp/tensors/numpy.py:47-58,89-94, _src/gp/kernels/numpy.py:12-31,

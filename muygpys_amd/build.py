@@ -52,6 +52,8 @@ PER_FILE_FLAGS = {
     "mgp_classify.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the cell scan of the approximate search: the query row and two steps of table rows sit in registers)
     "mgp_knn_cells.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the blocked factorisation beyond LDS: a 32 x 32 diagonal block and a panel row sit in registers)
+    "mgp_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 

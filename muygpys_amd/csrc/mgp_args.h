@@ -154,6 +154,13 @@ int launch_fused_rhs_mf(const FusedArgs&, hipStream_t);  // fp32 prediction vari
 template <typename T> int launch_fused_wide(const FusedArgs&, hipStream_t);
 int launch_fused_wide64(const FusedArgs&, hipStream_t);  // fp64, two lanes per row
 int max_nn_count(int elem_size, int R);
+// mgp_large.hip: systems beyond LDS (k + 1 + R <= kLargeMaxRows): blocked Cholesky on a slab of a caller-provided
+// global-memory workspace, one slab per workgroup of the persistent grid (which the workspace size bounds)
+static const int kLargeMaxRows = 1024;
+template <typename T> int launch_fused_large(const FusedArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
+template <typename T> int launch_solve_large(const SolveArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
+int64_t large_slab_bytes(int elem_size, int k, int R);
+int64_t large_workspace_bytes(int elem_size, int k, int R, int64_t b);
 
 // mgp_shear.hip: the multi-output solve and the shear model
 struct SolveMultiArgs {

@@ -54,7 +54,8 @@ enum { PATH_AUTO = 0, PATH_GENERIC = 1, PATH_RHS = 2 };
 enum {
   NEED_RESPONSES = 1,  // `tg` is read: the (n, R) table, or the gathered (b, k, R) tensor next to prepared tables
   NEED_OUTPUTS = 2,    // `mean` and `var` are written
-  KERNEL_IS_GEN = 4    // the entry serves MGP_KERNEL_MATERN_GEN alone: `kernel_id` is not looked at
+  KERNEL_IS_GEN = 4,   // the entry serves MGP_KERNEL_MATERN_GEN alone: `kernel_id` is not looked at
+  KERNEL_MAY_BE_GEN = 8  // MGP_KERNEL_MATERN_GEN is a known id the entry then refuses itself (MGP_EUNSUPPORTED)
 };
 enum { ARGS_READY = 1 };  // fused_args: valid arguments and a batch to serve; any other value is the entry's status
 
@@ -80,8 +81,9 @@ int fused_args(FusedArgs& a, int needs, const T* fq, const T* fn, int d, const i
   }
   if (!ni || !ls) return MGP_EINVAL;
   if ((needs & NEED_OUTPUTS) && (!mean || !var)) return MGP_EINVAL;
+  const bool known_gen = (needs & KERNEL_MAY_BE_GEN) && kernel_id == MGP_KERNEL_MATERN_GEN;
   if (needs & KERNEL_IS_GEN) kernel_id = MGP_KERNEL_MATERN_GEN;
-  else if (!valid_kernel(kernel_id)) return MGP_EINVAL;
+  else if (!valid_kernel(kernel_id) && !known_gen) return MGP_EINVAL;
   if (!valid_metric(metric_id)) return MGP_EINVAL;
   if (noise_mode < MGP_NOISE_SCALAR || noise_mode > MGP_NOISE_BATCH) return MGP_EINVAL;
   if (noise_mode != MGP_NOISE_SCALAR && !nd) return MGP_EINVAL;
@@ -214,6 +216,41 @@ int solve(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, double
   if (rc != MGP_EUNSUPPORTED) return rc;
   return launch_solve_generic<T>(a, static_cast<hipStream_t>(stream));
 }
+// ---- systems beyond LDS (mgp_large.hip) ------------------------------------------------------------------------------
+// the workspace of an mgp_*_large_* call: 16-byte aligned, at least one slab (checked with the pointers, before a
+// shape beyond the kernel is refused)
+static bool valid_workspace(const void* ws, int64_t bytes, int elem_size, int k, int R) {
+  return ws && reinterpret_cast<uintptr_t>(ws) % 16 == 0 && bytes >= large_slab_bytes(elem_size, k, R);
+}
+
+template <typename T>
+int posterior_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
+                    int R, int targets_batch, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id,
+                    const T* ls, int ls_count, T* mean, T* var, T* yk, int* info, void* ws, int64_t ws_bytes,
+                    void* stream) {
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_MAY_BE_GEN, fq, fn, d, bi, ni, b, k, tg, R,
+                                  noise_mode, eps, nd, kernel_id, metric_id, ls, ls_count, mean, var, yk, info, nullptr, 0,
+                                  nullptr, 0, targets_batch != 0);
+  if (ready != ARGS_READY) return ready;
+  if (!valid_workspace(ws, ws_bytes, sizeof(T), k, R)) return MGP_EINVAL;
+  return launch_fused_large<T>(a, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses rows > 1024 and the general nu)
+}
+
+template <typename T>
+int solve_large(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, double kout, T* mean, T* var, T* yk,
+                T* coeffs, int* info, void* ws, int64_t ws_bytes, void* stream) {
+  if (b < 0 || k < 1 || R < 0) return MGP_EINVAL;
+  if (b == 0) return MGP_OK;
+  if (!Kin) return MGP_EINVAL;
+  if (R > 0 && !Y) return MGP_EINVAL;
+  if ((mean || var) && !Kc) return MGP_EINVAL;
+  if ((mean || yk || coeffs) && R == 0) return MGP_EINVAL;
+  if (!valid_workspace(ws, ws_bytes, sizeof(T), k, R)) return MGP_EINVAL;
+  SolveArgs a{Kin, Kc, Y, mean, var, yk, coeffs, info, b, kout, k, R};
+  return launch_solve_large<T>(a, ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
 // behind the fused launch of a LOOCV evaluation: nothing when a wave kernel walked the tree itself; the walk by kernels
 // over the SAME leaves when it was launched without (three_launch); over the canonical leaves behind another family
 template <typename T>
@@ -456,6 +493,30 @@ int mgp_posterior_f64(const double* fq, const double* fn, int d, const int64_t* 
   }
 MGP_DEFINE_PATHS(f32, float)
 MGP_DEFINE_PATHS(f64, double)
+
+int mgp_large_max_nn_count(int elem_size, int R) {
+  if ((elem_size != 4 && elem_size != 8) || R < 0) return MGP_EINVAL;
+  return kLargeMaxRows - 1 - R > 0 ? kLargeMaxRows - 1 - R : 0;
+}
+int64_t mgp_large_workspace_bytes(int elem_size, int k, int R, int64_t b) {
+  if ((elem_size != 4 && elem_size != 8) || k < 1 || R < 0 || b < 0 || (int64_t)k + 1 + R > kLargeMaxRows) return 0;
+  return large_workspace_bytes(elem_size, k, R, b);
+}
+#define MGP_DEFINE_LARGE(SUF, T)                                                                                    \
+  int mgp_posterior_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b,    \
+                                int k, const T* tg, int R, int targets_batch, int nm, double eps, const T* nd,       \
+                                int kid, int mid, const T* ls, int lsc, T* mean, T* var, T* yk, int* info,           \
+                                void* workspace, int64_t workspace_bytes, void* st) {                                \
+    return posterior_large<T>(fq, fn, d, bi, ni, b, k, tg, R, targets_batch, nm, eps, nd, kid, mid, ls, lsc, mean,   \
+                              var, yk, info, workspace, workspace_bytes, st);                                        \
+  }                                                                                                                  \
+  int mgp_solve_large_##SUF(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, double kout, T* mean,    \
+                            T* var, T* yk, T* coeffs, int* info, void* workspace, int64_t workspace_bytes,           \
+                            void* st) {                                                                              \
+    return solve_large<T>(Kin, Kc, Y, b, k, R, kout, mean, var, yk, coeffs, info, workspace, workspace_bytes, st);   \
+  }
+MGP_DEFINE_LARGE(f32, float)
+MGP_DEFINE_LARGE(f64, double)
 
 int mgp_topk_rows_f32(const float* x, int64_t rows, int cols, int64_t row_stride, int k, float* out_values, int32_t* out_cols,
                       void* st) {

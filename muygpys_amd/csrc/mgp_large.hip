@@ -1,0 +1,568 @@
+// Local systems beyond LDS (k + 1 + R <= kLargeMaxRows = 1024): the work of mgp_generic.hip -- gather -> distances ->
+// kernel -> nugget -> augmented factorisation -> mean / var / yKinvy, and the same factorisation on a materialised
+// Kin -- with the system in GLOBAL memory: one slab of a caller-provided workspace per workgroup of the persistent
+// grid.  No workgroup waits on another; what a neighbourhood returns depends on nothing but its own inputs.
+//
+// Slab: the lower trapezoid of the augmented system of mgp_lds_factor.h, row by row.  Row i < k holds its columns up
+// to the end of its 32-column block (32 (i / 32 + 1) elements), the 1 + R trailing rows hold KP = 32 ceil(k / 32)
+// each; every row starts on a 128-byte boundary.  What lies right of the diagonal inside a diagonal block is never
+// initialised and never reaches a result (see factor_augmented_slab).
+//
+// Factorisation: left-looking by panels of LNB = 32 columns.  Per panel (first column j0):
+//   1. update   S[i][j0 + n] -= sum_{c < j0} S[i][c] S[j0 + n][c]  for every row i >= j0, the trailing rows included
+//               (the forward substitution of z and the responses "for free") -- a tiled GEMM on the matrix pipe,
+//               one tile of rows per wave, accumulators in registers over the whole c loop, operands streamed from
+//               the slab (L2): v_mfma_f32_32x32x2_f32 (bit for bit an fmaf chain) / v_mfma_f64_16x16x4_f64.
+//               This is the k^3 / 3 of the factorisation.
+//   2. the 32 x 32 diagonal block is factorised by EVERY wave, redundantly, in registers (lane = row, the column
+//      broadcasts are v_readlane: no LDS round trip and no barrier inside the block), as factor_augmented_rows does
+//      with its 4 x 4 block; the first wave's copy goes back to the slab and into LDS
+//   3. every row below the block forward-substitutes its 32 panel entries, one row per thread, the block's rows
+//      coming out of LDS as 16-byte broadcasts
+// Four workgroup barriers per panel.  The diagonal holds the INVERSE pivots afterwards (nothing reads the diagonal of
+// L but the back-substitution of the coefficient output, which wants the inverse).
+#include "mgp_args.h"
+#include "mgp_lds_factor.h"
+
+namespace mgp {
+
+constexpr int LNB = 32;  // panel width = side of a diagonal block
+
+__host__ __device__ inline int large_kp(int k) { return (k + LNB - 1) / LNB * LNB; }
+// element offset of row i of the slab of a system with k elimination columns
+__host__ __device__ inline int large_row_off(int i, int k) {
+  const int t = i < k ? i : k;
+  const int q = t / LNB, r = t - q * LNB;
+  const int tri = LNB * LNB * (q * (q + 1) / 2) + r * LNB * (q + 1);
+  return i < k ? tri : tri + (i - k) * large_kp(k);
+}
+__host__ __device__ inline int large_slab_elems(int k, int R) { return large_row_off(k + 1 + R, k); }
+// row stride of the LDS copy of a diagonal block: 16-byte aligned rows
+template <typename T>
+__host__ __device__ constexpr int large_lp() { return LNB + 16 / (int)sizeof(T); }
+
+template <typename T>
+struct SlabRows {
+  T* S;
+  int k;
+  __device__ __forceinline__ T* operator()(int i) const { return S + large_row_off(i, k); }
+};
+
+// the value lane `src` (a compile-time constant after unrolling) holds, as a wave-uniform scalar
+__device__ __forceinline__ float lane_value(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+__device__ __forceinline__ double lane_value(double v, int src) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src),
+                          __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+
+// step 1 of a panel, fp32: 32-row tiles on v_mfma_f32_32x32x2_f32.  Lane l feeds row (l & 31) of either operand; the
+// instruction contracts over two columns per issue and the order of the columns is free as long as both operands
+// agree, so lane half h = l >> 5 takes columns [c0 + 8 h, c0 + 8 h + 8) of a 16-column step as two 16-byte loads and
+// issue e of the step contracts columns {c0 + e, c0 + 8 + e}: a fixed order, the same for every tile.
+__device__ __forceinline__ void panel_update(SlabRows<float> row, int j0, int rows, int tid, int NT) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef float f16 __attribute__((ext_vector_type(16)));
+  const int lane = tid & 63, wave = tid >> 6, nw = NT >> 6;
+  const int m = lane & 31, h = lane >> 5;
+  const int ntiles = (rows - j0 + 31) / 32;
+  const float* pb = row(min(j0 + m, rows - 1)) + h * 8;  // (rows past the system: any valid row, results dropped)
+  for (int t = wave; t < ntiles; t += nw) {
+    const int i0 = j0 + 32 * t;
+    const float* pa = row(min(i0 + m, rows - 1)) + h * 8;
+    f16 acc = f16(0);
+    f4 a0 = *reinterpret_cast<const f4*>(pa), a1 = *reinterpret_cast<const f4*>(pa + 4);
+    f4 b0 = *reinterpret_cast<const f4*>(pb), b1 = *reinterpret_cast<const f4*>(pb + 4);
+    for (int c0 = 0; c0 < j0; c0 += 16) {
+      const f4 x0 = a0, x1 = a1, y0 = b0, y1 = b1;
+      if (c0 + 16 < j0) {  // the next step's operands are in flight while this one is on the matrix pipe
+        a0 = *reinterpret_cast<const f4*>(pa + c0 + 16), a1 = *reinterpret_cast<const f4*>(pa + c0 + 20);
+        b0 = *reinterpret_cast<const f4*>(pb + c0 + 16), b1 = *reinterpret_cast<const f4*>(pb + c0 + 20);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[e], y0[e], acc, 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[e], y1[e], acc, 0, 0, 0);
+    }
+    // accumulator g of lane l: row 8 (g / 4) + 4 (l >> 5) + g % 4, column l & 31
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+      const int i = i0 + 8 * (g / 4) + 4 * h + (g & 3);
+      if (i < rows) row(i)[j0 + m] -= acc[g];
+    }
+  }
+}
+
+// ... fp64: 16-row tiles against the panel's two 16-column halves on v_mfma_f64_16x16x4_f64 (four columns per issue:
+// lane quarter h = l >> 4 takes columns [c0 + 4 h, c0 + 4 h + 4) of a 16-column step)
+__device__ __forceinline__ void panel_update(SlabRows<double> row, int j0, int rows, int tid, int NT) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  const int lane = tid & 63, wave = tid >> 6, nw = NT >> 6;
+  const int m = lane & 15, h = lane >> 4;
+  const int ntiles = (rows - j0 + 15) / 16;
+  const double* pb = row(min(j0 + m, rows - 1)) + h * 4;
+  const double* pc = row(min(j0 + 16 + m, rows - 1)) + h * 4;
+  for (int t = wave; t < ntiles; t += nw) {
+    const int i0 = j0 + 16 * t;
+    const double* pa = row(min(i0 + m, rows - 1)) + h * 4;
+    d4 acc0 = d4(0), acc1 = d4(0);
+    d2 a0 = *reinterpret_cast<const d2*>(pa), a1 = *reinterpret_cast<const d2*>(pa + 2);
+    d2 b0 = *reinterpret_cast<const d2*>(pb), b1 = *reinterpret_cast<const d2*>(pb + 2);
+    d2 c0v = *reinterpret_cast<const d2*>(pc), c1v = *reinterpret_cast<const d2*>(pc + 2);
+    for (int c0 = 0; c0 < j0; c0 += 16) {
+      const d2 x0 = a0, x1 = a1, y0 = b0, y1 = b1, z0 = c0v, z1 = c1v;
+      if (c0 + 16 < j0) {
+        a0 = *reinterpret_cast<const d2*>(pa + c0 + 16), a1 = *reinterpret_cast<const d2*>(pa + c0 + 18);
+        b0 = *reinterpret_cast<const d2*>(pb + c0 + 16), b1 = *reinterpret_cast<const d2*>(pb + c0 + 18);
+        c0v = *reinterpret_cast<const d2*>(pc + c0 + 16), c1v = *reinterpret_cast<const d2*>(pc + c0 + 18);
+      }
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[e], y0[e], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x0[e], z0[e], acc1, 0, 0, 0);
+      }
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[e], y1[e], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x1[e], z1[e], acc1, 0, 0, 0);
+      }
+    }
+    // accumulator g of lane l: row (l >> 4) + 4 g, column l & 15
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int i = i0 + h + 4 * g;
+      if (i < rows) {
+        double* p = row(i) + j0 + m;
+        p[0] -= acc0[g];
+        p[16] -= acc1[g];
+      }
+    }
+  }
+}
+
+#ifdef MGP_LARGE_VALU_UPDATE
+// A/B copy of step 1 on the VALU (tools/mkvariant.sh valu mgp_large.hip -DMGP_LARGE_VALU_UPDATE=1):
+// the same operands from the same place -- rows of L as 16-byte loads from the slab, nothing staged in LDS -- with a
+// register tile of 8 rows x 4 panel columns per thread, the contraction in ascending column order.
+template <typename T>
+__device__ __forceinline__ void panel_update_valu(SlabRows<T> row, int j0, int rows, int tid, int NT) {
+  using V = typename lds_vec<T>::type;
+  constexpr int E = 16 / (int)sizeof(T), TM = 8, TN = 4;
+  const int ntasks = (rows - j0 + TM - 1) / TM * (LNB / TN);
+  for (int t = tid; t < ntasks; t += NT) {
+    const int n0 = j0 + t % (LNB / TN) * TN, i0 = j0 + t / (LNB / TN) * TM;
+    const T* pa[TM];
+    const T* pb[TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) pa[i] = row(min(i0 + i, rows - 1));
+#pragma unroll
+    for (int n = 0; n < TN; ++n) pb[n] = row(min(n0 + n, rows - 1));
+    T acc[TM][TN] = {};
+    for (int c = 0; c < j0; c += E) {
+      V av[TM], bv[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) av[i] = *reinterpret_cast<const V*>(pa[i] + c);
+#pragma unroll
+      for (int n = 0; n < TN; ++n) bv[n] = *reinterpret_cast<const V*>(pb[n] + c);
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int n = 0; n < TN; ++n) acc[i][n] += av[i][e] * bv[n][e];
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+      if (i0 + i < rows) {
+        T* p = row(i0 + i) + n0;
+#pragma unroll
+        for (int n = 0; n < TN; ++n) p[n] -= acc[i][n];
+      }
+  }
+}
+#endif
+
+// All NT threads of the workgroup call this on a filled slab (every write to it behind a barrier).  Lb: LNB * large_lp
+// elements of LDS, 16-byte aligned.  Returns, to every thread, whether a non-positive / NaN pivot was met.  On return
+// (behind a barrier) rows 0 .. k-1 hold L with the inverse pivots on the diagonal, row k holds z = L^-1 c and row
+// k+1+r holds L^-1 y_r.
+//
+// Entries right of the diagonal inside a diagonal block (never initialised) are carried along by step 1 and by the
+// register factorisation, and stay where they are: lane r's entry (r, c) with c > r only ever feeds entries (r, m)
+// with m > c of the same lane, no broadcast reads them (the broadcast of column c takes lanes >= c), and step 3 reads
+// row c of the block up to its diagonal.
+template <typename T>
+__device__ __forceinline__ bool factor_augmented_slab(SlabRows<T> row, int k, int rows, T* Lb, int tid, int NT) {
+  using V = typename lds_vec<T>::type;
+  constexpr int E = 16 / (int)sizeof(T);
+  constexpr int LP = large_lp<T>();
+  const int lane = tid & 63, r = lane & 31;
+  bool bad = false;
+  for (int j0 = 0; j0 < k; j0 += LNB) {
+    const int nb = min(LNB, k - j0);
+    if (j0 > 0) {
+#ifdef MGP_LARGE_VALU_UPDATE
+      panel_update_valu<T>(row, j0, rows, tid, NT);
+#else
+      panel_update(row, j0, rows, tid, NT);
+#endif
+      __syncthreads();
+    }
+    // step 2: row r of the diagonal block in lane r's registers; the block is padded to 32 x 32 with the identity
+    // (a last panel of nb < 32 columns: the padding's pivots are 1 and it leaves the rest alone)
+    {
+      T D[LNB];
+      T dinv = T(0);  // lane r: the inverse pivot of column r
+      // (the lane index behind an empty asm, once per use: the 32 lane masks r == c are then made where they are
+      // used instead of being hoisted out of the panel loop, kept in 64 scalar registers and spilled)
+      int r1 = r, r2 = r, r3 = r;
+      asm volatile("" : "+v"(r1));
+      asm volatile("" : "+v"(r2));
+      asm volatile("" : "+v"(r3));
+      const T* src = row(min(j0 + r, rows - 1)) + j0;
+#pragma unroll
+      for (int c = 0; c < LNB; c += E) {
+        const V v = *reinterpret_cast<const V*>(src + c);
+#pragma unroll
+        for (int e = 0; e < E; ++e) D[c + e] = (r < nb && c + e < nb) ? v[e] : (r1 == c + e ? T(1) : T(0));
+      }
+      __syncthreads();  // every wave holds the block: its rows (and the LDS copy of the last one) may now be overwritten
+#pragma unroll
+      for (int c = 0; c < LNB; ++c) {
+        const T p = lane_value(D[c], c);
+        bad = bad || !(p > T(0));
+        const T iv = num<T>::rsqrt(p);
+        const T v = D[c] * iv;  // lane r > c: L[r][c]
+        D[c] = v;
+        dinv = r2 == c ? iv : dinv;
+        // (eight broadcasts at a time: left alone, the scheduler lines up the whole block's and spills scalars)
+#pragma unroll
+        for (int m = c + 1; m < LNB; ++m) {
+          D[m] -= v * lane_value(v, m);
+          if ((m & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (tid < LNB) {  // the first wave's copy goes to the slab and, for step 3, to LDS
+        T* dst = row(min(j0 + r, rows - 1)) + j0;
+#pragma unroll
+        for (int c = 0; c < LNB; c += E) {
+          V v;
+#pragma unroll
+          for (int e = 0; e < E; ++e) v[e] = r3 == c + e ? dinv : D[c + e];  // (the diagonal keeps the inverse pivot)
+          *reinterpret_cast<V*>(Lb + r * LP + c) = v;
+          if (r < nb) *reinterpret_cast<V*>(dst + c) = v;
+        }
+      }
+    }
+    __syncthreads();
+    // step 3: y = a L^-T for the 32 panel entries a of every row below the block, one row per thread; row c of the
+    // block comes out of LDS as 16-byte broadcasts
+    for (int i = j0 + nb + tid; i < rows; i += NT) {
+      T* p = row(i) + j0;
+      T y[LNB];
+#pragma unroll
+      for (int c = 0; c < LNB; c += E) {
+        const V v = *reinterpret_cast<const V*>(p + c);
+#pragma unroll
+        for (int e = 0; e < E; ++e) y[c + e] = v[e];
+      }
+#pragma unroll
+      for (int c = 0; c < LNB; ++c) {
+        T v = y[c];
+#pragma unroll
+        for (int m0 = 0; m0 <= c; m0 += E) {
+          const V l = *reinterpret_cast<const V*>(Lb + c * LP + m0);
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            if (m0 + e < c) v -= y[m0 + e] * l[e];
+            if (m0 + e == c) v *= l[e];  // (the inverse pivot: the last entry the row contributes)
+          }
+        }
+        y[c] = v;
+        __builtin_amdgcn_sched_barrier(0);  // (one row of the block in flight, not all 32)
+      }
+#pragma unroll
+      for (int c = 0; c < LNB; c += E) {
+        V v;
+#pragma unroll
+        for (int e = 0; e < E; ++e) v[e] = y[c + e];
+        *reinterpret_cast<V*>(p + c) = v;  // (columns past k of a last panel: inside the row, never read as data)
+      }
+    }
+    __syncthreads();
+  }
+  return bad;
+}
+
+// mean (R), var, ykinvy (R) from the factored slab: the inner products of emit_outputs_lds, same order
+template <typename T>
+__device__ __forceinline__ void emit_outputs_slab(SlabRows<T> row, int k, int R, T kout, bool bad, bool has_cross, T* mean, T* var,
+                                         T* ykinvy, int tid) {
+  if (tid >= MGP_WAVE) return;
+  const T* z = row(k);
+  for (int o = 0; o < 1 + 2 * R; ++o) {
+    const T* x = z;
+    const T* y = z;
+    T* dst = nullptr;
+    if (o == 0) {
+      if (var != nullptr && has_cross) dst = var;
+    } else if (o <= R) {
+      y = row(k + o);
+      if (mean != nullptr && has_cross) dst = mean + (o - 1);
+    } else {
+      x = y = row(k + 1 + (o - R - 1));
+      if (ykinvy != nullptr) dst = ykinvy + (o - R - 1);
+    }
+    if (dst == nullptr) continue;  // uniform
+    T s = T(0);
+    for (int m = tid; m < k; m += MGP_WAVE) s += x[m] * y[m];
+    s = wave_sum(s);
+    if (tid == 0) *dst = bad ? num<T>::nan() : (o == 0 ? kout - s : s);
+  }
+}
+
+// dynamic LDS carve (every array 16-byte aligned): [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T]
+template <typename T>
+__global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* workspace, int slab_elems) {
+  using V = typename lds_vec<T>::type;
+  constexpr int E = 16 / (int)sizeof(T);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int k_ = a.k, d = a.d, R_ = a.R, dc = a.dc;
+  const int XP = dc + E;  // feature-tile row stride: 16-byte aligned rows, odd number of 16-byte slots (dc % (2 E) == 0)
+  T* Lb = reinterpret_cast<T*>(smem);
+  int64_t* idx = reinterpret_cast<int64_t*>(Lb + LNB * large_lp<T>());
+  T* X = reinterpret_cast<T*>(idx + ((k_ + 2) & ~1));
+  T* il = X + (k_ + 1) * XP;
+
+  const T* feat_q = static_cast<const T*>(a.feat_q);
+  const T* feat_nn = static_cast<const T*>(a.feat_nn);
+  const T* targets = static_cast<const T*>(a.targets);
+  const T* noise_dev = static_cast<const T*>(a.noise_dev);
+  const T* ls = static_cast<const T*>(a.length_scale);
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const bool aniso = a.ls_count > 1;
+  const bool vec_ok = d % E == 0 && dc % E == 0 && ((uintptr_t)feat_q | (uintptr_t)feat_nn) % 16 == 0;
+
+  T post_scale = T(1);
+  if (!aniso) {
+    const T l = ls[0];
+    post_scale = a.metric_id == MGP_METRIC_L2 ? T(1) / l : T(1) / (l * l);
+  }
+
+  for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
+    __syncthreads();  // previous neighbourhood fully consumed
+    int k = k_, R = R_;
+    asm volatile("" : "+s"(k), "+s"(R));
+    const int rows = k + 1 + R;
+    const int npairs = (k + 1) * k / 2;
+    const SlabRows<T> row{workspace + (int64_t)blockIdx.x * slab_elems, k};
+    for (int r = tid; r <= k; r += NT)
+      idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
+    __syncthreads();
+
+    // squared distances of the (k+1)-point set, one chunk of dc features at a time: the chunk's rows are staged in
+    // LDS, the partial sums live in the slab
+    for (int d0 = 0; d0 < d; d0 += dc) {
+      const int w = min(dc, d - d0);
+      const int wp = (w + E - 1) / E * E;  // zero-padded to whole 16-byte pieces
+      gather_tile_lds<T>(X, XP, feat_q, feat_nn, idx, k, d, d0, w, wp, vec_ok, tid, NT);
+      if (aniso)
+        for (int c = tid; c < wp; c += NT) il[c] = c < w ? T(1) / ls[d0 + c] : T(0);
+      __syncthreads();
+      for (int p = tid; p < npairs; p += NT) {
+        // p -> (row a_, col c_) of the strict lower triangle of the (k+1)-point set
+        int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
+        while (a_ * (a_ - 1) / 2 > p) --a_;
+        while ((a_ + 1) * a_ / 2 <= p) ++a_;
+        const int c_ = p - a_ * (a_ - 1) / 2;
+        const T* xa = X + a_ * XP;
+        const T* xc = X + c_ * XP;
+        T acc = T(0);
+        if (aniso) {
+#pragma unroll 2
+          for (int j = 0; j < wp; j += E) {
+            const V df = (*reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j)) *
+                         *reinterpret_cast<const V*>(il + j);
+            acc += vec_dot(df, df);
+          }
+        } else {
+#pragma unroll 2
+          for (int j = 0; j < wp; j += E) {
+            const V df = *reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j);
+            acc += vec_dot(df, df);
+          }
+        }
+        T* dst = row(a_) + c_;
+        if (d0 > 0) acc += *dst;
+        // the last chunk turns the distance into the covariance
+        *dst = d0 + dc >= d ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
+      }
+      __syncthreads();
+    }
+    // nugget on the diagonal, responses into the tail rows
+    for (int r = tid; r < k; r += NT) {
+      T eps;
+      if (a.noise_mode == MGP_NOISE_SCALAR) eps = (T)a.noise_scalar;
+      else if (a.noise_mode == MGP_NOISE_TABLE) eps = noise_dev[idx[r]];
+      else eps = noise_dev[nb * k + r];
+      row(r)[r] = T(1) + eps;  // kernel(0) == 1 for every kernel on the path
+    }
+    for (int t = tid; t < k * R; t += NT) {
+      const int c = t / R, r = t - c * R;
+      row(k + 1 + r)[c] = targets[(a.targets_batch ? nb * k + c : idx[c]) * (int64_t)R + r];
+    }
+    __syncthreads();
+    const bool bad = factor_augmented_slab<T>(row, k, rows, Lb, tid, NT);
+    T* mean = static_cast<T*>(a.mean);
+    T* var = static_cast<T*>(a.var);
+    T* yk = static_cast<T*>(a.ykinvy);
+    emit_outputs_slab<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
+                         yk ? yk + nb * R : nullptr, tid);
+    if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(512) solve_large_kernel(SolveArgs a, T* workspace, int slab_elems) {
+  const int k_ = a.k, R_ = a.R;
+  const T* Kin = static_cast<const T*>(a.Kin);
+  const T* Kcross = static_cast<const T*>(a.Kcross);
+  const T* Y = static_cast<const T*>(a.Y);
+  const int tid = threadIdx.x, NT = blockDim.x;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  T* Lb = reinterpret_cast<T*>(smem);  // the LDS copy of the diagonal block: all the LDS this front end needs
+
+  for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
+    __syncthreads();
+    int k = k_, R = R_;
+    asm volatile("" : "+s"(k), "+s"(R));
+    const int rows = k + 1 + R;
+    const SlabRows<T> row{workspace + (int64_t)blockIdx.x * slab_elems, k};
+    const T* Kb = Kin + nb * (int64_t)k * k;
+    for (int t = tid; t < k * k; t += NT) {
+      const int i = t / k, j = t - i * k;
+      if (j <= i) row(i)[j] = Kb[t];  // lower triangle, as LAPACK 'L' would read it
+    }
+    for (int c = tid; c < k; c += NT) row(k)[c] = Kcross ? Kcross[nb * k + c] : T(0);
+    for (int t = tid; t < k * R; t += NT) {
+      const int c = t / R, r = t - c * R;
+      row(k + 1 + r)[c] = Y[(nb * k + c) * (int64_t)R + r];
+    }
+    __syncthreads();
+    const bool bad = factor_augmented_slab<T>(row, k, rows, Lb, tid, NT);
+    T* mean = static_cast<T*>(a.mean);
+    T* var = static_cast<T*>(a.var);
+    T* yk = static_cast<T*>(a.ykinvy);
+    emit_outputs_slab<T>(row, k, R, (T)a.kout, bad, Kcross != nullptr, mean ? mean + nb * R : nullptr,
+                         var ? var + nb : nullptr, yk ? yk + nb * R : nullptr, tid);
+    if (a.coeffs) {
+      // back-substitution L^T x = L^-1 y_r of all R responses at once, in place in rows k+1+r, column by column
+      // from the last: x[j] = w[j] / L[j][j], then w[m] -= L[j][m] x[j] for every m < j -- row j of L, read
+      // contiguously by consecutive threads
+      T* co = static_cast<T*>(a.coeffs) + nb * (int64_t)k * R;
+      for (int j = k - 1; j >= 0; --j) {
+        __syncthreads();  // the outputs' reads / the updates of column j + 1 are done
+        const T* Lj = row(j);
+        const T ivj = Lj[j];
+        for (int r = tid; r < R; r += NT) co[j * (int64_t)R + r] = bad ? num<T>::nan() : row(k + 1 + r)[j] * ivj;
+        for (int m = tid; m < j; m += NT) {
+          const T l = Lj[m] * ivj;
+          for (int r = 0; r < R; ++r) {
+            T* w = row(k + 1 + r);
+            w[m] -= l * w[j];
+          }
+        }
+      }
+    }
+    if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
+  }
+}
+
+static const size_t kMaxLds = 160 * 1024;
+static const int64_t kMaxWorkspace = 512LL << 20;
+static const int kCuCount = 256, kMaxPerCu = 1;  // (104 - 205 registers at 512 threads: one workgroup per CU)
+
+static int block_threads(int rows) { return rows <= 128 ? 256 : 512; }
+
+template <typename T>
+static size_t fused_lds_bytes(int k, int dc) {
+  size_t n = (size_t)((k + 2) & ~1) * sizeof(int64_t);
+  n += ((size_t)LNB * large_lp<T>() + (size_t)(k + 1) * (dc + 16 / sizeof(T)) + dc) * sizeof(T);
+  return (n + 15) & ~(size_t)15;
+}
+
+int64_t large_slab_bytes(int elem_size, int k, int R) {
+  // large_slab_elems in 64 bits (the C entries size-check a workspace before they refuse a k beyond the limit);
+  // whole 256-byte lines: the slabs of neighbouring workgroups share none
+  const int64_t q = k / LNB, r = k % LNB, kp = (q + (r ? 1 : 0)) * LNB;
+  const int64_t elems = LNB * LNB * (q * (q + 1) / 2) + r * LNB * (q + 1) + (1 + (int64_t)R) * kp;
+  if (elems > (INT64_MAX - 255) / elem_size) return INT64_MAX;  // (k or R near INT_MAX: no workspace holds a slab)
+  return (elems * elem_size + 255) / 256 * 256;
+}
+
+int64_t large_workspace_bytes(int elem_size, int k, int R, int64_t b) {
+  const int64_t slab = large_slab_bytes(elem_size, k, R);
+  int64_t n = b < 1 ? 1 : b;
+  if (n > kCuCount * kMaxPerCu) n = kCuCount * kMaxPerCu;
+  return n * slab > kMaxWorkspace ? kMaxWorkspace : n * slab;
+}
+
+// persistent grid: one workgroup per slab of the workspace, at most the resident capacity, at most b
+static int grid_for(int64_t b, int64_t slabs, size_t lds) {
+  const size_t granules = (lds + 1279) / 1280;  // (LDS is handed out in 1280-byte granules: mgp_generic.hip)
+  int per_cu = (int)(kMaxLds / ((granules ? granules : 1) * 1280));
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > kMaxPerCu) per_cu = kMaxPerCu;
+  int64_t g = (int64_t)kCuCount * per_cu;
+  if (g > slabs) g = slabs;
+  return (int)(b < g ? b : g);
+}
+
+template <typename T>
+int launch_fused_large(const FusedArgs& in, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  FusedArgs a = in;
+  const int64_t rows = (int64_t)a.k + 1 + a.R;  // (64 bits: k or R near INT_MAX must not wrap past the limit)
+  if (rows > kLargeMaxRows || a.kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
+  const int64_t slab = large_slab_bytes(sizeof(T), a.k, a.R);
+  // feature chunk: a multiple of 8, as wide as fits the CU's LDS (one workgroup per CU: nothing to share it with; every
+  // further chunk is one more pass over the slab's triangle: at k = 1000, d = 40 five chunks of 8 cost as much as
+  // the factorisation), at least 8
+  int dc = a.d < 64 ? (a.d + 7) / 8 * 8 : 64;
+  while (dc > 8 && fused_lds_bytes<T>(a.k, dc) > kMaxLds) dc -= 8;
+  const size_t lds = fused_lds_bytes<T>(a.k, dc);
+  if (lds > kMaxLds) return MGP_EUNSUPPORTED;
+  a.dc = dc;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_large_kernel<T>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return -(1000 + (int)e);
+  }
+  const int grid = grid_for(a.b, workspace_bytes / slab, lds);
+  hipLaunchKernelGGL(fused_large_kernel<T>, dim3(grid), dim3(block_threads((int)rows)), lds, stream, a,
+                     static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)));
+  MGP_HIP_CHECK_LAUNCH();
+  note_launch("mgp::fused_large_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return MGP_OK;
+}
+
+template <typename T>
+int launch_solve_large(const SolveArgs& a, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  const int64_t rows = (int64_t)a.k + 1 + a.R;
+  if (rows > kLargeMaxRows) return MGP_EUNSUPPORTED;
+  const int64_t slab = large_slab_bytes(sizeof(T), a.k, a.R);
+  const size_t lds = (size_t)LNB * large_lp<T>() * sizeof(T);
+  const int grid = grid_for(a.b, workspace_bytes / slab, lds);
+  hipLaunchKernelGGL(solve_large_kernel<T>, dim3(grid), dim3(block_threads((int)rows)), lds, stream, a,
+                     static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)));
+  MGP_HIP_CHECK_LAUNCH();
+  return MGP_OK;
+}
+
+template int launch_fused_large<float>(const FusedArgs&, void*, int64_t, hipStream_t);
+template int launch_fused_large<double>(const FusedArgs&, void*, int64_t, hipStream_t);
+template int launch_solve_large<float>(const SolveArgs&, void*, int64_t, hipStream_t);
+template int launch_solve_large<double>(const SolveArgs&, void*, int64_t, hipStream_t);
+
+}  // namespace mgp

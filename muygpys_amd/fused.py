@@ -328,6 +328,32 @@ def _posterior_call(spec: KernelSpec, inp: _Inputs, gathered: bool, path: str, p
     return _lib.fn(base, inp.fn.dtype), args
 
 
+def _large_workspace(dtype, k: int, R: int, b: int, device) -> torch.Tensor:
+    """The workspace of one ``mgp_*_large_*`` call (``mgp_large_workspace_bytes``: one slab per workgroup of the grid, at
+    most 512 MiB), from torch's stream-ordered allocator.  ``ValueError`` for a system beyond the kernel."""
+    lib = _lib.load()
+    es = 4 if dtype == torch.float32 else 8
+    size = int(lib.mgp_large_workspace_bytes(es, k, R, b))
+    if size == 0:
+        raise ValueError(
+            f"nn_count = {k} with {R} response column(s) exceeds mgp_large_max_nn_count = {lib.mgp_large_max_nn_count(es, R)} "
+            "(a local system holds at most 1024 rows: nn_count + 1 + response_count)"
+        )
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
+def _posterior_large(spec: KernelSpec, inp: _Inputs, gathered: bool, outs: tuple) -> int:
+    """One ``mgp_posterior_large_*`` launch on the plain tables (systems beyond LDS, csrc/mgp_large.hip); ``outs`` as
+    for :func:`_posterior_call`.  Returns the status."""
+    P = _lib.ptr
+    ws = _large_workspace(inp.fn.dtype, inp.k, inp.R, inp.b, inp.fn.device)
+    return _lib.fn("posterior_large", inp.fn.dtype)(
+        P(inp.fq), P(inp.fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, int(gathered),
+        inp.mode, inp.eps, P(inp.nz), spec.kernel_id(), spec.metric_id(), P(inp.ls), inp.ls.numel(),
+        *outs[:4], P(ws), ws.numel(), outs[4],
+    )
+
+
 def posterior_mean_var(
     spec: KernelSpec,
     test_features: torch.Tensor,
@@ -351,7 +377,10 @@ def posterior_mean_var(
     (:44-67 with Kout = 1); ``ykinvy (b, R)`` holds ``y_r^T K^-1 y_r`` per neighbourhood
     (the summand of _analytic_scale_optim_unnormalized, scale/numpy.py:9-15).
 
-    ``path``: "auto" (dispatcher), or one kernel family by name -- "generic" / "rhs" (parity tests).
+    ``path``: "auto" (dispatcher), or one kernel family by name -- "generic" / "rhs" / "large" (parity tests).
+    "auto" hands a closed-form kernel whose system no longer fits LDS (``nn_count`` beyond ``mgp_max_nn_count``) to the
+    blocked factorisation in global memory (``mgp_posterior_large_*``), up to ``nn_count + 1 + R = 1024`` rows;
+    beyond that: ``ValueError``.
     ``packed``: "auto" reads the tables through prepared copies (:class:`PackedTable`, cached per
     tensor) when the shape allows it and the batch touches the table often enough to pay for the
     one-time pack; True forces, False disables.
@@ -364,15 +393,15 @@ def posterior_mean_var(
     mean = out_mean if out_mean is not None else torch.empty((b, R), device=fn.device, dtype=dtype)
     var = out_var if out_var is not None else torch.empty((b,), device=fn.device, dtype=dtype)
     yk = torch.empty((b, R), device=fn.device, dtype=dtype) if want_ykinvy else None
-    if path not in ("auto", "generic", "rhs"):
+    if path not in ("auto", "generic", "rhs", "large"):
         raise ValueError(f"unknown kernel path {path!r}")
     gen = spec.kernel == "matern_gen"  # one entry point for every table form (mgp_posterior_gen_*)
     if gen and path != "auto":
         raise ValueError("the general-smoothness Matern goes through the dispatcher (path='auto')")
     if gen and (spec.smoothness is None or not float(spec.smoothness) > 0.0):
         raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
-    if gathered and path != "auto":
-        raise ValueError("gathered responses go through the dispatcher (path='auto')")
+    if gathered and path not in ("auto", "large"):
+        raise ValueError("gathered responses go through the dispatcher (path='auto') or path='large'")
     # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
     rows = fn.shape[0] + (0 if test_features is train_features else inp.fq.shape[0])
     use_packed = path == "auto" and _use_packed(packed, inp, train_features, train_targets, rows, gathered)
@@ -385,9 +414,14 @@ def posterior_mean_var(
         rc = call(*args)
     # MGP_EUNSUPPORTED on the prepared tables (or not tried): the plain tables -- for the closed-form kernels only
     # (matern_gen does NOT retry on the plain tables: the caller gets FusedUnsupported)
-    if rc == _lib.EUNSUPPORTED and not (gen and use_packed):
+    if path == "large":
+        rc = _posterior_large(spec, inp, gathered, outs)
+    elif rc == _lib.EUNSUPPORTED and not (gen and use_packed):
         call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
         rc = call(*args)
+        # a closed-form kernel whose system does not fit LDS: the blocked factorisation in global memory
+        if rc == _lib.EUNSUPPORTED and path == "auto" and not gen:
+            rc = _posterior_large(spec, inp, gathered, outs)
     if gen and rc == _lib.EUNSUPPORTED:
         raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={inp.k}, R={R}, d={inp.d}")
     _lib.check(rc, "mgp_posterior_gen" if gen else "mgp_posterior")
@@ -446,6 +480,13 @@ def loocv_partials(
     if rc == _lib.EUNSUPPORTED:
         call, args = _loocv_call(None, inp, spec, inp.ls, **rest)
         rc = call(*args)
+        if rc == _lib.EUNSUPPORTED and spec.kernel != "matern_gen":
+            # a system beyond LDS: the blocked factorisation in global memory, then the same reduction tree over its
+            # outputs on the canonical leaves (what mgp_loocv_* does behind every kernel family but the wave kernels)
+            outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
+            _lib.check(_posterior_large(spec, inp, False, outs), "mgp_posterior_large")
+            partials = loocv_tree_sums(mean, var, yk, inp.tg, inp.bi, huber_delta)
+            rc = 0
     if rc != 0:
         _lib.loocv_scratch_reset()
     _lib.check(rc, "mgp_loocv")
