@@ -446,6 +446,31 @@ int mgp_knn_scan_f32(const float* train, const float* train_sqn, int64_t n, int 
                      int k, int64_t start, float* best_d, int32_t* best_i, int32_t* overflow,
                      void* stream);
 
+/* The same exact search and its finish step for k-best lists of up to 1 024 entries (csrc/mgp_knn_wide.hip): the
+ * reference's NN_Wrapper takes any nn_count (src/MuyGPyS/neighbors.py:89-107, 129-211), and the posterior entries
+ * above serve nn_count + 1 + response_count <= 1024.
+ *   mgp_knn_wide_max_nn_count   the largest k the two entries below take: 1024.
+ *   mgp_knn_scan_wide           the parameters and the best_d / best_i contract of mgp_knn_scan_f32 (Gram-form fp32
+ *       distances, lists unordered, start % 64 == 0), for 1 <= k <= 1024.  The list stays in global memory; the wave
+ *       that merges a query's survivors holds its distances as ceil(k / 64) entries per lane.  A query's queue has one
+ *       slot per column of the 64-row tile and is emptied after every tile, so it cannot overflow: `overflow` is
+ *       accepted (and must not be NULL) but never written, whatever the order of the table.  The IN lists must be
+ *       whole: start >= k, and start >= k + 1 where self_idx is given; MGP_EUNSUPPORTED otherwise.
+ *   mgp_knn_finish_wide         the parameters and the result of mgp_knn_finish_f32 (difference-form fp32 distances in
+ *       ascending order, ties by position in the list, NaN last, every output slot written; row_map optional), for
+ *       1 <= k <= 1024: one workgroup per query, ranked in LDS, no (m, k, d) temporary.  m < 2^31.
+ * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), nothing to do (m == 0 or start >= n: MGP_OK,
+ * pointers not looked at), NULL pointers (MGP_EINVAL; self_idx, row_map and the stream are optional), then
+ * MGP_EUNSUPPORTED for k > 1024, d outside {4, 8, .. 64} (the finish step: d % 4 != 0), alignment, n >= 2^31,
+ * start % 64 != 0 and k + 1 > start with self_idx (k > start without). */
+int mgp_knn_wide_max_nn_count(void);
+int mgp_knn_scan_wide(const float* train, const float* train_sqn, int64_t n, int d,
+                      const float* queries, const float* query_sqn, const int64_t* self_idx, int64_t m,
+                      int k, int64_t start, float* best_d, int32_t* best_i, int32_t* overflow,
+                      void* stream);
+int mgp_knn_finish_wide(const float* queries, const float* train, int d, const int32_t* candidates, int64_t m, int k,
+                        const int64_t* row_map, int64_t* out_idx, float* out_dist, void* stream);
+
 /* Same search with a split-bf16 pre-filter on the matrix cores (3 bf16 MFMA chains
  * hi.hi + hi.lo + lo.hi, error < 2^-14 |q||x|, folded into the threshold) and an
  * exact fp32 difference-form re-measurement of every survivor: exact results,

@@ -29,6 +29,8 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-
 # the k-NN scans test the MFMA results right away: keep them in VGPRs (no v_accvgpr_read per value)
 PER_FILE_FLAGS = {
     "mgp_knn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    # (the wide-list scan too; its registers, LDS and scratch go into the report: DESIGN sec. 4.6)
+    "mgp_knn_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
     # the 64-step elimination must unroll completely (the fp64 / 16-response body exceeds the default
     # pragma-unroll budget, and a rolled loop indexes the 128-register row at run time = in scratch)
     "mgp_fused_rhs.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],

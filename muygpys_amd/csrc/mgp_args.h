@@ -127,6 +127,12 @@ int launch_knn_scan_packed(const KnnPackedArgs&, hipStream_t);
 int launch_topk_rows(const float* x, int64_t rows, int cols, int64_t stride, int k, float* out_v, int* out_i, hipStream_t);
 int launch_knn_finish(const float* queries, const float* train, int d, const int* cand, int64_t m, int k, const int64_t* perm,
                       int64_t* out_idx, float* out_dist, hipStream_t);
+// the same pair for k-best lists of up to KNN_WIDE_MAX_K entries (mgp_knn_wide.hip): the list in global memory, held by
+// the draining wave as up to 16 entries per lane; the finish step one workgroup per query, ranked in LDS
+constexpr int KNN_WIDE_MAX_K = 1024;
+int launch_knn_scan_wide(const KnnArgs&, hipStream_t);
+int launch_knn_finish_wide(const float* queries, const float* train, int d, const int* cand, int64_t m, int k,
+                           const int64_t* perm, int64_t* out_idx, float* out_dist, hipStream_t);
 
 template <typename T> int launch_fused_generic(const FusedArgs&, hipStream_t);
 template <typename T> int launch_solve_generic(const SolveArgs&, hipStream_t);

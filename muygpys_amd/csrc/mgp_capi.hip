@@ -543,6 +543,24 @@ int mgp_knn_scan_f32(const float* train, const float* train_sqn, int64_t n, int 
   return launch_knn_scan(a, S_(st));
 }
 
+int mgp_knn_wide_max_nn_count(void) { return KNN_WIDE_MAX_K; }
+int mgp_knn_scan_wide(const float* train, const float* train_sqn, int64_t n, int d, const float* queries,
+                      const float* query_sqn, const int64_t* self_idx, int64_t m, int k, int64_t start, float* best_d,
+                      int32_t* best_i, int32_t* overflow, void* st) {
+  if (n < 0 || m < 0 || d < 1 || k < 1 || start < 0) return MGP_EINVAL;
+  if (m == 0 || start >= n) return MGP_OK;
+  if (!train || !train_sqn || !queries || !query_sqn || !best_d || !best_i || !overflow) return MGP_EINVAL;
+  KnnArgs a{train, train_sqn, queries, query_sqn, self_idx, best_d, best_i, overflow, n, m, start, d, k};
+  return launch_knn_scan_wide(a, S_(st));
+}
+int mgp_knn_finish_wide(const float* queries, const float* train, int d, const int32_t* candidates, int64_t m, int k,
+                        const int64_t* row_map, int64_t* out_idx, float* out_dist, void* st) {
+  if (m < 0 || d < 1 || k < 1) return MGP_EINVAL;
+  if (m == 0) return MGP_OK;
+  if (!queries || !train || !candidates || !out_idx || !out_dist) return MGP_EINVAL;
+  return launch_knn_finish_wide(queries, train, d, candidates, m, k, row_map, out_idx, out_dist, S_(st));
+}
+
 int mgp_knn_scan_bf16x3(const float* train, const void* packed_train, const float* train_sqn, int64_t n, int d,
                         const float* queries, const void* packed_queries, const float* query_sqn,
                         const int64_t* self_idx, int64_t m, int k, int64_t start, float* best_d, int32_t* best_i,

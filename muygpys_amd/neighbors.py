@@ -11,8 +11,15 @@ squared-l2 distances)`` with the self-match dropped for batch queries (neighbors
   per pair against the query's running k-th best, rare survivors merged into per-query k-best
   lists -- after the lists have been initialised from the first rows of the table on the dense
   path.  Nothing of size (queries x train) is ever materialised.
+* the same tables, ``64 < k <= 1024``: the wide-list scan ``mgp_knn_scan_wide`` and its finish step
+  ``mgp_knn_finish_wide`` (``csrc/mgp_knn_wide.hip``) -- the same arithmetic, the lists in global memory and held by
+  the draining wave as ceil(k / 64) entries per lane, a queue slot per column of the tile, so no queue can overflow;
+  the lists start from ``SCAN_INIT_ROWS`` head rows.  3 to 24 times the dense path at 1 M x 1 M
+  (``profiles/knn_wide_bench.json``); ``MUYGPYS_HIP_KNN_WIDE=0`` keeps these searches on the dense path.
 * anything else: the dense path, in row chunks, ``|q|^2 + |x|^2 - 2 q.x`` through
   ``torch.matmul`` (rocBLAS) followed by ``topk``.
+
+``last_route`` ("scan" | "wide" | "dense" | "ivf") names what served the most recent search.
 
 Either way the k winners are then re-measured in difference form and sorted, so the returned
 distances carry no cancellation error and ties resolve by distance then index order of the sort.
@@ -39,6 +46,7 @@ import torch
 from . import _lib
 
 SCAN_INIT_ROWS = 4096  # rows of the table the k-best lists are initialised from (dense path)
+WIDE_MAX_K = 1024      # mgp_knn_wide_max_nn_count(): the longest list of the wide scan (64 < k: csrc/mgp_knn_wide.hip)
 CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
 CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
 
@@ -109,6 +117,7 @@ class NN_Wrapper:
         self.scan_kind = "bf16x3" if scan_kind == "auto" else scan_kind
         self._packed_train, self._packed_qmax, self._packed_layout = None, None, None
         self.last_overflow = None  # per-query overflow flags of the most recent scan (device int32)
+        self.last_route = None     # what served the most recent search: "scan" | "wide" | "dense" | "ivf"
         self._sq = (self.train.double() ** 2).sum(1).to(self.train.dtype)
         # the scan kernel reads |x|^2 in whole 64-row tiles: +inf past the end (never a neighbour)
         pad = (-self.train_count) % 64
@@ -130,18 +139,26 @@ class NN_Wrapper:
         if not centred:
             samples = samples.to(self.train.dtype) - self._mean
         if self.nn_method == "ivf":
+            self.last_route = "ivf"
             return self._cells_nns(samples, nn_count, exclude)
-        out = self._scan_nns(samples, nn_count, exclude)
-        idx, dist = out if out is not None else self._dense_nns(samples, nn_count, exclude)
+        out = self._scan_nns(samples, nn_count, exclude)  # (sets last_route where it serves the call)
+        if out is None:
+            self.last_route = "dense"
+            out = self._dense_nns(samples, nn_count, exclude)
+        idx, dist = out
         return (idx if self._perm is None else self._perm[idx]), dist
 
     def _scan_supported(self, samples, nn_count) -> bool:
         d = self.feature_count
         return (
             self.use_scan and self.train.dtype == torch.float32 and samples.dtype == torch.float32
-            and d % 4 == 0 and 4 <= d <= 64 and 1 <= nn_count <= 64
+            and d % 4 == 0 and 4 <= d <= 64 and 1 <= nn_count <= (WIDE_MAX_K if self._wide_enabled() else 64)
             and self.train_count > 2 * SCAN_INIT_ROWS and self.train_count < 2**31
         )
+
+    @staticmethod
+    def _wide_enabled() -> bool:
+        return os.environ.get("MUYGPYS_HIP_KNN_WIDE", "1") != "0"  # (0: nn_count > 64 stays on the dense path, for A/B)
 
     @staticmethod
     def _split_bf16(v: torch.Tensor):
@@ -177,8 +194,9 @@ class NN_Wrapper:
             packed[:, 16:18] = 1.0
         return packed
 
-    def _scan_nns(self, samples, nn_count, exclude=None):
-        """Fused MFMA scan (see the module docstring); None when the shape is not covered."""
+    def _scan_nns(self, samples, nn_count, exclude=None, force_wide=False):
+        """Fused MFMA scan (see the module docstring); None when the shape is not covered.  ``force_wide``: the wide
+        pair for k <= 64 too (tools/knnwidebench.py's sanity line; no search is routed that way)."""
         if not self._scan_supported(samples, nn_count):
             return None
         q = samples.contiguous()
@@ -190,8 +208,11 @@ class NN_Wrapper:
         # earliest, so the first tile -- 128 rows for the short packed rows, 64 otherwise -- should bring two at most
         # (P(Poisson(2) >= 17) ~ 5e-11): tile * k / 2 rows, in steps of 1 024, SCAN_INIT_ROWS at most.  torch's topk
         # over these rows was a fifth of the search's time at 1 M x 1 M, k = 30 (round 5)
+        # Lists of more than 64 entries (mgp_knn_scan_wide): its queues cannot overflow whatever the head rows are, and
+        # the more rows the lists start from the fewer candidates the scan merges: SCAN_INIT_ROWS for every k
+        wide = k > 64 or force_wide
         tile_rows = 128 if (self.scan_kind == "bf16x3" and self.feature_count + 2 <= 16) else 64
-        init_rows = min(SCAN_INIT_ROWS, max(1024, -(-(tile_rows * k // 2) // 1024) * 1024))
+        init_rows = SCAN_INIT_ROWS if wide else min(SCAN_INIT_ROWS, max(1024, -(-(tile_rows * k // 2) // 1024) * 1024))
         head = self.train[:init_rows]
         best_d = torch.empty((m, k), device=q.device, dtype=torch.float32)
         best_i = torch.empty((m, k), device=q.device, dtype=torch.int32)
@@ -218,6 +239,8 @@ class NN_Wrapper:
                 _lib.check(rc_sel, "mgp_topk_rows_f32")
         overflow = torch.zeros((m,), device=q.device, dtype=torch.int32)
         ex64 = None if exclude is None else exclude.to(torch.int64).contiguous()
+        if wide:
+            return self._wide_nns(q, qn, ex64, exclude, init_rows, best_d, best_i, overflow)
         if self.scan_kind == "bf16x3":
             # the split-bf16 kernel keeps exact (difference-form) distances in the lists
             for s in range(0, m, 65536):
@@ -277,6 +300,45 @@ class NN_Wrapper:
         if redo.numel():  # queues overflowed (adversarial row order): those queries go dense
             ri, rd = self._dense_nns(q[redo], k, None if exclude is None else exclude[redo])
             idx[redo], dist[redo] = ri, rd
+        self.last_route = "scan"
+        return idx, dist
+
+    FINISH_BUDGET_BYTES = 1 << 30  # the (rows, k, d) temporary of the torch finish step, where the kernel declines
+
+    def _wide_nns(self, q, qn, ex64, exclude, init_rows, best_d, best_i, overflow):
+        """The scan and the finish step for 64 < k <= WIDE_MAX_K (csrc/mgp_knn_wide.hip) on lists that hold the exact
+        k-best of the first ``init_rows`` rows (Gram form); None where the scan declines (alignment)."""
+        (m, k), d = best_d.shape, self.feature_count
+        rc = _lib.load().mgp_knn_scan_wide(
+            _lib.ptr(self.train), _lib.ptr(self._sq_scan), self.train_count, d, _lib.ptr(q), _lib.ptr(qn),
+            _lib.ptr(ex64), m, k, init_rows, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
+        )
+        if rc == _lib.EUNSUPPORTED:
+            return None
+        _lib.check(rc, "mgp_knn_scan_wide")
+        idx = torch.empty((m, k), dtype=torch.int64, device=q.device)
+        dist = torch.empty((m, k), dtype=q.dtype, device=q.device)
+        rc_fin = _lib.load().mgp_knn_finish_wide(_lib.ptr(q), _lib.ptr(self.train), d, _lib.ptr(best_i), m, k,
+                                                 None, _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr())
+        if rc_fin == _lib.EUNSUPPORTED:
+            # rows per pass from a byte budget: the gathered (rows, k, d) block and its squares (at k = 1023, d = 40 a
+            # fixed 65 536 rows would be 10.7 GB)
+            rows = max(1, self.FINISH_BUDGET_BYTES // (2 * k * d * q.element_size()))
+            for s in range(0, m, rows):
+                c = best_i[s:s + rows].to(torch.int64)
+                diff = q[s:s + rows, None, :] - self.train[c]
+                dd = (diff * diff).sum(-1)
+                order = dd.argsort(dim=1, stable=True)
+                idx[s:s + rows] = c.gather(1, order)
+                dist[s:s + rows] = dd.gather(1, order)
+        else:
+            _lib.check(rc_fin, "mgp_knn_finish_wide")
+        self.last_overflow = overflow
+        redo = overflow.nonzero().reshape(-1)
+        if redo.numel():  # (the contract of the narrow scans; the wide scan's queues cannot overflow)
+            ri, rd = self._dense_nns(q[redo], k, None if exclude is None else exclude[redo])
+            idx[redo], dist[redo] = ri, rd
+        self.last_route = "wide"
         return idx, dist
 
     DENSE_BUDGET_BYTES = 4 << 30  # (chunk x train_count) distance matrix + topk temporaries
@@ -334,7 +396,7 @@ class NN_Wrapper:
             raise ValueError(f"nn_method='ivf' serves 1 <= n < 2^31 table rows, got n = {n}")
         self.train_count, self.feature_count = n, d
         self.nn_count, self.nn_method, self.chunk = k, "ivf", int(chunk)
-        self.use_scan, self.scan_kind, self.last_overflow = False, None, None
+        self.use_scan, self.scan_kind, self.last_overflow, self.last_route = False, None, None, None
         self.last_short = None  # per query: 1 where the probed cells held fewer than k rows (recomputed exactly)
         self._width = max(4, -(-d // 4) * 4)
         self._mean = table.double().mean(0).to(table.dtype)
