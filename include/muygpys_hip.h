@@ -693,6 +693,44 @@ int mgp_solve_large_f32(const float* Kin, const float* Kcross, const float* Y, i
 int mgp_solve_large_f64(const double* Kin, const double* Kcross, const double* Y, int64_t b, int k, int R, double kout,
                         double* mean, double* var, double* ykinvy, double* coeffs, int* info,
                         void* workspace, int64_t workspace_bytes, void* stream);
+/* Hyper-parameter gradients for any such k: the length-scale and noise partials of mgp_posterior_backward_* /
+ * mgp_loocv_backward_* (see there: what the reference obtains from torch autograd over torch/muygps_layer.py:129-164,
+ * and what spares scipy's L-BFGS-B its p + 1 finite-difference evaluations per iteration,
+ * _src/optimize/chassis/numpy.py:57-81) beyond mgp_max_nn_count_backward, on the same blocked factor.  Serves every
+ * k >= 1 with k + 2 <= 1024 (k <= mgp_large_max_nn_count(elem_size, 1) = 1022) whatever R is: the responses enter as
+ * ONE combined right-hand side.  The training table is on both sides (the query of neighbourhood i is row
+ * batch_idx[i]; NULL = row i); any d >= 1, the five closed-form kernels, both metrics, scalar or per-feature length
+ * scale, the three noise modes.  No feature or response cotangents.
+ *   grad_ykinvy given (R must be 1): the LOOCV form, K-bar = gv a a^T - gm a u^T - gyk u u^T with u = K^-1 y;
+ *       grad_mean / grad_var may be NULL (= 0).  grad_ykinvy NULL: the posterior form with grad_mean (b, R) and / or
+ *       grad_var (b).  At least one of the three is given.
+ *   grad_ls (b, ls_count) and grad_noise (b, k): per-neighbourhood partials, written (not accumulated); either may
+ *       be NULL, not both.  A neighbourhood with a non-positive or NaN pivot counts in *info and leaves its rows of
+ *       both untouched.  Every sum inside a neighbourhood runs in a fixed order and nothing is accumulated across
+ *       workgroups: a neighbourhood's partials are the same bits whatever its place in the batch, the batch, the grid,
+ *       the workspace size (at least one slab) and the workspace's previous contents.
+ *   workspace: as above; a backward slab holds the factor trapezoid and the distances of all (k + 1) k / 2 pairs.
+ *   mgp_backward_large_workspace_bytes: one backward slab per workgroup of the grid the launcher would choose, at
+ *       most 512 MiB, at least one slab (b = 0), a multiple of 16; 0 for arguments nothing serves.
+ *   Order of the checks, all before any HIP call: sizes b < 0, k < 1, d < 1, R < 1 (MGP_EINVAL); the empty batch
+ *   (MGP_OK, nothing else looked at); required pointers, grad_ykinvy with R != 1, all three cotangents NULL, both
+ *   outputs NULL, ids, a noise mode without noise_dev, ls_count not in {1, d}, the workspace NULL, misaligned or
+ *   shorter than one slab (MGP_EINVAL); then k + 2 > 1024 or MGP_KERNEL_MATERN_GEN: MGP_EUNSUPPORTED. */
+int64_t mgp_backward_large_workspace_bytes(int elem_size, int k, int64_t b);
+int mgp_hyper_backward_large_f32(const float* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                 int64_t b, int k, const float* targets, int R,
+                                 int noise_mode, double noise_scalar, const float* noise_dev,
+                                 int kernel_id, int metric_id, const float* length_scale, int ls_count,
+                                 const float* grad_mean, const float* grad_var, const float* grad_ykinvy,
+                                 float* grad_ls, float* grad_noise, int* info,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_hyper_backward_large_f64(const double* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                 int64_t b, int k, const double* targets, int R,
+                                 int noise_mode, double noise_scalar, const double* noise_dev,
+                                 int kernel_id, int metric_id, const double* length_scale, int ls_count,
+                                 const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
+                                 double* grad_ls, double* grad_noise, int* info,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Fused fast posterior mean (prediction from precomputed coefficients).  Replaces

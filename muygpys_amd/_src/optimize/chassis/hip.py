@@ -183,7 +183,9 @@ def _scale_mode(muygps, scale_fn):
 
 def _scipy_optimize(muygps, obj_fn: Callable, verbose: bool = False, analytic_gradient: bool = False, **kwargs):
     """numpy.py:57-81.  ``analytic_gradient`` (round 5, opt-in; default: the reference's finite differences, the same
-    trajectory as the reference's): hand scipy the analytic gradient of the LOOCV loss."""
+    trajectory as the reference's): hand scipy the analytic gradient of the LOOCV loss -- for every
+    nn_count the forward serves: beyond ``mgp_max_nn_count_backward`` the gradient comes from the backward on the slab
+    factor (``mgp_hyper_backward_large_*``), up to nn_count = 1022; ``ValueError`` beyond."""
     from scipy import optimize as opt
 
     x0_names, x0, bounds = _get_opt_lists(muygps, verbose=verbose)

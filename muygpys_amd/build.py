@@ -56,6 +56,8 @@ PER_FILE_FLAGS = {
     "mgp_knn_cells.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the blocked factorisation beyond LDS: a 32 x 32 diagonal block and a panel row sit in registers)
     "mgp_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the hyper-parameter backward on the same factor)
+    "mgp_backward_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 

@@ -167,6 +167,12 @@ template <typename T> int launch_fused_large(const FusedArgs&, void* workspace, 
 template <typename T> int launch_solve_large(const SolveArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
 int64_t large_slab_bytes(int elem_size, int k, int R);
 int64_t large_workspace_bytes(int elem_size, int k, int R, int64_t b);
+// mgp_backward_large.hip: the hyper-parameter partials (grad_ls, grad_noise) of BackwardArgs for k + 2 <= kLargeMaxRows,
+// one table on both sides, on the same blocked factor; a backward slab holds the factor trapezoid (two tail rows) and
+// the triangle of pair distances
+template <typename T> int launch_hyper_backward_large(const BackwardArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
+int64_t backward_large_slab_bytes(int elem_size, int k);
+int64_t backward_large_workspace_bytes(int elem_size, int k, int64_t b);
 
 // mgp_shear.hip: the multi-output solve and the shear model
 struct SolveMultiArgs {

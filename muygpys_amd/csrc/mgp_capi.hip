@@ -251,6 +251,24 @@ int solve_large(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, 
   return launch_solve_large<T>(a, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
+// the hyper-parameter backward on the slab factor (mgp_backward_large.hip): one table on both sides
+template <typename T>
+int hyper_backward_large(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg, int R,
+                         int noise_mode, double eps, const T* nd, int kernel_id, int metric_id, const T* ls, int ls_count,
+                         const T* gmean, const T* gvar, const T* gyk, T* gls, T* gnz, int* info, void* ws,
+                         int64_t ws_bytes, void* stream) {
+  BackwardArgs g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES | KERNEL_MAY_BE_GEN, feat, feat, d, bi, ni, b, k, tg, R, noise_mode,
+                                  eps, nd, kernel_id, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (gyk && R != 1) return MGP_EINVAL;  // (the LOOCV losses are defined for one response)
+  if ((!gmean && !gvar && !gyk) || (!gls && !gnz)) return MGP_EINVAL;
+  if (!ws || reinterpret_cast<uintptr_t>(ws) % 16 != 0 || ws_bytes < backward_large_slab_bytes(sizeof(T), k))
+    return MGP_EINVAL;
+  g.grad_mean = gmean, g.grad_var = gvar, g.grad_yk = gyk, g.grad_ls = gls, g.grad_noise = gnz;
+  return launch_hyper_backward_large<T>(g, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024 and the general nu)
+}
+
 // behind the fused launch of a LOOCV evaluation: nothing when a wave kernel walked the tree itself; the walk by kernels
 // over the SAME leaves when it was launched without (three_launch); over the canonical leaves behind another family
 template <typename T>
@@ -618,6 +636,21 @@ MGP_DEFINE_COEF(f64, double)
 MGP_DEFINE_BWD(f32, float)
 MGP_DEFINE_BWD(f64, double)
 int mgp_max_nn_count_backward(int elem_size) { return max_nn_count_backward(elem_size); }
+
+int64_t mgp_backward_large_workspace_bytes(int elem_size, int k, int64_t b) {
+  if ((elem_size != 4 && elem_size != 8) || k < 1 || b < 0 || (int64_t)k + 2 > kLargeMaxRows) return 0;
+  return backward_large_workspace_bytes(elem_size, k, b);
+}
+#define MGP_DEFINE_BWD_LARGE(SUF, T)                                                                                \
+  int mgp_hyper_backward_large_##SUF(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,   \
+                                     const T* tg, int R, int nm, double eps, const T* nd, int kid, int mid,          \
+                                     const T* ls, int lsc, const T* gmean, const T* gvar, const T* gyk, T* gls,      \
+                                     T* gnz, int* info, void* workspace, int64_t workspace_bytes, void* st) {        \
+    return hyper_backward_large<T>(feat, d, bi, ni, b, k, tg, R, nm, eps, nd, kid, mid, ls, lsc, gmean, gvar, gyk,   \
+                                   gls, gnz, info, workspace, workspace_bytes, st);                                  \
+  }
+MGP_DEFINE_BWD_LARGE(f32, float)
+MGP_DEFINE_BWD_LARGE(f64, double)
 
 #define MGP_DEFINE(SUF, T)                                                                                           \
   int mgp_crosswise_diffs_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b,    \

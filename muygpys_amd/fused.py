@@ -342,6 +342,20 @@ def _large_workspace(dtype, k: int, R: int, b: int, device) -> torch.Tensor:
     return torch.empty(size, dtype=torch.uint8, device=device)
 
 
+def _backward_large_workspace(dtype, k: int, b: int, device) -> torch.Tensor:
+    """The workspace of one ``mgp_hyper_backward_large_*`` call (``mgp_backward_large_workspace_bytes``: one backward
+    slab per workgroup of the grid, at most 512 MiB).  ``ValueError`` for a system beyond the kernel."""
+    lib = _lib.load()
+    es = 4 if dtype == torch.float32 else 8
+    size = int(lib.mgp_backward_large_workspace_bytes(es, k, b))
+    if size == 0:
+        raise ValueError(
+            f"nn_count = {k} exceeds the limit of the analytic hyper-parameter gradient, mgp_large_max_nn_count = "
+            f"{lib.mgp_large_max_nn_count(es, 1)} (a local system holds at most 1024 rows: nn_count + 2 in the backward)"
+        )
+    return torch.empty(size, dtype=torch.uint8, device=device)
+
+
 def _posterior_large(spec: KernelSpec, inp: _Inputs, gathered: bool, outs: tuple) -> int:
     """One ``mgp_posterior_large_*`` launch on the plain tables (systems beyond LDS, csrc/mgp_large.hip); ``outs`` as
     for :func:`_posterior_call`.  Returns the status."""
@@ -650,7 +664,11 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     """One backward launch for the hyper-parameters: the per-neighbourhood partials ``(g_l (b, ls_count), g_n (b, k) or
     None)`` of the cotangents ``gm`` / ``gv`` (either may be None) -- and ``gyk`` of ``y^T K^-1 y``: given, the launch is
     the LOOCV objective's (``mgp_loocv_backward_*``, one response), else ``mgp_posterior_backward_*`` with no feature or
-    response cotangents.  The noise is ``spec``'s (homoscedastic); everything else comes from ``inp``."""
+    response cotangents.  The noise is ``spec``'s (homoscedastic); everything else comes from ``inp``.
+
+    A closed-form kernel whose two triangles no longer fit LDS (``nn_count`` beyond ``mgp_max_nn_count_backward``) goes
+    to the backward on the slab factor (``mgp_hyper_backward_large_*``, csrc/mgp_backward_large.hip), up to
+    ``mgp_large_max_nn_count(elem_size, 1)`` = 1022 whatever the response count; ``ValueError`` beyond."""
     P = _lib.ptr
     fn, ls = inp.fn, inp.ls
     g_l = torch.zeros((inp.b, ls.numel()), device=fn.device, dtype=fn.dtype)
@@ -658,13 +676,20 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
     model = (_lib.NOISE_SCALAR, float(spec.noise), None, spec.kernel_id(), spec.metric_id(), P(ls), ls.numel())
     shape = (inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg))
-    out = (P(g_l), P(g_n), P(info), _lib.stream_ptr())
+    out = (P(g_l), P(g_n), P(info))
     if gyk is not None:
-        rc = _lib.fn("loocv_backward", fn.dtype)(P(fn), *shape, *model, P(gm), P(gv), P(gyk), *out)
-        _lib.check(rc, "mgp_loocv_backward")
+        what = "mgp_loocv_backward"
+        rc = _lib.fn("loocv_backward", fn.dtype)(P(fn), *shape, *model, P(gm), P(gv), P(gyk), *out, _lib.stream_ptr())
     else:
-        rc = _lib.fn("posterior_backward", fn.dtype)(P(fn), P(fn), *shape, inp.R, *model, P(gm), P(gv), None, None, None, *out)
-        _lib.check(rc, "mgp_posterior_backward")
+        what = "mgp_posterior_backward"
+        rc = _lib.fn("posterior_backward", fn.dtype)(P(fn), P(fn), *shape, inp.R, *model, P(gm), P(gv), None, None, None,
+                                                     *out, _lib.stream_ptr())
+    if rc == _lib.EUNSUPPORTED and spec.kernel != "matern_gen":
+        what = "mgp_hyper_backward_large"
+        ws = _backward_large_workspace(fn.dtype, inp.k, inp.b, fn.device)
+        rc = _lib.fn("hyper_backward_large", fn.dtype)(P(fn), *shape, inp.R, *model, P(gm), P(gv), P(gyk), *out,
+                                                       P(ws), ws.numel(), _lib.stream_ptr())
+    _lib.check(rc, what)
     return g_l, g_n
 
 
@@ -714,6 +739,9 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     (gp/hyperparameter/scale.py:206,214 against gp/noise/homoscedastic.py:112-113).  Then ``y^T K^-1 y`` comes from a
     second forward launch at ``sigma_noise`` and its cotangent goes back through a second backward launch there; the
     returned noise gradient is the trial noise's (sigma^2 does not depend on it).
+
+    Any ``nn_count`` the forward serves: beyond ``mgp_max_nn_count_backward`` the backward launches run on the slab
+    factor in global memory (``mgp_hyper_backward_large_*``), up to ``nn_count = 1022``; ``ValueError`` beyond.
 
     Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS (the objective the
     drivers maximise is its negative)."""
@@ -805,6 +833,9 @@ def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_l
 
     ``reduce_fn`` (sharded batches): sums a float64 device vector over the ranks in place -- applied to the sums (so
     the mse count is the global one) and to the gradient.
+
+    Any ``nn_count`` the forward serves (``nn_count + 1 + R <= 1024``): beyond ``mgp_max_nn_count_backward`` the
+    backward launch runs on the slab factor in global memory (``mgp_hyper_backward_large_*``).
 
     Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS."""
     if loss not in ("cross_entropy", "mse"):
