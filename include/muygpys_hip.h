@@ -329,7 +329,8 @@ int mgp_last_loocv_geometry(int* grid, int* nh);
  * _src/optimize/loss/mpi.py:57. */
 int mgp_loocv_tree_mode_get(void);
 int mgp_loocv_tree_mode_set(int mode);
-/* launch geometry of the calling thread's most recent wave-kernel / matrix-core-layout launch: workgroups (the
+/* launch geometry of the calling thread's most recent fused launch of an LDS-resident family (wave, rhs, matrix-core
+ * layout, wide, generic, shear; the large kernels note none): workgroups (the
  * persistent grid) and dynamic LDS bytes per workgroup -- what profiles/ quote next to the compiler's register
  * record (lib/kernel_resources.json); diagnostic */
 int mgp_last_launch_geometry(int64_t* workgroups, int* lds_bytes);

@@ -226,7 +226,7 @@ def loocv_tree_selfcheck(device=None, rounds: int = 6, force: bool = False) -> b
 
 
 def last_launch_geometry():
-    """(workgroups, dynamic LDS bytes per workgroup) of this thread's last wave-kernel launch."""
+    """(workgroups, dynamic LDS bytes per workgroup) of this thread's last fused launch (every LDS-resident family)."""
     g, n = C.c_int64(0), C.c_int(0)
     check(load().mgp_last_launch_geometry(C.byref(g), C.byref(n)), "mgp_last_launch_geometry")
     return g.value, n.value

@@ -1020,6 +1020,7 @@ static int launch_rhs_impl(const FusedArgs& a, hipStream_t stream) {
   MGP_HIP_CHECK_LAUNCH();
   note_launch("mgp::fused_rhs_kernel<%s,%d,%s,%s%s>", sizeof(T) == 4 ? "float" : "double", RC, BACK ? "true" : "false",
               GRAM ? "true" : "false", W3 ? ",w3" : (FOLD ? ",fold" : ""));
+  note_launch_geometry(grid, lds);
   return MGP_OK;
 }
 

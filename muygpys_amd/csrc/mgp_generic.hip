@@ -217,10 +217,11 @@ int launch_fused_generic(const FusedArgs& in, hipStream_t stream) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return -(1000 + (int)e);
   }
-  hipLaunchKernelGGL(fused_generic_kernel<T>, dim3(grid_for(a.b, lds)), dim3(block_threads(a.k + 1 + a.R)), lds,
-                     stream, a);
+  const int grid = grid_for(a.b, lds);
+  hipLaunchKernelGGL(fused_generic_kernel<T>, dim3(grid), dim3(block_threads(a.k + 1 + a.R)), lds, stream, a);
   MGP_HIP_CHECK_LAUNCH();
   note_launch("mgp::fused_generic_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  note_launch_geometry(grid, lds);
   return MGP_OK;
 }
 
