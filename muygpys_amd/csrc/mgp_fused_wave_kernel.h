@@ -126,6 +126,10 @@
 #ifndef MGP_F64_DIST_HALF
 #define MGP_F64_DIST_HALF 0
 #endif
+// (folded fp32 kernels, Gram form) partner groups in flight ahead of the block that consumes one.  See phase 2.
+#ifndef MGP_GRAM_PREFETCH
+#define MGP_GRAM_PREFETCH 3
+#endif
 
 // (BWD keeps all NS squared distances through the covariance phase, where the forward retires them batch by batch:
 // five interleaved exp chains on top of that spill 26 registers at two waves per SIMD)
@@ -684,7 +688,12 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
 
   // (FOLD) the folded rows: FS = row l (columns 0 .. 15), FL = row 16 + l, of the neighbourhood of the lane's
   // quarter; quarters 0 / 1 belong to the first task of a pair, 2 / 3 to the second
-  V FL[FOLD ? NG : 1], FS[FOLD ? NGS : 1];
+  // (MIRROR: fp32, 32 slots) lane l owns rows l and NP-1-l instead: together NP + 1 lower-triangle entries whatever
+  // the lane -- nine register groups FM instead of twelve.  See phase 4F.
+  constexpr bool MIRROR = FOLD && sizeof(T) == 4 && NP == 32;
+  constexpr int NGM = (NP + 1 + E - 1) / E;  // (MIRROR) register groups of a lane
+  static_assert(!MIRROR || (NG >= 5 && NG <= 8), "mirror fold: registers 0 .. 4 hold long-row groups in every lane");
+  V FL[FOLD && !MIRROR ? NG : 1], FS[FOLD && !MIRROR ? NGS : 1], FM[MIRROR ? NGM : 1];
   int fold_sub = 0;
   int fold_task_a = 0;
   for (; task >= 0; task = t1, t1 = t2) {
@@ -865,6 +874,7 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
         };
         constexpr int NCF = DFIX > 0 ? DSTFIX / E : 1;  // 16-byte groups per row (static shapes)
         constexpr bool OWNREG = MGP_OWN_REG && DFIX > 0;
+        constexpr bool GPF = FOLD && sizeof(T) == 4 && DFIX > 0 && !OWNREG && !DPRE && MGP_GRAM_PREFETCH > 0;  // pipelined Gram loop
         V x[DFIX > 0 ? NCF : 1];
         if (MGP_PHASE(g, 2)) {
           const bool has = i < k || i == q;
@@ -949,6 +959,38 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
         MGP_WAVE_T(1)
         // ---- phase 2 (Gram form): acc = a'.b' per pair ------------------------------------------
         if (MGP_PHASE(g, 2)) {
+          if constexpr (GPF) {
+            // (folded kernels) the blocks of the loop below as a software pipeline over the 16-byte groups: group gi
+            // of the BA own rows against group gi of partners 1 .. BP, the stream of partner groups requested GPD
+            // blocks ahead of its use (a ring of GPD + 1 register groups) and the own rows of group gi + 1 when group
+            // gi starts -- BP blocks ahead, into the other half of a double buffer (the registers of own0 / own1
+            // below).  Left to itself the scheduler sinks every read to its use to save registers: a partner's two
+            // reads were issued behind the previous partner's last FMA and waited for at once, twenty exposed LDS
+            // round trips a task, and five more for the own rows.  The scheduling barriers pin the order; the wait
+            // counts (LDS returns in order) are the compiler's.  Every accumulator takes its products in the order of
+            // the loop below: the distances are bit-identical.
+            constexpr int NGR = DSTFIX / E, NT = NGR * BP, GPD = MGP_GRAM_PREFETCH;
+            auto own_row = [&](int j) { return Xh + wrap(i + own_offset(j)) * xs; };
+            auto par_group = [&](int t) { return *reinterpret_cast<const V*>(Xh + wrap(i + t % BP + 1) * xs + (t / BP) * E); };
+            V own[2][BA], par[GPD + 1];
+#pragma unroll
+            for (int j = 0; j < BA; ++j) own[0][j] = *reinterpret_cast<const V*>(own_row(j));
+#pragma unroll
+            for (int t = 0; t < GPD && t < NT; ++t) par[t] = par_group(t);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              const int gi = t / BP, s = t % BP;
+              if (t + GPD < NT) par[(t + GPD) % (GPD + 1)] = par_group(t + GPD);
+              if (s == 0 && gi + 1 < NGR) {
+#pragma unroll
+                for (int j = 0; j < BA; ++j) own[(gi + 1) & 1][j] = *reinterpret_cast<const V*>(own_row(j) + (gi + 1) * E);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+              gram_block<BA, BP>(&acc[s], own[gi & 1], par[t % (GPD + 1)]);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          } else {
 #pragma unroll
           for (int c0 = 0; c0 < (DFIX > 0 ? DSTFIX : wp); c0 += CH) {
             V own0[BA], own1[BA];
@@ -971,6 +1013,7 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
               gram_block<BA, BP>(&acc[s - 1], own0, o0);
               gram_block<BA, BP>(&acc[s - 1], own1, o1);
             }
+          }
           }
           // squared distance of a pair: |a'|^2 + |b'|^2 - 2 a'.b', clamped at zero; left in acc[].x
           // (acc[].y = 0) so that the covariance stage below reads it like a difference-form sum
@@ -1241,10 +1284,23 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
       if ((lane >> 5) == fold_sub) {
         const T* Kq = tile + (NH == 1 ? 0 : (lane >> LOGH) & (NH - 1)) * KMAT;
         const int lh = lane & (HALF - 1);
+        if constexpr (MIRROR) {
+          // register r <- long-row group r (r < 8 - lh / 4) or short-row group 8 - r (r >= 8 - lh / 4); a long-row
+          // group beyond the live columns does not exist, its register is a short-row group in every lane
+          const T* rS = Kq + rowoff(lh);
+          const T* rL = Kq + rowoff(NP - 1 - lh);
 #pragma unroll
-        for (int c4 = 0; c4 < NGS; ++c4) FS[c4] = *reinterpret_cast<const V*>(Kq + rowoff(lh) + c4 * E);
+          for (int r = 0; r < NGM; ++r) {
+            const int sg = NGM - 1 - r;
+            const T* src = r <= 4 ? rL + r * E : (r == NGM - 1 || r >= NG ? rS + sg * E : (lh >= E * sg ? rS + sg * E : rL + r * E));
+            FM[r] = *reinterpret_cast<const V*>(src);
+          }
+        } else {
 #pragma unroll
-        for (int c4 = 0; c4 < NG; ++c4) FL[c4] = *reinterpret_cast<const V*>(Kq + rowoff(HALF + lh) + c4 * E);
+          for (int c4 = 0; c4 < NGS; ++c4) FS[c4] = *reinterpret_cast<const V*>(Kq + rowoff(lh) + c4 * E);
+#pragma unroll
+          for (int c4 = 0; c4 < NG; ++c4) FL[c4] = *reinterpret_cast<const V*>(Kq + rowoff(HALF + lh) + c4 * E);
+        }
       }
     } else if constexpr (DLT) {
       // the lane's pairs: slot s holds pair 64 s + lane of the dealt order (lane-linear, conflict-free); and what each
@@ -1297,7 +1353,79 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
       if (MGP_PHASE(g, 8)) {
         const int lh = lane & (HALF - 1);
         T* colq = colbuf + (lane >> LOGH) * NP;  // the neighbourhood's column buffer (together: the row-address array's space)
-        if constexpr (sizeof(T) == 4) {
+        if constexpr (MIRROR) {
+          // ---- mirror fold: lane l owns rows l (short) and NP-1-l (long).  Register r of FM holds
+          //        r = 0 .. 4    columns 4r .. 4r+3 of the long row, in every lane
+          //        r = 5 .. 7    the same where the long row reaches that far (l < 4 (8 - r)), else columns
+          //                      4s .. 4s+3, s = 8 - r, of the short row -- a register group keeps its columns' alignment,
+          //                      so every step indexes registers at compile time
+          //        r = 8         columns 0 .. 3 of the short row
+          // A mixed register's lanes differ in the column group and the multiplier they need: while its short rows are
+          // being eliminated the group comes from a per-lane address (fixed per lane: no more reads than the uniform
+          // ones it replaces) and the multiplier from one select; afterwards the register is a long-row group like
+          // any other (the short rows' lanes take junk updates nobody reads).  The arithmetic of an entry is what it
+          // was: outputs are bit-identical to the (l, 16 + l) layout's.  Group updates per four neighbourhoods at
+          // k = 30: 146 instead of 182, and 36 selects.
+          constexpr int NMX = 3;  // mixed registers 5 .. 7
+          bool shm[NMX];
+          const T* cmx[NMX];
+#pragma unroll
+          for (int u = 0; u < NMX; ++u) {
+            const int r = 5 + u, sg = NGM - 1 - r;
+            shm[u] = lh >= E * sg;
+            cmx[u] = colq + (shm[u] ? sg : r) * E;
+          }
+          // what register r does in step j: 0 nothing, 1 long-row group r, 2 short-row group 8 - r, 3 mixed
+          auto kind = [](int r, int j) {
+            const int g0 = j / E, sg = NGM - 1 - r;
+            const bool la = r < NG && r >= g0 && r < NGM - 1, sa = r > 4 && j < HALF && sg >= g0;
+            return la && sa ? 3 : (la ? 1 : (sa ? 2 : 0));
+          };
+          colq[NP - 1 - lh] = FM[0][0];
+          colq[lh] = FM[NGM - 1][0];
+          V piv = *reinterpret_cast<const V*>(colq);
+#pragma unroll
+          for (int j = 0; j < KFIX; ++j) {
+            const int g0 = j / E, e0 = j % E;
+            const bool sh = j < HALF;  // (compile-time after unrolling) the short rows are still being eliminated
+            const T aL = FM[g0][e0];
+            const T aS = sh ? FM[NGM - 1 - g0][e0] : T(0);
+            V col[NG], colm[NMX];
+            col[g0] = piv;
+#pragma unroll
+            for (int c4 = g0 + 1; c4 < NG; ++c4) {
+              // (a uniform group is read when a register takes it as its long-row or as its short-row group)
+              const bool need = kind(c4, j) == 1 || (NGM - 1 - c4 > 4 && kind(NGM - 1 - c4, j) == 2);
+              if (need) col[c4] = *reinterpret_cast<const V*>(colq + c4 * E);
+            }
+#pragma unroll
+            for (int u = 0; u < NMX; ++u)
+              if (kind(5 + u, j) == 3) colm[u] = *reinterpret_cast<const V*>(cmx[u]);
+            const T p = piv[e0];
+            bad = bad || !(p > T(0));
+            const T rp = pivot_rcp(p);
+            const T nL = -aL * rp, nS = -aS * rp;
+            const V ntL = V(nL), ntS = V(nS);
+            auto upd = [&](int r) {
+              const int kd = kind(r, j);
+              if (kd == 1) FM[r] = col[r < NG ? r : 0] * ntL + FM[r];
+              else if (kd == 2) FM[r] = col[NGM - 1 - r] * ntS + FM[r];
+              else if (kd == 3) FM[r] = colm[r - 5] * V(shm[r - 5] ? nS : nL) + FM[r];
+            };
+            const int g1 = (j + 1 < KFIX ? j + 1 : j) / E;
+            const int s1 = j + 1 < HALF ? NGM - 1 - g1 : -1;  // the register of the short rows' column j + 1
+            upd(g1);
+            if (s1 >= 0) upd(s1);
+            if (j + 1 < KFIX) {  // look-ahead: column j + 1 is complete, post it and ask for its pivot group
+              colq[NP - 1 - lh] = FM[g1][(j + 1) % E];
+              if (s1 >= 0) colq[lh] = FM[s1][(j + 1) % E];
+              piv = *reinterpret_cast<const V*>(colq + g1 * E);
+            }
+#pragma unroll
+            for (int r = 0; r < NGM; ++r)
+              if (r != g1 && r != s1) upd(r);
+          }
+        } else if constexpr (sizeof(T) == 4) {
           colq[HALF + lh] = FL[0][0];
           colq[lh] = FS[0][0];
           V piv = *reinterpret_cast<const V*>(colq);
@@ -1371,8 +1499,35 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
       __builtin_amdgcn_s_setprio(0);
 #endif
       MGP_WAVE_T(4)
-      // Schur block: the query row KFIX and the response rows behind it are long rows (lanes KFIX - HALF ...)
-      if constexpr (RFIX > 1) {
+      // Schur block: the query row KFIX and the response rows behind it are long rows (lanes KFIX - HALF ...;
+      // MIRROR: lanes NP-1 - KFIX and below)
+      if constexpr (MIRROR) {
+        constexpr int QF = KFIX;
+        const int l16 = lane & (HALF - 1);
+        const int row = NP - 1 - l16;  // the lane's long row
+        const bool second = (lane >> 5) != 0;
+        const int64_t nbq = (int64_t)(second ? task : fold_task_a) * NH + (NH == 1 ? 0 : (lane >> LOGH) & (NH - 1));
+        const bool liveq = nbq < a.b && (!second || have_b);
+        T* mean = static_cast<T*>(a.mean);
+        T* var = static_cast<T*>(a.var);
+        T* yk = static_cast<T*>(a.ykinvy);
+        const T sq = FM[QF / E][QF % E];  // column q of the lane's long row
+        T sd = T(0);                       // its diagonal, picked out by a compare-select sweep (one response: column q + 1)
+        if (yk) {
+#pragma unroll
+          for (int c = QF + 1; c < QF + 1 + RFIX; ++c) sd = c == row ? FM[c / E][c % E] : sd;
+        }
+        if (liveq) {
+          if (row == QF) {
+            *(var + nbq) = bad ? num<T>::nan() : sq;
+            if (bad && a.info) atomicAdd(a.info, 1);
+          } else if (row > QF && row <= QF + RFIX) {
+            const int r = row - QF - 1;
+            *(mean + (nbq * RFIX + r)) = bad ? num<T>::nan() : -sq;
+            if (yk) *(yk + (nbq * RFIX + r)) = bad ? num<T>::nan() : -sd;
+          }
+        }
+      } else if constexpr (RFIX > 1) {
         constexpr int QF = KFIX;
         const int l16 = lane & (HALF - 1);
         const bool second = (lane >> 5) != 0;
