@@ -732,6 +732,44 @@ int mgp_hyper_backward_large_f64(const double* features, int d, const int64_t* b
                                  const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
                                  double* grad_ls, double* grad_noise, int* info,
                                  void* workspace, int64_t workspace_bytes, void* stream);
+/* The whole vector-Jacobian product of mgp_posterior_backward_* for any such k: what the reference obtains from torch
+ * autograd when a deep-kernel model trains through MuyGPs_layer (torch/muygps_layer.py:129-164) with an nn_count beyond
+ * mgp_max_nn_count_backward, on the same blocked factor and the same backward slab.  Arguments and semantics as
+ * mgp_posterior_backward_* (two feature tables; the query of neighbourhood i is row batch_idx[i] of feat_q, NULL = row
+ * i); serves every k >= 1 with k + 2 <= 1024 whatever R is, any d >= 1, the five closed-form kernels, both metrics,
+ * scalar or per-feature length scale, the three noise modes.  There is no grad_ykinvy form.
+ *   grad_mean (b, R) / grad_var (b): either may be NULL (= 0), not both.
+ *   grad_feat_q (n_q, d), grad_feat_nn (n_nn, d), grad_targets (n_nn, R): ACCUMULATED into, one atomic add per (row,
+ *       column) and neighbourhood -- the sums of one (point, feature) are completed inside the workgroup in a fixed
+ *       order first; the caller zero-fills; the two feature buffers may be the same buffer.  Pairs at zero distance
+ *       contribute no distance gradient under l2, as above.
+ *   grad_ls (b, ls_count) and grad_noise (b, k): per-neighbourhood partials, written, the same bits whatever the
+ *       placement (as mgp_hyper_backward_large_*).
+ *   Any output may be NULL, not all five.  A neighbourhood with a non-positive or NaN pivot counts in *info, issues
+ *   no atomic and writes no row of grad_ls / grad_noise.
+ *   workspace: as mgp_hyper_backward_large_* (mgp_backward_large_workspace_bytes serves both entries).
+ *   Order of the checks, all before any HIP call: sizes b < 0, k < 1, d < 1, R < 1 (MGP_EINVAL); the empty batch
+ *   (MGP_OK, nothing else looked at); required pointers, both cotangents NULL, all outputs NULL, ids, a noise mode
+ *   without noise_dev, ls_count not in {1, d}, the workspace NULL, misaligned or shorter than one slab (MGP_EINVAL);
+ *   then k + 2 > 1024 or MGP_KERNEL_MATERN_GEN: MGP_EUNSUPPORTED. */
+int mgp_posterior_backward_large_f32(const float* feat_q, const float* feat_nn, int d,
+                                     const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                     const float* targets, int R,
+                                     int noise_mode, double noise_scalar, const float* noise_dev,
+                                     int kernel_id, int metric_id, const float* length_scale, int ls_count,
+                                     const float* grad_mean, const float* grad_var,
+                                     float* grad_feat_q, float* grad_feat_nn, float* grad_targets,
+                                     float* grad_ls, float* grad_noise, int* info,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_posterior_backward_large_f64(const double* feat_q, const double* feat_nn, int d,
+                                     const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                     const double* targets, int R,
+                                     int noise_mode, double noise_scalar, const double* noise_dev,
+                                     int kernel_id, int metric_id, const double* length_scale, int ls_count,
+                                     const double* grad_mean, const double* grad_var,
+                                     double* grad_feat_q, double* grad_feat_nn, double* grad_targets,
+                                     double* grad_ls, double* grad_noise, int* info,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Fused fast posterior mean (prediction from precomputed coefficients).  Replaces

@@ -1,4 +1,5 @@
-"""Differentiable fused posterior: ``mgp_posterior_*`` forward, ``mgp_posterior_backward_*`` backward.
+"""Differentiable fused posterior: ``mgp_posterior_*`` forward, ``mgp_posterior_backward_*`` backward -- and, on request,
+their ``_large_`` forms on the slab factor for an ``nn_count`` beyond LDS (:func:`beyond_lds`).
 
 The reference differentiates this path with torch autograd over its torch backend, keeping the
 ``(b,k,k,d)`` difference tensors alive (torch/muygps_layer.py:129-164; the training loop calls
@@ -9,13 +10,37 @@ materialised and there is no CPU or eager fallback.
 
 from __future__ import annotations
 
+import contextlib
+import os
 from typing import Optional
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .fused import KernelSpec, _noise_args, _normalize
+from .fused import KernelSpec, _backward_large_workspace, _large_workspace, _noise_args, _normalize
+
+# whether ``posterior`` serves an nn_count beyond ``mgp_max_nn_count_backward`` on the slab factor when its caller does
+# not say: off unless MUYGPYS_HIP_AUTOGRAD_LARGE=1 (a backward at nn_count = 1022 takes a 512 MiB workspace and runs
+# at tens of thousands of neighbourhoods per second: asked for, never met by accident)
+_BEYOND_LDS = os.environ.get("MUYGPYS_HIP_AUTOGRAD_LARGE", "") == "1"
+
+
+@contextlib.contextmanager
+def beyond_lds(enabled: bool = True):
+    """``with autograd.beyond_lds(True):`` -- the default of ``posterior(..., beyond_lds=None)`` inside the block; the
+    previous default is restored on the way out."""
+    global _BEYOND_LDS
+    previous, _BEYOND_LDS = _BEYOND_LDS, bool(enabled)
+    try:
+        yield
+    finally:
+        _BEYOND_LDS = previous
+
+
+def beyond_lds_default() -> bool:
+    """What ``posterior(..., beyond_lds=None)`` does right now (the environment's choice, or an enclosing block's)."""
+    return _BEYOND_LDS
 
 
 def _column_sums(x2: torch.Tensor) -> torch.Tensor:
@@ -26,7 +51,7 @@ def _column_sums(x2: torch.Tensor) -> torch.Tensor:
 class _FusedPosterior(torch.autograd.Function):
     @staticmethod
     def forward(ctx, test_features, train_features, targets, length_scale, noise, batch_indices, nn_indices,
-                kernel_id, metric_id, shared_table):
+                kernel_id, metric_id, shared_table, large_backward=False):
         fq, fn, tg = test_features.contiguous(), train_features.contiguous(), targets.contiguous()
         ls = length_scale.contiguous()
         b, k = nn_indices.shape
@@ -35,22 +60,26 @@ class _FusedPosterior(torch.autograd.Function):
         mean = torch.empty((b, R), device=fn.device, dtype=fn.dtype)
         var = torch.empty((b,), device=fn.device, dtype=fn.dtype)
         info = torch.zeros(1, device=fn.device, dtype=torch.int32)
-        rc = _lib.fn("posterior", fn.dtype)(
-            _lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(batch_indices), _lib.ptr(nn_indices), b, k, _lib.ptr(tg), R,
-            mode, eps, _lib.ptr(nz), kernel_id, metric_id, _lib.ptr(ls), ls.numel(),
-            _lib.ptr(mean), _lib.ptr(var), None, _lib.ptr(info), _lib.stream_ptr(),
-        )
-        _lib.check(rc, "mgp_posterior")
+        args = (_lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(batch_indices), _lib.ptr(nn_indices), b, k, _lib.ptr(tg), R)
+        model = (mode, eps, _lib.ptr(nz), kernel_id, metric_id, _lib.ptr(ls), ls.numel())
+        outs = (_lib.ptr(mean), _lib.ptr(var), None, _lib.ptr(info))
+        what = "mgp_posterior"
+        rc = _lib.fn("posterior", fn.dtype)(*args, *model, *outs, _lib.stream_ptr())
+        if rc == _lib.EUNSUPPORTED:  # a system beyond LDS: the blocked factorisation on a slab (the (n, R) table: 0)
+            what = "mgp_posterior_large"
+            ws = _large_workspace(fn.dtype, k, R, b, fn.device)
+            rc = _lib.fn("posterior_large", fn.dtype)(*args, 0, *model, *outs, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, what)
         _lib.raise_if_not_spd(info, "posterior (autograd forward)")
         ctx.save_for_backward(fq, fn, tg, ls, noise, batch_indices, nn_indices)
-        ctx.conf = (mode, eps, kernel_id, metric_id, shared_table)
+        ctx.conf = (mode, eps, kernel_id, metric_id, shared_table, large_backward)
         return mean, var
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_mean, grad_var):
         fq, fn, tg, ls, noise, bi, ni = ctx.saved_tensors
-        mode, eps, kernel_id, metric_id, shared = ctx.conf
+        mode, eps, kernel_id, metric_id, shared, large = ctx.conf
         need_q, need_x, need_t, need_l, need_n = ctx.needs_input_grad[:5]
         b, k = ni.shape
         d, R = fn.shape[1], tg.shape[1]
@@ -58,7 +87,7 @@ class _FusedPosterior(torch.autograd.Function):
         gm = None if grad_mean is None else grad_mean.to(dt).contiguous()
         gv = None if grad_var is None else grad_var.to(dt).contiguous()
         if gm is None and gv is None:
-            return (None,) * 10
+            return (None,) * 11
         nz = None if mode == _lib.NOISE_SCALAR else noise.contiguous()
         # one buffer when the query table is the training table (the LOOCV layout of MuyGPs_layer)
         g_x = torch.zeros_like(fn) if (need_x or (shared and need_q)) else None
@@ -67,13 +96,19 @@ class _FusedPosterior(torch.autograd.Function):
         g_l = torch.empty((b, ls.numel()), device=dev, dtype=dt) if need_l else None
         g_n = torch.empty((b, k), device=dev, dtype=dt) if need_n else None
         info = torch.zeros(1, device=dev, dtype=torch.int32)
-        rc = _lib.fn("posterior_backward", dt)(
+        args = (
             _lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(tg), R,
             mode, eps, _lib.ptr(nz), kernel_id, metric_id, _lib.ptr(ls), ls.numel(),
             _lib.ptr(gm), _lib.ptr(gv), _lib.ptr(g_q), _lib.ptr(g_x), _lib.ptr(g_t), _lib.ptr(g_l), _lib.ptr(g_n),
-            _lib.ptr(info), _lib.stream_ptr(),
+            _lib.ptr(info),
         )
-        _lib.check(rc, "mgp_posterior_backward")
+        if large:  # (decided in `posterior`: nn_count beyond the two LDS triangles)
+            ws = _backward_large_workspace(dt, k, b, dev)
+            rc = _lib.fn("posterior_backward_large", dt)(*args, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+            _lib.check(rc, "mgp_posterior_backward_large")
+        else:
+            rc = _lib.fn("posterior_backward", dt)(*args, _lib.stream_ptr())
+            _lib.check(rc, "mgp_posterior_backward")
         _lib.raise_if_not_spd(info, "posterior (autograd backward)")
         out_l = _column_sums(g_l).to(dt).reshape(ls.shape) if need_l else None
         out_n = None
@@ -87,8 +122,8 @@ class _FusedPosterior(torch.autograd.Function):
         if shared:
             # both roles accumulate in g_x; hand it to whichever leaf asked (autograd adds them anyway)
             return (g_x if need_q and not need_x else None, g_x if need_x else None, g_t, out_l, out_n,
-                    None, None, None, None, None)
-        return (g_q if need_q else None, g_x if need_x else None, g_t, out_l, out_n, None, None, None, None, None)
+                    None, None, None, None, None, None)
+        return (g_q if need_q else None, g_x if need_x else None, g_t, out_l, out_n, None, None, None, None, None, None)
 
 
 def _as_param(v, like: torch.Tensor) -> torch.Tensor:
@@ -104,6 +139,7 @@ def posterior(
     batch_indices: Optional[torch.Tensor],
     nn_indices: torch.Tensor,
     train_targets: torch.Tensor,
+    beyond_lds: Optional[bool] = None,
 ):
     """Differentiable ``(mean, var)`` of every neighbourhood (unscaled variance ``1 - c^T K^-1 c``).
 
@@ -111,16 +147,30 @@ def posterior(
     ``test_features``, ``train_features``, ``train_targets`` and to ``spec.length_scale`` /
     ``spec.noise`` when those are tensors that require grad.  Passing the *same tensor* as
     ``test_features`` and ``train_features`` (``MuyGPs_layer.forward``: crosswise_tensor(x, x, ...),
-    torch/muygps_layer.py:146-155) accumulates both roles into one gradient buffer."""
+    torch/muygps_layer.py:146-155) accumulates both roles into one gradient buffer.
+
+    ``beyond_lds``: serve an ``nn_count`` beyond ``mgp_max_nn_count_backward`` (137 in fp32, 96 in fp64) on the slab
+    factor -- ``mgp_posterior_large_*`` forward, ``mgp_posterior_backward_large_*`` backward, up to ``nn_count`` 1022 and
+    ``nn_count + 1 + response_count <= 1024`` -- instead of raising.  ``None``: the module default (off; set by
+    ``MUYGPYS_HIP_AUTOGRAD_LARGE=1`` or ``with autograd.beyond_lds(True):``)."""
     # (the length scale stays attached to the graph; the noise tensor is decoded inside the autograd function)
     inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, want_noise=False,
                      detach=False)
     fq, fn, ni, tg, b, k, ls = inp.fq, inp.fn, inp.ni, inp.tg, inp.b, inp.k, inp.ls
     kmax = _lib.load().mgp_max_nn_count_backward(4 if fn.dtype == torch.float32 else 8)
-    if k > kmax:
-        raise ValueError(f"nn_count {k} exceeds the differentiable kernel's limit {kmax} for {fn.dtype}")
+    large = k > kmax
+    if large:
+        if not (_BEYOND_LDS if beyond_lds is None else beyond_lds) or spec.kernel == "matern_gen":
+            raise ValueError(f"nn_count {k} exceeds the differentiable kernel's limit {kmax} for {fn.dtype}")
+        lib, es = _lib.load(), fn.element_size()
+        if not (lib.mgp_large_workspace_bytes(es, k, inp.R, b) and lib.mgp_backward_large_workspace_bytes(es, k, b)):
+            raise ValueError(
+                f"nn_count = {k} with {inp.R} response column(s) exceeds mgp_large_max_nn_count = "
+                f"{lib.mgp_large_max_nn_count(es, inp.R)} (a local system holds at "
+                "most 1024 rows: nn_count + 1 + response_count in the forward, nn_count + 2 in the backward)"
+            )
     bi = inp.bi if inp.bi is not None else torch.arange(b, device=ni.device, dtype=torch.int64)
     noise = _as_param(spec.noise, fn)
     mean, var = _FusedPosterior.apply(fq, fn, tg, ls, noise, bi, ni, spec.kernel_id(), spec.metric_id(),
-                                      test_features is train_features)
+                                      test_features is train_features, large)
     return (mean.reshape(b) if inp.squeeze else mean), var

@@ -171,6 +171,9 @@ int64_t large_workspace_bytes(int elem_size, int k, int R, int64_t b);
 // one table on both sides, on the same blocked factor; a backward slab holds the factor trapezoid (two tail rows) and
 // the triangle of pair distances
 template <typename T> int launch_hyper_backward_large(const BackwardArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
+// ... and the whole vector-Jacobian product of BackwardArgs on the same slab (no grad_yk): feat_q / feat_nn may be two
+// tables; the feature and response cotangents leave with one atomic add per (row, column) and neighbourhood
+template <typename T> int launch_posterior_backward_large(const BackwardArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
 int64_t backward_large_slab_bytes(int elem_size, int k);
 int64_t backward_large_workspace_bytes(int elem_size, int k, int64_t b);
 

@@ -7,7 +7,8 @@
 // row after row: acc of every pair, later its cotangent q], each region in whole 256-byte lines.  The query is the
 // training row batch_idx[nb]: one table serves both sides, as in LOOCV.
 //
-// Per neighbourhood:
+// Per neighbourhood (the phases are in mgp_backward_large.h, shared with the whole vector-Jacobian product of
+// mgp_backward_large_full.hip):
 //   1. assemble as fused_large_kernel does (feature chunks of dc columns through LDS); the squared distances
 //      accumulate in the triangle and stay there, the last chunk writes the covariances into the trapezoid.  Two tail
 //      rows whatever R is: c, and ONE combined right-hand side yt = y (LOOCV form) or Y gm
@@ -21,49 +22,20 @@
 // Every sum is per-thread partials in a fixed pair order -> wave_sum -> the waves' totals in wave order through LDS:
 // no floating-point atomic, so what a neighbourhood returns depends on nothing but its own inputs (the block size is
 // a function of k alone).
-#include "mgp_large_factor.h"
+#include "mgp_backward_large.h"
 
 namespace mgp {
 
-constexpr int kBwdGroup = 8;  // features summed per pass over the triangle (Anisotropy)
-constexpr int kBwdMaxWaves = 8;
-
-// the workgroup's total of v, to every thread, in a fixed order: lanes by the butterfly, waves in ascending order.
-// red: kBwdMaxWaves elements of LDS.  Two barriers.
-template <typename T>
-__device__ __forceinline__ T block_sum_ordered(T v, T* red, int tid, int NT) {
-  v = wave_sum(v);
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  T s = red[0];
-  for (int w = 1; w < (NT >> 6); ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
-
-// dynamic LDS carve (every array 16-byte aligned; KA = k rounded up to a 16-byte piece):
-// [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T][av: KA T][wv: KA T][red: kBwdMaxWaves*kBwdGroup T]
 template <typename T>
 __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs g, T* workspace, int slab_elems, int factor_elems) {
-  using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
-  constexpr int U = 2;  // entries of a tail row per thread: k <= 126 at 256 threads, k <= 1022 at 512
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const FusedArgs& a = g.f;
-  const int k_ = a.k, d = a.d, R = a.R, dc = a.dc;
-  const int XP = dc + E;
-  const int KA = (k_ + E - 1) / E * E;
-  T* Lb = reinterpret_cast<T*>(smem);
-  int64_t* idx = reinterpret_cast<int64_t*>(Lb + LNB * large_lp<T>());
-  T* X = reinterpret_cast<T*>(idx + ((k_ + 2) & ~1));
-  T* il = X + (k_ + 1) * XP;
-  T* av = il + dc;
-  T* wv = av + KA;
-  T* red = wv + KA;
+  const int k_ = a.k, d = a.d, dc = a.dc;
+  const BackwardLargeLds<T> s = backward_large_carve<T>(smem, k_, dc);
+  T *av = s.av, *wv = s.wv;
 
   const T* feat = static_cast<const T*>(a.feat_nn);
-  const T* targets = static_cast<const T*>(a.targets);
-  const T* noise_dev = static_cast<const T*>(a.noise_dev);
   const T* ls = static_cast<const T*>(a.length_scale);
   const T* gmean = static_cast<const T*>(g.grad_mean);
   const T* gvar = static_cast<const T*>(g.grad_var);
@@ -93,116 +65,19 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
     T* slab = workspace + (int64_t)blockIdx.x * slab_elems;
     const SlabRows<T> row{slab, k};
     T* Dst = slab + factor_elems;
-    for (int r = tid; r <= k; r += NT)
-      idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
-    __syncthreads();
 
     // ---- 1. squared distances (kept in Dst), covariances, nugget, the two tail rows ----
-    for (int d0 = 0; d0 < d; d0 += dc) {
-      const int w = min(dc, d - d0);
-      const int wp = (w + E - 1) / E * E;  // zero-padded to whole 16-byte pieces
-      gather_tile_lds<T>(X, XP, feat, feat, idx, k, d, d0, w, wp, vec_ok, tid, NT);
-      if (aniso)
-        for (int c = tid; c < wp; c += NT) il[c] = c < w ? T(1) / ls[d0 + c] : T(0);
-      __syncthreads();
-      for (int p = tid; p < npairs; p += NT) {
-        int a_, c_;
-        large_tri_decode(p, a_, c_);
-        const T* xa = X + a_ * XP;
-        const T* xc = X + c_ * XP;
-        T acc = T(0);
-        if (aniso) {
-#pragma unroll 2
-          for (int j = 0; j < wp; j += E) {
-            const V df = (*reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j)) *
-                         *reinterpret_cast<const V*>(il + j);
-            acc += vec_dot(df, df);
-          }
-        } else {
-#pragma unroll 2
-          for (int j = 0; j < wp; j += E) {
-            const V df = *reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j);
-            acc += vec_dot(df, df);
-          }
-        }
-        if (d0 > 0) acc += Dst[p];
-        if (keep_acc) Dst[p] = acc;
-        // the last chunk also writes the covariance into the system
-        if (d0 + dc >= d) row(a_)[c_] = kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale));
-      }
-      __syncthreads();
-    }
-    for (int r = tid; r < k; r += NT) {
-      T eps;
-      if (a.noise_mode == MGP_NOISE_SCALAR) eps = (T)a.noise_scalar;
-      else if (a.noise_mode == MGP_NOISE_TABLE) eps = noise_dev[idx[r]];
-      else eps = noise_dev[nb * k + r];
-      row(r)[r] = T(1) + eps;  // kernel(0) == 1 for every kernel on the path
-      T yt = T(0);
-      if (gyk)
-        yt = targets[idx[r] * (int64_t)R];
-      else if (gmean)
-        for (int q = 0; q < R; ++q) yt += gmean[nb * R + q] * targets[idx[r] * (int64_t)R + q];
-      row(k + 1)[r] = yt;
-    }
-    __syncthreads();
+    backward_large_assemble<T>(a, gmean, gyk, keep_acc, post_scale, nb, k, row, Dst, s, tid, NT);
 
     // ---- 2. factorisation; rows k, k + 1 then hold z = L^-1 c and zy = L^-1 yt ----
-    const bool bad = factor_augmented_slab<T>(row, k, rows, Lb, tid, NT);
+    const bool bad = factor_augmented_slab<T>(row, k, rows, s.Lb, tid, NT);
     if (bad) {  // uniform
       if (tid == 0 && a.info) atomicAdd(a.info, 1);
       continue;  // the partials of a non-SPD neighbourhood are left untouched
     }
 
     // ---- 3. back-substitution of both tail rows, in LDS ----
-    for (int m = tid; m < k; m += NT) {
-      av[m] = row(k)[m];
-      wv[m] = row(k + 1)[m];
-    }
-    {
-      T ln[U], ivn, oa[U], ow[U];
-      const T* Lj = row(k - 1);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int m = tid + u * NT;
-        ln[u] = m < k - 1 ? Lj[m] : T(0);
-        oa[u] = ow[u] = T(0);
-      }
-      ivn = Lj[k - 1];
-      __syncthreads();
-      for (int j = k - 1; j >= 0; --j) {
-        T l[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) l[u] = ln[u];
-        const T iv = ivn;
-        if (j > 0) {  // row j - 1 of L: nothing in it depends on this step
-          const T* Ln = row(j - 1);
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const int m = tid + u * NT;
-            ln[u] = m < j - 1 ? Ln[m] : T(0);
-          }
-          ivn = Ln[j - 1];
-        }
-        const T xa = av[j] * iv, xw = wv[j] * iv;  // (entry j is final: steps > j are behind the barrier)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int m = tid + u * NT;
-          if (m < j) {
-            av[m] -= l[u] * xa;
-            wv[m] -= l[u] * xw;
-          }
-          if (m == j) oa[u] = xa, ow[u] = xw;  // its owner keeps the solution; written once nobody reads entry j
-        }
-        __syncthreads();
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int m = tid + u * NT;
-        if (m < k) av[m] = oa[u], wv[m] = ow[u];
-      }
-      __syncthreads();
-    }
+    backward_large_solve_tails<T>(row, k, av, wv, tid, NT);
 
     // ---- 4. cotangents: a = K^-1 c in av, w = K^-1 yt in wv ----
     const T gv = gvar ? gvar[nb] : T(0);
@@ -213,14 +88,7 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
       for (int p = tid; p < npairs; p += NT) {
         int a_, c_;
         large_tri_decode(p, a_, c_);
-        const T ac = av[c_], wc = wv[c_];
-        T gK;
-        if (a_ < k) {
-          const T aa = av[a_], wa = wv[a_];
-          gK = T(2) * gv * aa * ac - gm1 * (aa * wc + ac * wa) - T(2) * gyv * wa * wc;
-        } else {
-          gK = gm1 * wc - T(2) * gv * ac;
-        }
+        const T gK = backward_large_pair_cotangent<T>(av, wv, a_, c_, k, gv, gm1, gyv);
         const T x = metric_arg<T>(Dst[p], a.metric_id, post_scale);
         const T kp = kernel_deriv<T>(a.kernel_id, x);
         if (aniso) {
@@ -233,7 +101,7 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
         }
       }
       if (!aniso) {
-        const T total = block_sum_ordered<T>(liso, red, tid, NT);
+        const T total = block_sum_ordered<T>(liso, s.red, tid, NT);
         if (tid == 0) gls[nb] = -(l2 ? T(1) : T(2)) * inv_l * total;  // dx/dl = -x/l | -2x/l
       }
     }
@@ -246,52 +114,11 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
       const int w = min(dc, d - d0);
       const int wp = (w + E - 1) / E * E;
       __syncthreads();  // q is in the triangle; the previous chunk's rows are consumed
-      gather_tile_lds<T>(X, XP, feat, feat, idx, k, d, d0, w, wp, vec_ok, tid, NT);
+      gather_tile_lds<T>(s.X, s.XP, feat, feat, s.idx, k, d, d0, w, wp, vec_ok, tid, NT);
       __syncthreads();
-      for (int c0 = 0; c0 < wp; c0 += kBwdGroup) {
-        V s[kBwdGroup / E];
-#pragma unroll
-        for (int u = 0; u < kBwdGroup / E; ++u) s[u] = V(0);
-        for (int p = tid; p < npairs; p += NT) {
-          int a_, c_;
-          large_tri_decode(p, a_, c_);
-          const T q = Dst[p];
-          const T* xa = X + a_ * XP + c0;
-          const T* xc = X + c_ * XP + c0;
-#pragma unroll
-          for (int u = 0; u < kBwdGroup / E; ++u)
-            if (c0 + u * E < wp) {  // uniform
-              const V df = *reinterpret_cast<const V*>(xa + u * E) - *reinterpret_cast<const V*>(xc + u * E);
-              s[u] += q * df * df;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kBwdGroup / E; ++u)
-#pragma unroll
-          for (int e = 0; e < E; ++e) {
-            const T v = wave_sum(s[u][e]);
-            if ((tid & 63) == 0) red[(tid >> 6) * kBwdGroup + u * E + e] = v;
-          }
-        __syncthreads();
-        if (tid < kBwdGroup && c0 + tid < w) {
-          T t = red[tid];
-          for (int wi = 1; wi < (NT >> 6); ++wi) t += red[wi * kBwdGroup + tid];
-          const T ilc = T(1) / ls[d0 + c0 + tid];
-          gls[nb * (int64_t)a.ls_count + d0 + c0 + tid] = T(-2) * ilc * ilc * ilc * t;
-        }
-        __syncthreads();
-      }
+      backward_large_ls_chunk<T>(Dst, s.X, s.XP, s.red, ls + d0, gls + nb * (int64_t)a.ls_count + d0, w, wp, npairs, tid, NT);
     }
   }
-}
-
-template <typename T>
-static size_t backward_large_lds_bytes(int k, int dc) {
-  const int E = 16 / (int)sizeof(T);
-  size_t n = (size_t)((k + 2) & ~1) * sizeof(int64_t);
-  n += ((size_t)LNB * large_lp<T>() + (size_t)(k + 1) * (dc + E) + dc + 2 * (size_t)((k + E - 1) / E * E) +
-        (size_t)kBwdMaxWaves * kBwdGroup) * sizeof(T);
-  return (n + 15) & ~(size_t)15;
 }
 
 // the factor trapezoid with two tail rows, then the triangle of the (k+1)-point set: whole 256-byte lines each
@@ -316,19 +143,14 @@ int launch_hyper_backward_large(const BackwardArgs& in, void* workspace, int64_t
   if (rows > kLargeMaxRows || g.f.kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
   const int k = g.f.k;
   const int64_t slab = backward_large_slab_bytes(sizeof(T), k);
-  int dc = g.f.d < 64 ? (g.f.d + 7) / 8 * 8 : 64;  // as the forward: a multiple of 8, as wide as fits
-  while (dc > 8 && backward_large_lds_bytes<T>(k, dc) > kMaxLds) dc -= 8;
-  const size_t lds = backward_large_lds_bytes<T>(k, dc);
-  if (lds > kMaxLds) return MGP_EUNSUPPORTED;
-  g.f.dc = dc;
+  size_t lds;
+  if (!backward_large_plan<T>(k, g.f.d, g.f.dc, lds)) return MGP_EUNSUPPORTED;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hyper_backward_large_kernel<T>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return -(1000 + (int)e);
   }
-  int64_t grid = workspace_bytes / slab;  // one workgroup per slab, at most one per CU, at most b
-  if (grid > kCuCount * kMaxPerCu) grid = kCuCount * kMaxPerCu;
-  if (grid > g.f.b) grid = g.f.b;
+  const int64_t grid = backward_large_grid(workspace_bytes, slab, g.f.b);
   hipLaunchKernelGGL(hyper_backward_large_kernel<T>, dim3((unsigned)grid), dim3(block_threads((int)rows)), lds, stream, g,
                      static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)),
                      (int)(large_slab_bytes(sizeof(T), k, 1) / (int64_t)sizeof(T)));

@@ -269,6 +269,24 @@ int hyper_backward_large(const T* feat, int d, const int64_t* bi, const int64_t*
   return launch_hyper_backward_large<T>(g, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024 and the general nu)
 }
 
+// ... and the whole vector-Jacobian product there: two tables, every cotangent of mgp_posterior_backward_*
+template <typename T>
+int posterior_backward_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                             const T* tg, int R, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id,
+                             const T* ls, int ls_count, const T* gmean, const T* gvar, T* gfq, T* gfn, T* gtg, T* gls,
+                             T* gnz, int* info, void* ws, int64_t ws_bytes, void* stream) {
+  BackwardArgs g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES | KERNEL_MAY_BE_GEN, fq, fn, d, bi, ni, b, k, tg, R, noise_mode, eps,
+                                  nd, kernel_id, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if ((!gmean && !gvar) || (!gfq && !gfn && !gtg && !gls && !gnz)) return MGP_EINVAL;
+  if (!ws || reinterpret_cast<uintptr_t>(ws) % 16 != 0 || ws_bytes < backward_large_slab_bytes(sizeof(T), k))
+    return MGP_EINVAL;
+  g.grad_mean = gmean, g.grad_var = gvar;
+  g.grad_feat_q = gfq, g.grad_feat_nn = gfn, g.grad_targets = gtg, g.grad_ls = gls, g.grad_noise = gnz;
+  return launch_posterior_backward_large<T>(g, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024 and the general nu)
+}
+
 // behind the fused launch of a LOOCV evaluation: nothing when a wave kernel walked the tree itself; the walk by kernels
 // over the SAME leaves when it was launched without (three_launch); over the canonical leaves behind another family
 template <typename T>
@@ -651,6 +669,17 @@ int64_t mgp_backward_large_workspace_bytes(int elem_size, int k, int64_t b) {
   }
 MGP_DEFINE_BWD_LARGE(f32, float)
 MGP_DEFINE_BWD_LARGE(f64, double)
+#define MGP_DEFINE_BWD_LARGE_FULL(SUF, T)                                                                           \
+  int mgp_posterior_backward_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,      \
+                                         int64_t b, int k, const T* tg, int R, int nm, double eps, const T* nd,      \
+                                         int kid, int mid, const T* ls, int lsc, const T* gmean, const T* gvar,      \
+                                         T* gfq, T* gfn, T* gtg, T* gls, T* gnz, int* info, void* workspace,         \
+                                         int64_t workspace_bytes, void* st) {                                        \
+    return posterior_backward_large<T>(fq, fn, d, bi, ni, b, k, tg, R, nm, eps, nd, kid, mid, ls, lsc, gmean, gvar,  \
+                                       gfq, gfn, gtg, gls, gnz, info, workspace, workspace_bytes, st);               \
+  }
+MGP_DEFINE_BWD_LARGE_FULL(f32, float)
+MGP_DEFINE_BWD_LARGE_FULL(f64, double)
 
 #define MGP_DEFINE(SUF, T)                                                                                           \
   int mgp_crosswise_diffs_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b,    \

@@ -343,7 +343,7 @@ def _large_workspace(dtype, k: int, R: int, b: int, device) -> torch.Tensor:
 
 
 def _backward_large_workspace(dtype, k: int, b: int, device) -> torch.Tensor:
-    """The workspace of one ``mgp_hyper_backward_large_*`` call (``mgp_backward_large_workspace_bytes``: one backward
+    """The workspace of one ``mgp_hyper_backward_large_*`` / ``mgp_posterior_backward_large_*`` call (``mgp_backward_large_workspace_bytes``: one backward
     slab per workgroup of the grid, at most 512 MiB).  ``ValueError`` for a system beyond the kernel."""
     lib = _lib.load()
     es = 4 if dtype == torch.float32 else 8

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from muygpys_amd import lazy
+from muygpys_amd import autograd, lazy
 from muygpys_amd.gp.deformation import Isotropy
 from muygpys_amd.gp.hyperparameter import ScalarParam
 from muygpys_amd.gp.muygps import MuyGPS
@@ -36,9 +36,13 @@ class MuyGPs_layer(nn.Module):
     ``forward(x)`` takes the embedded training features ``(train_count, embed_dim)`` and returns
     ``(predictions (b, R), variances (b,))`` for the batch given at construction; only Isotropy with a
     scalar length scale is accepted, like muygps_layer.py:107-121.
+
+    ``beyond_lds=True`` (not in the reference): an ``nn_count`` beyond ``mgp_max_nn_count_backward`` trains on the
+    slab factor (``muygpys_amd.autograd.beyond_lds``) instead of raising ``ValueError``.
     """
 
-    def __init__(self, muygps_model: MuyGPS, batch_indices, batch_nn_indices, batch_targets, batch_nn_targets):
+    def __init__(self, muygps_model: MuyGPS, batch_indices, batch_nn_indices, batch_targets, batch_nn_targets,
+                 beyond_lds: bool = False):
         super().__init__()
         if not isinstance(muygps_model.kernel.deformation, Isotropy):
             raise NotImplementedError(
@@ -56,8 +60,14 @@ class MuyGPs_layer(nn.Module):
         self.batch_nn_indices = batch_nn_indices
         self.batch_targets = batch_targets
         self.batch_nn_targets = batch_nn_targets
+        self.beyond_lds = bool(beyond_lds)
 
     def forward(self, x):
+        # (the keyword turns the route on; it never turns a default off that the environment or an outer block set)
+        with autograd.beyond_lds(self.beyond_lds or autograd.beyond_lds_default()):
+            return self._forward(x)
+
+    def _forward(self, x):
         self.muygps_model._make()
         crosswise = self.deformation.crosswise_tensor(x, x, self.batch_indices, self.batch_nn_indices, lazy=True)
         pairwise = self.deformation.pairwise_tensor(x, self.batch_nn_indices, lazy=True)
@@ -77,9 +87,10 @@ class MultivariateMuyGPs_layer(nn.Module):
 
     ``multivariate_muygps_model`` is anything with a ``models`` sequence of :class:`MuyGPS` (the
     reference's deprecated ``MultivariateMuyGPS`` container is not part of this package).  Returns
-    ``(predictions (b, R), variances (b, R))``."""
+    ``(predictions (b, R), variances (b, R))``.  ``beyond_lds``: as :class:`MuyGPs_layer`."""
 
-    def __init__(self, multivariate_muygps_model, batch_indices, batch_nn_indices, batch_targets, batch_nn_targets):
+    def __init__(self, multivariate_muygps_model, batch_indices, batch_nn_indices, batch_targets, batch_nn_targets,
+                 beyond_lds: bool = False):
         super().__init__()
         models = getattr(multivariate_muygps_model, "models", multivariate_muygps_model)
         self.multivariate_muygps_model = multivariate_muygps_model
@@ -89,8 +100,13 @@ class MultivariateMuyGPs_layer(nn.Module):
         self.batch_nn_indices = batch_nn_indices
         self.batch_targets = batch_targets
         self.batch_nn_targets = batch_nn_targets
+        self.beyond_lds = bool(beyond_lds)
 
     def forward(self, x):
+        with autograd.beyond_lds(self.beyond_lds or autograd.beyond_lds_default()):
+            return self._forward(x)
+
+    def _forward(self, x):
         table = _targets_table(self.batch_nn_indices, self.batch_nn_targets.to(x.dtype), x.shape[0])
         if table.shape[1] != len(self.models):
             raise ValueError(f"{len(self.models)} models for {table.shape[1]} response columns")
