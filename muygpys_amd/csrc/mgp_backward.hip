@@ -14,6 +14,7 @@
 // kappa and the metric is applied per pair, and the per-point feature cotangents leave with one
 // atomic add per (point, feature).
 #include "mgp_args.h"
+#include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
 namespace mgp {
@@ -330,8 +331,6 @@ __global__ __launch_bounds__(256) void backward_kernel(BackwardArgs g, int stage
   }
 }
 
-static const size_t kMaxLdsBwd = 160 * 1024;
-
 template <typename T>
 static size_t backward_lds_bytes(int k, int dc) {
   const int SP = lds_row_stride<T>(k);
@@ -344,33 +343,18 @@ static size_t backward_lds_bytes(int k, int dc) {
 template <typename T>
 int launch_backward(const BackwardArgs& in, hipStream_t stream) {
   BackwardArgs g = in;
-  int dc = g.f.d < 64 ? (g.f.d + 7) / 8 * 8 : 64;  // multiple of 8: whole 16-byte pieces, odd slot count
-  while (dc > 8 && backward_lds_bytes<T>(g.f.k, dc) > kMaxLdsBwd) dc -= 8;
-  const size_t lds = backward_lds_bytes<T>(g.f.k, dc);
-  if (lds > kMaxLdsBwd) return MGP_EUNSUPPORTED;
-  g.f.dc = dc;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&backward_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(1000 + (int)e);
-  }
-  int per_cu = (int)(kMaxLdsBwd / (((lds + 1279) / 1280) * 1280));  // LDS comes in 1280-byte granules
-  per_cu = per_cu < 1 ? 1 : (per_cu > 16 ? 16 : per_cu);
-  const int64_t full = 256LL * per_cu;
+  const FeatureChunk fc = feature_chunk(g.f.d, [&](int dc) { return backward_lds_bytes<T>(g.f.k, dc); });
+  if (!fc.fits) return MGP_EUNSUPPORTED;
+  g.f.dc = fc.dc;
   const int threads = g.f.k + 2 <= 64 ? 64 : (g.f.k + 2 <= 128 ? 128 : 256);
-  hipLaunchKernelGGL(backward_kernel<T>, dim3((unsigned)(g.f.b < full ? g.f.b : full)), dim3(threads), lds, stream, g, g_bwd_stage);
-  MGP_HIP_CHECK_LAUNCH();
-  return MGP_OK;
+  return launch_capacity(&backward_kernel<T>, threads, fc.lds, g.f.b, Capacity{16}, stream, nullptr, g, g_bwd_stage).status;
 }
 
 template int launch_backward<float>(const BackwardArgs&, hipStream_t);
 template int launch_backward<double>(const BackwardArgs&, hipStream_t);
 
 int max_nn_count_backward(int elem_size) {
-  int k = 1;
-  while ((elem_size == 4 ? backward_lds_bytes<float>(k + 1, 8) : backward_lds_bytes<double>(k + 1, 8)) <= kMaxLdsBwd)
-    ++k;
-  return k;
+  return largest_k([&](int k) { return (elem_size == 4 ? backward_lds_bytes<float>(k, 8) : backward_lds_bytes<double>(k, 8)) <= kCuLdsBytes; });
 }
 
 }  // namespace mgp

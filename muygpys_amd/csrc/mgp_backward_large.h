@@ -60,20 +60,10 @@ static size_t backward_large_lds_bytes(int k, int dc) {
   return (n + 15) & ~(size_t)15;
 }
 
-// the feature chunk and the LDS of a launch: dc as the forward (a multiple of 8, as wide as fits); false when nothing fits
+// the feature chunk and the LDS of a launch: dc as the forward (a multiple of 8, as wide as fits)
 template <typename T>
-static bool backward_large_plan(int k, int d, int& dc, size_t& lds) {
-  dc = d < 64 ? (d + 7) / 8 * 8 : 64;
-  while (dc > 8 && backward_large_lds_bytes<T>(k, dc) > kMaxLds) dc -= 8;
-  lds = backward_large_lds_bytes<T>(k, dc);
-  return lds <= kMaxLds;
-}
-
-// one workgroup per slab, at most one per CU, at most b
-static inline int64_t backward_large_grid(int64_t workspace_bytes, int64_t slab, int64_t b) {
-  int64_t grid = workspace_bytes / slab;
-  if (grid > kCuCount * kMaxPerCu) grid = kCuCount * kMaxPerCu;
-  return grid > b ? b : grid;
+static FeatureChunk backward_large_chunk(int k, int d) {
+  return feature_chunk(d, [&](int dc) { return backward_large_lds_bytes<T>(k, dc); });
 }
 
 // ---- 1. the index list, squared distances (kept in Dst when keep_acc), covariances, nugget, the two tail rows: c, and

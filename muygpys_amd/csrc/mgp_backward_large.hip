@@ -130,9 +130,7 @@ int64_t backward_large_slab_bytes(int elem_size, int k) {
 }
 
 int64_t backward_large_workspace_bytes(int elem_size, int k, int64_t b) {
-  const int64_t slab = backward_large_slab_bytes(elem_size, k);
-  int64_t n = b < 1 ? 1 : b;
-  if (n > kCuCount * kMaxPerCu) n = kCuCount * kMaxPerCu;
+  const int64_t slab = backward_large_slab_bytes(elem_size, k), n = slab_count(b);
   return n * slab > kMaxWorkspace ? kMaxWorkspace : n * slab;
 }
 
@@ -143,20 +141,14 @@ int launch_hyper_backward_large(const BackwardArgs& in, void* workspace, int64_t
   if (rows > kLargeMaxRows || g.f.kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
   const int k = g.f.k;
   const int64_t slab = backward_large_slab_bytes(sizeof(T), k);
-  size_t lds;
-  if (!backward_large_plan<T>(k, g.f.d, g.f.dc, lds)) return MGP_EUNSUPPORTED;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&hyper_backward_large_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(1000 + (int)e);
-  }
-  const int64_t grid = backward_large_grid(workspace_bytes, slab, g.f.b);
-  hipLaunchKernelGGL(hyper_backward_large_kernel<T>, dim3((unsigned)grid), dim3(block_threads((int)rows)), lds, stream, g,
-                     static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)),
-                     (int)(large_slab_bytes(sizeof(T), k, 1) / (int64_t)sizeof(T)));
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::hyper_backward_large_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
-  return MGP_OK;
+  const FeatureChunk fc = backward_large_chunk<T>(k, g.f.d);
+  if (!fc.fits) return MGP_EUNSUPPORTED;
+  g.f.dc = fc.dc;
+  // (one workgroup per slab, at most one per CU, at most b)
+  const LaunchLabel label(g.f.b, k, g.f.d, g.f.R, "mgp::hyper_backward_large_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return launch_capacity(&hyper_backward_large_kernel<T>, slab_block_threads((int)rows), fc.lds, g.f.b, Capacity{kMaxPerCu, workspace_bytes / slab},
+                         stream, &label, g, static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)),
+                         (int)(large_slab_bytes(sizeof(T), k, 1) / (int64_t)sizeof(T))).status;
 }
 
 template int launch_hyper_backward_large<float>(const BackwardArgs&, void*, int64_t, hipStream_t);

@@ -488,15 +488,8 @@ static int launch_bwd_np_impl(const BackwardArgs& g, hipStream_t stream) {
   const int vec_ok = (g.f.d % E == 0) && (align % 16 == 0);
   const size_t lds = ((size_t)NH * NP * xs + (size_t)NH * NP * KS + 4 * 64) * sizeof(T) + 64 * sizeof(int64_t);
   static Residency res;
-  int per_cu = 0, cus = 0;
-  const int rc = res.lookup(reinterpret_cast<const void*>(&backward_wave_kernel<T, NP, DG, KFIX, HYPER>), 64, lds, &per_cu, &cus);
-  if (rc != MGP_OK) return rc;
-  const int64_t ntasks = (g.f.b + NH - 1) / NH;
-  int64_t grid = (int64_t)cus * per_cu;
-  if (grid > ntasks) grid = ntasks;
-  hipLaunchKernelGGL((backward_wave_kernel<T, NP, DG, KFIX, HYPER>), dim3((unsigned)grid), dim3(64), lds, stream, g, vec_ok);
-  MGP_HIP_CHECK_LAUNCH();
-  return MGP_OK;
+  return launch_resident(&backward_wave_kernel<T, NP, DG, KFIX, HYPER>, res, 64, lds, (g.f.b + NH - 1) / NH, nullptr, stream, nullptr, g,
+                         vec_ok).status;
 }
 // (no feature cotangent asked for: the instantiation without the sweep)
 template <typename T, int NP, int DG, int KFIX = 0>

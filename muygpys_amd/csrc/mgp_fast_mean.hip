@@ -18,6 +18,7 @@
 // i: difference-form distance to the query row, kernel, product with its coefficient(s), and a
 // cross-lane sum.
 #include "mgp_args.h"
+#include "mgp_launch.h"
 
 namespace mgp {
 
@@ -153,7 +154,7 @@ static int launch_fast_np(FastArgs a, hipStream_t stream) {
   size_t lds = ((size_t)NH * NP * a.xs + a.dst + (a.dst & 1)) * sizeof(T) + 64 * sizeof(int64_t);
   lds = (lds + 15) & ~(size_t)15;
   const int64_t ntasks = (a.b + NH - 1) / NH;
-  int64_t grid = 256LL * 16;  // memory-bound: grid-stride over plenty of resident waves
+  int64_t grid = kAssumedCus * 16;  // memory-bound: grid-stride over plenty of resident waves
   if (grid > ntasks) grid = ntasks;
   hipLaunchKernelGGL((fast_mean_kernel<T, NP>), dim3((unsigned)grid), dim3(64), lds, stream, a);
   MGP_HIP_CHECK_LAUNCH();

@@ -18,8 +18,6 @@
 // One wave (= one workgroup) per neighbourhood; phases 0-3 as in mgp_fused_wave.hip (register
 // staged row-walking gather; cyclic difference-form distances among the k rows plus one
 // crosswise distance per lane; covariances exchanged through LDS into row-per-lane registers).
-#include <cstdio>
-#include <cstdlib>
 #include "mgp_wave_common.h"
 
 // issue priorities per phase: covariances / exchange / elimination before the other wave's distances
@@ -1005,23 +1003,10 @@ static int launch_rhs_impl(const FusedArgs& a, hipStream_t stream) {
   size_t lds = (tile_elems + (FOLD ? 4 * NP : W3 ? 2 * NP : NP) + (FOLD ? 2 * NP : NRV * E) + g.dst + (g.dst & 1)) * sizeof(T) + 66 * sizeof(int64_t);
   lds = (lds + 15) & ~(size_t)15;
   static Residency res;
-  int per_cu = 0, cus = 0;
-  const int rc = res.lookup(reinterpret_cast<const void*>(&fused_rhs_kernel<T, RC, BACK, GRAM, W3, FOLD>), 64, lds, &per_cu, &cus);
-  if (rc != MGP_OK) return rc;
-  static const int env_per_cu = getenv("MGP_RHS_PER_CU") ? atoi(getenv("MGP_RHS_PER_CU")) : 0;  // occupancy experiments
-  if (env_per_cu > 0 && env_per_cu < per_cu) per_cu = env_per_cu;
-  static const bool trace = getenv("MGP_TRACE") != nullptr;
-  if (trace)
-    fprintf(stderr, "[mgp] fused_rhs_kernel<%d,%d,%d,%d,%d>: lds %zu B, %d workgroups per CU\n", RC, (int)BACK, (int)GRAM, (int)W3, (int)FOLD, lds, per_cu);
-  int64_t grid = (int64_t)cus * per_cu;
   const int64_t nunits = FOLD ? (g.ntasks + 1) / 2 : g.ntasks;  // (FOLD: a pass of the persistent loop takes two tasks)
-  if (grid > nunits) grid = nunits;
-  hipLaunchKernelGGL((fused_rhs_kernel<T, RC, BACK, GRAM, W3, FOLD>), dim3((unsigned)grid), dim3(64), lds, stream, a, g);
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::fused_rhs_kernel<%s,%d,%s,%s%s>", sizeof(T) == 4 ? "float" : "double", RC, BACK ? "true" : "false",
-              GRAM ? "true" : "false", W3 ? ",w3" : (FOLD ? ",fold" : ""));
-  note_launch_geometry(grid, lds);
-  return MGP_OK;
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_rhs_kernel<%s,%d,%s,%s%s>", sizeof(T) == 4 ? "float" : "double", RC,
+                          BACK ? "true" : "false", GRAM ? "true" : "false", W3 ? ",w3" : (FOLD ? ",fold" : ""));
+  return launch_resident(&fused_rhs_kernel<T, RC, BACK, GRAM, W3, FOLD>, res, 64, lds, nunits, "MGP_RHS_PER_CU", stream, &label, a, g).status;
 }
 
 #ifndef MGP_RHS_GRAM

@@ -29,8 +29,6 @@
 // where the back-substitution reads them column-wise; right-hand side, back-substitution and outputs as in
 // mgp_fused_rhs.hip (prediction variant).
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include "mgp_wave_common.h"
 
 #ifndef MGP_RHS_MF_TIMING
@@ -604,20 +602,9 @@ int launch_fused_rhs_mf(const FusedArgs& a, hipStream_t stream) {
   size_t lds = (tile_elems + 4 * NP + g.dst + (g.dst & 1)) * sizeof(float);
   lds = (lds + 15) & ~(size_t)15;
   static Residency res;
-  int per_cu = 0, cus = 0;
-  const int rc = res.lookup(reinterpret_cast<const void*>(&fused_rhs_mf_kernel<RC>), 64, lds, &per_cu, &cus);
-  if (rc != MGP_OK) return rc;
-  static const int env_per_cu = getenv("MGP_RHS_PER_CU") ? atoi(getenv("MGP_RHS_PER_CU")) : 0;  // occupancy experiments
-  if (env_per_cu > 0 && env_per_cu < per_cu) per_cu = env_per_cu;
-  static const bool trace = getenv("MGP_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "[mgp] fused_rhs_mf_kernel<%d>: lds %zu B, %d workgroups per CU\n", RC, lds, per_cu);
-  int64_t grid = (int64_t)cus * per_cu;
-  if (grid > g.ntasks) grid = g.ntasks;
-  hipLaunchKernelGGL((fused_rhs_mf_kernel<RC>), dim3((unsigned)grid), dim3(64), lds, stream, ak, g);
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::fused_rhs_mf_kernel<%d>%s", RC, packed ? " [prepared tables]" : "");  // (the symbol rocprofv3 lists)
-  note_launch_geometry(grid, lds);
-  return MGP_OK;
+  // (the name: the symbol rocprofv3 lists)
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_rhs_mf_kernel<%d>%s", RC, packed ? " [prepared tables]" : "");
+  return launch_resident(&fused_rhs_mf_kernel<RC>, res, 64, lds, g.ntasks, "MGP_RHS_PER_CU", stream, &label, ak, g).status;
 }
 
 }  // namespace mgp

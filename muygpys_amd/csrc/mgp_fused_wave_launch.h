@@ -6,9 +6,6 @@
 // by the backward launchers (mgp_backward_dlt.hip).
 #pragma once
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <type_traits>
 
 #include "mgp_fused_wave_kernel.h"
 
@@ -145,7 +142,6 @@ inline int wave_grid(int es, int NP, int kfix, bool bwd, int env, bool tree, int
 #endif
   // (fp64, 32 slots, run-time shape: two waves per SIMD although three would fit -- measured, mgp_fused_wave_kernel.h)
   if (es == 8 && NP == 32 && kfix == 0 && per_cu > 8) per_cu = 8;
-  auto env_int = [](const char* name) { return getenv(name) ? atoi(getenv(name)) : 0; };
   static const int env_per_cu[] = {env_int("MGP_WAVE_PER_CU"), env_int("MGP_JIT_PER_CU"), env_int("MGP_BWD_DLT_PER_CU"),
                                    env_int("MGP_BWD_ROW_PER_CU"), 0};
   if (env_per_cu[env] > 0 && env_per_cu[env] < per_cu) per_cu = env_per_cu[env];
@@ -173,25 +169,13 @@ int wave_launch(Kernel fn, Residency& res, const FusedArgs& a, const WaveShape& 
   al.tree.nh = w.nh;
   if (a.tree.mode == kTreeThreeLaunch) al.tree.out = nullptr;  // (the caller walks these leaves by kernels behind the launch)
   auto tf = [](bool v) { return v ? "true" : "false"; };
-  char name[160];
-  snprintf(name, sizeof(name), "mgp::fused_wave_kernel<%s,%d,%d,%d,%d,%s,%s,%s,%s%s>%s", s.es == 4 ? "float" : "double", s.NP, s.kfix, s.rfix,
-           s.dfix, tf(s.piped), tf(s.coeff), tf(s.packed), tf(s.gram), s.bwd ? ",false,backward" : (s.gen64 ? ",gen64" : ""),
-           s.jit ? " [run-time compiled]" : "");
-  static const bool trace = getenv("MGP_TRACE") != nullptr;  // which instantiation served a call
-  if (trace)
-    fprintf(stderr, "mgp: %s b=%lld k=%d d=%d R=%d grid=%lld lds=%zu, %d workgroups per CU\n", name, (long long)a.b, a.k, a.d, a.R,
-            (long long)grid, w.lds, per_cu);
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_wave_kernel<%s,%d,%d,%d,%d,%s,%s,%s,%s%s>%s", s.es == 4 ? "float" : "double", s.NP,
+                          s.kfix, s.rfix, s.dfix, tf(s.piped), tf(s.coeff), tf(s.packed), tf(s.gram),
+                          s.bwd ? ",false,backward" : (s.gen64 ? ",gen64" : ""), s.jit ? " [run-time compiled]" : "");
   void* params[] = {&al, &w.g};
-  if constexpr (std::is_same_v<Kernel, hipFunction_t>) {
-    const hipError_t err = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 64, 1, 1, (unsigned)w.lds, stream, params, nullptr);
-    if (err != hipSuccess) return -(1000 + (int)err);
-  } else {
-    (void)hipLaunchKernel(fn, dim3((unsigned)grid), dim3(64), params, w.lds, stream);
-    MGP_HIP_CHECK_LAUNCH();
-  }
-  note_launch("%s", name);
+  const int lrc = launch_noted(fn, grid, 64, w.lds, per_cu, stream, params, &label);  // (which instantiation served a call)
+  if (lrc != MGP_OK) return lrc;
   if (!s.bwd) note_tree_geometry(a.tree.out ? (int)grid : 0, w.nh);
-  note_launch_geometry(grid, w.lds);
   return MGP_OK;
 }
 

@@ -398,34 +398,15 @@ int launch_fused_wide(const FusedArgs& a, hipStream_t stream) {
     const size_t tile_elems = (size_t)NP * g.xs > TRI ? (size_t)NP * g.xs : TRI;
     size_t lds = (tile_elems + 2 * NP * E + g.dst + 2 * 17 + ((g.dst + 2 * 17) & 1)) * sizeof(float) + NP * sizeof(int64_t);
     lds = (lds + 15) & ~(size_t)15;
-    const void* fn = nullptr;
     static Residency res[8];
-    int ri = 0;
+    const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_wide_kernel<%d>", ng);
     switch (ng) {
-#define MGP_WIDE_CASE(N, I) case N: fn = reinterpret_cast<const void*>(&fused_wide_kernel<N>); ri = I; break;
+#define MGP_WIDE_CASE(N, I) case N: return launch_resident(&fused_wide_kernel<N>, res[I], NP, lds, a.b, nullptr, stream, &label, a, g).status;
       MGP_WIDE_CASE(17, 0) MGP_WIDE_CASE(20, 1) MGP_WIDE_CASE(22, 2) MGP_WIDE_CASE(24, 3)
       MGP_WIDE_CASE(26, 4) MGP_WIDE_CASE(28, 5) MGP_WIDE_CASE(30, 6)
-      default: fn = reinterpret_cast<const void*>(&fused_wide_kernel<32>); ri = 7; break;
+      default: MGP_WIDE_CASE(32, 7)
 #undef MGP_WIDE_CASE
     }
-    int per_cu = 0, cus = 0;
-    const int rc = res[ri].lookup(fn, NP, lds, &per_cu, &cus);
-    if (rc != MGP_OK) return rc;
-    int64_t grid = (int64_t)cus * per_cu;
-    if (grid > a.b) grid = a.b;
-    static const bool trace = getenv("MGP_TRACE") != nullptr;
-    if (trace)
-      fprintf(stderr, "mgp: fused_wide_kernel b=%lld k=%d d=%d R=%d grid=%lld lds=%zu per_cu=%d\n", (long long)a.b, a.k, a.d,
-              a.R, (long long)grid, lds, per_cu);
-    void* kargs[] = {const_cast<FusedArgs*>(&a), &g};
-    {
-      const hipError_t le = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(NP), kargs, lds, stream);
-      if (le != hipSuccess) return -(1000 + (int)le);
-    }
-    MGP_HIP_CHECK_LAUNCH();
-    note_launch("mgp::fused_wide_kernel<%d>", ng);
-    note_launch_geometry(grid, lds);
-    return MGP_OK;
   }
 }
 

@@ -5,6 +5,7 @@
 // (see mgp_lds_factor.h).  The specialised register-resident kernels in mgp_fused_wave.hip
 // take over for the shapes they cover; this file is the path for everything else.
 #include "mgp_args.h"
+#include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
 namespace mgp {
@@ -173,9 +174,6 @@ __global__ void solve_generic_kernel(SolveArgs a) {
   }
 }
 
-static int block_threads(int rows) { return rows <= 64 ? 64 : 256; }
-static const size_t kMaxLds = 160 * 1024;
-
 template <typename T>
 static size_t fused_lds_bytes(int k, int R, int dc) {
   const int rows = k + 1 + R, SP = lds_row_stride<T>(k);
@@ -190,54 +188,23 @@ static size_t solve_lds_bytes(int k, int R) {
   return (n + 15) & ~(size_t)15;
 }
 
-static int grid_for(int64_t b, size_t lds) {
-  // Persistent grid = the resident capacity (the kernels grid-stride over the rest): LDS is handed
-  // out in 1280-byte granules of the CU's 160 KiB (measured, see mgp_fused_wave.hip); one workgroup
-  // more than fits would run as a second, nearly empty round.
-  const size_t granules = (lds + 1279) / 1280;
-  int per_cu = (int)(kMaxLds / ((granules ? granules : 1) * 1280));
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 16) per_cu = 16;
-  int64_t g = 256LL * per_cu;
-  return (int)(b < g ? b : g);
-}
-
+// (at most 16 workgroups per CU: mgp_launch.h, capacity_grid)
 template <typename T>
 int launch_fused_generic(const FusedArgs& in, hipStream_t stream) {
   FusedArgs a = in;
   // feature chunk: as wide as fits next to the factor (bounded so small problems stay small)
-  // feature chunk: a multiple of 8 (whole 16-byte pieces, odd slot count with the pad), as wide as fits
-  int dc = a.d < 64 ? (a.d + 7) / 8 * 8 : 64;
-  while (dc > 8 && fused_lds_bytes<T>(a.k, a.R, dc) > kMaxLds) dc -= 8;
-  const size_t lds = fused_lds_bytes<T>(a.k, a.R, dc);
-  if (lds > kMaxLds) return MGP_EUNSUPPORTED;
-  a.dc = dc;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_generic_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(1000 + (int)e);
-  }
-  const int grid = grid_for(a.b, lds);
-  hipLaunchKernelGGL(fused_generic_kernel<T>, dim3(grid), dim3(block_threads(a.k + 1 + a.R)), lds, stream, a);
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::fused_generic_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
-  note_launch_geometry(grid, lds);
-  return MGP_OK;
+  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, a.R, dc); });
+  if (!fc.fits) return MGP_EUNSUPPORTED;
+  a.dc = fc.dc;
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return launch_capacity(&fused_generic_kernel<T>, lds_factor_threads(a.k + 1 + a.R), fc.lds, a.b, Capacity{16}, stream, &label, a).status;
 }
 
 template <typename T>
 int launch_solve_generic(const SolveArgs& a, hipStream_t stream) {
   const size_t lds = solve_lds_bytes<T>(a.k, a.R);
-  if (lds > kMaxLds) return MGP_EUNSUPPORTED;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_generic_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(1000 + (int)e);
-  }
-  hipLaunchKernelGGL(solve_generic_kernel<T>, dim3(grid_for(a.b, lds)), dim3(block_threads(a.k + 1 + a.R)), lds,
-                     stream, a);
-  MGP_HIP_CHECK_LAUNCH();
-  return MGP_OK;
+  if (lds > kCuLdsBytes) return MGP_EUNSUPPORTED;
+  return launch_capacity(&solve_generic_kernel<T>, lds_factor_threads(a.k + 1 + a.R), lds, a.b, Capacity{16}, stream, nullptr, a).status;
 }
 
 template int launch_fused_generic<float>(const FusedArgs&, hipStream_t);
@@ -246,13 +213,7 @@ template int launch_solve_generic<float>(const SolveArgs&, hipStream_t);
 template int launch_solve_generic<double>(const SolveArgs&, hipStream_t);
 
 int max_nn_count(int elem_size, int R) {
-  int k = 1;
-  while (true) {
-    const size_t lds = elem_size == 4 ? fused_lds_bytes<float>(k + 1, R, 8) : fused_lds_bytes<double>(k + 1, R, 8);
-    if (lds > kMaxLds) break;
-    ++k;
-  }
-  return k;
+  return largest_k([&](int k) { return (elem_size == 4 ? fused_lds_bytes<float>(k, R, 8) : fused_lds_bytes<double>(k, R, 8)) <= kCuLdsBytes; });
 }
 
 }  // namespace mgp

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "mgp_args.h"
+#include "mgp_launch.h"
 
 namespace mgp {
 
@@ -106,7 +107,7 @@ struct Env {
     src_dir = s && *s ? s : lib + "/../csrc";
     const char* c = getenv("MUYGPYS_HIP_JIT_CACHE");
     cache_dir = c && *c ? c : lib + "/jit";
-    trace = getenv("MGP_TRACE") != nullptr;
+    trace = trace_enabled();
     uint64_t h = 1469598103934665603ull;
     sources_ok = true;
     for (const char* name : kSources) {

@@ -209,7 +209,9 @@ __global__ void __launch_bounds__(512) solve_large_kernel(SolveArgs a, T* worksp
   }
 }
 
-// (kMaxLds, kMaxWorkspace, kCuCount / kMaxPerCu and block_threads: mgp_large_factor.h, shared with the backward)
+// (kMaxWorkspace, kMaxPerCu, slab_count and slab_block_threads: mgp_large_factor.h, shared with the backward; the LDS of
+// a CU, the feature chunk and the grid -- one workgroup per slab of the workspace, at most the resident capacity, at most
+// b: mgp_launch.h)
 
 template <typename T>
 static size_t fused_lds_bytes(int k, int dc) {
@@ -228,21 +230,8 @@ int64_t large_slab_bytes(int elem_size, int k, int R) {
 }
 
 int64_t large_workspace_bytes(int elem_size, int k, int R, int64_t b) {
-  const int64_t slab = large_slab_bytes(elem_size, k, R);
-  int64_t n = b < 1 ? 1 : b;
-  if (n > kCuCount * kMaxPerCu) n = kCuCount * kMaxPerCu;
+  const int64_t slab = large_slab_bytes(elem_size, k, R), n = slab_count(b);
   return n * slab > kMaxWorkspace ? kMaxWorkspace : n * slab;
-}
-
-// persistent grid: one workgroup per slab of the workspace, at most the resident capacity, at most b
-static int grid_for(int64_t b, int64_t slabs, size_t lds) {
-  const size_t granules = (lds + 1279) / 1280;  // (LDS is handed out in 1280-byte granules: mgp_generic.hip)
-  int per_cu = (int)(kMaxLds / ((granules ? granules : 1) * 1280));
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > kMaxPerCu) per_cu = kMaxPerCu;
-  int64_t g = (int64_t)kCuCount * per_cu;
-  if (g > slabs) g = slabs;
-  return (int)(b < g ? b : g);
 }
 
 template <typename T>
@@ -254,22 +243,12 @@ int launch_fused_large(const FusedArgs& in, void* workspace, int64_t workspace_b
   // feature chunk: a multiple of 8, as wide as fits the CU's LDS (one workgroup per CU: nothing to share it with; every
   // further chunk is one more pass over the slab's triangle: at k = 1000, d = 40 five chunks of 8 cost as much as
   // the factorisation), at least 8
-  int dc = a.d < 64 ? (a.d + 7) / 8 * 8 : 64;
-  while (dc > 8 && fused_lds_bytes<T>(a.k, dc) > kMaxLds) dc -= 8;
-  const size_t lds = fused_lds_bytes<T>(a.k, dc);
-  if (lds > kMaxLds) return MGP_EUNSUPPORTED;
-  a.dc = dc;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fused_large_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(1000 + (int)e);
-  }
-  const int grid = grid_for(a.b, workspace_bytes / slab, lds);
-  hipLaunchKernelGGL(fused_large_kernel<T>, dim3(grid), dim3(block_threads((int)rows)), lds, stream, a,
-                     static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)));
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::fused_large_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
-  return MGP_OK;
+  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, dc); });
+  if (!fc.fits) return MGP_EUNSUPPORTED;
+  a.dc = fc.dc;
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return launch_capacity(&fused_large_kernel<T>, slab_block_threads((int)rows), fc.lds, a.b, Capacity{kMaxPerCu, workspace_bytes / slab}, stream,
+                         &label, a, static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T))).status;
 }
 
 template <typename T>
@@ -278,11 +257,8 @@ int launch_solve_large(const SolveArgs& a, void* workspace, int64_t workspace_by
   if (rows > kLargeMaxRows) return MGP_EUNSUPPORTED;
   const int64_t slab = large_slab_bytes(sizeof(T), a.k, a.R);
   const size_t lds = (size_t)LNB * large_lp<T>() * sizeof(T);
-  const int grid = grid_for(a.b, workspace_bytes / slab, lds);
-  hipLaunchKernelGGL(solve_large_kernel<T>, dim3(grid), dim3(block_threads((int)rows)), lds, stream, a,
-                     static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)));
-  MGP_HIP_CHECK_LAUNCH();
-  return MGP_OK;
+  return launch_capacity(&solve_large_kernel<T>, slab_block_threads((int)rows), lds, a.b, Capacity{kMaxPerCu, workspace_bytes / slab}, stream,
+                         nullptr, a, static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T))).status;
 }
 
 template int launch_fused_large<float>(const FusedArgs&, void*, int64_t, hipStream_t);

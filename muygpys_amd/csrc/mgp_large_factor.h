@@ -8,6 +8,7 @@
 #pragma once
 
 #include "mgp_args.h"
+#include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
 namespace mgp {
@@ -27,12 +28,13 @@ __host__ __device__ inline int large_slab_elems(int k, int R) { return large_row
 template <typename T>
 __host__ __device__ constexpr int large_lp() { return LNB + 16 / (int)sizeof(T); }
 
-// launch rules of every kernel on a slab: the LDS of a CU, the cap of a recommended workspace, one workgroup per CU
-// (104 - 217 registers at 512 threads), 256 threads up to 128 rows and 512 above
-static const size_t kMaxLds = 160 * 1024;
+// launch rules of every kernel on a slab (the rest: mgp_launch.h): the cap of a recommended workspace, one workgroup per
+// CU (104 - 217 registers at 512 threads), 256 threads up to 128 rows and 512 above
 static const int64_t kMaxWorkspace = 512LL << 20;
-static const int kCuCount = 256, kMaxPerCu = 1;
-static inline int block_threads(int rows) { return rows <= 128 ? 256 : 512; }
+static const int kMaxPerCu = 1;
+static inline int slab_block_threads(int rows) { return rows <= 128 ? 256 : 512; }
+// the slabs worth recommending for b systems: one per workgroup of a full grid
+static inline int64_t slab_count(int64_t b) { return capacity_grid(b < 1 ? 1 : b, 0, Capacity{kMaxPerCu}); }
 
 // p -> (row, col) of the strict lower triangle of the (k+1)-point set (8 p + 1 is an exact float for every p here,
 // p < 2^20; the two loops settle the last unit)

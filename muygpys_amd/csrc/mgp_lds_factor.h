@@ -31,6 +31,9 @@ __host__ __device__ inline int lds_row_stride(int k) {
   return slots * E;
 }
 
+// threads of a workgroup that factors `rows` rows here: one wave while every row has a lane, four beyond
+inline int lds_factor_threads(int rows) { return rows <= 64 ? 64 : 256; }
+
 template <typename T> struct lds_vec;
 template <> struct lds_vec<float> { typedef float type __attribute__((ext_vector_type(4))); };
 template <> struct lds_vec<double> { typedef double type __attribute__((ext_vector_type(2))); };

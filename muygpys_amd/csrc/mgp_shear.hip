@@ -13,6 +13,7 @@
 // n elimination steps of factor_augmented_rows leave K_c^T K^-1 K_c, the 3 means and y^T K^-1 y as
 // inner products of the trailing rows (emit_block_outputs): no back-substitution.
 #include "mgp_args.h"
+#include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
 namespace mgp {
@@ -215,28 +216,6 @@ __global__ void __launch_bounds__(256) shear_posterior_kernel(ShearArgs a) {
   }
 }
 
-static const size_t kShearMaxLds = 160 * 1024;
-
-static int shear_block_threads(int rows) { return rows <= 64 ? 64 : 256; }
-
-static int shear_grid_for(int64_t b, size_t lds) {
-  // persistent grid sized to residency (as grid_for in mgp_generic.hip): LDS goes in 1280-byte granules
-  const size_t granules = (lds + 1279) / 1280;
-  int per_cu = (int)(kShearMaxLds / ((granules ? granules : 1) * 1280));
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 16) per_cu = 16;
-  const int64_t g = 256LL * per_cu;
-  return (int)(b < g ? b : g);
-}
-
-template <typename K>
-static int allow_lds(K kernel, size_t lds) {
-  if (lds <= 64 * 1024) return MGP_OK;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  return e == hipSuccess ? MGP_OK : -(1000 + (int)e);
-}
-
 template <typename T>
 int launch_shear_tensor(const T* diffs, int64_t G, int n, int m, int variant, double ell, T* out, hipStream_t stream) {
   const int64_t total = G * n * m;
@@ -253,19 +232,14 @@ int launch_shear_tensor(const T* diffs, int64_t G, int n, int m, int variant, do
   return MGP_OK;
 }
 
+// (the persistent kernels: at most 16 workgroups per CU, as the workgroup kernels of mgp_generic.hip)
 template <typename T>
 int launch_solve_multi(const SolveMultiArgs& a, hipStream_t stream) {
   if ((int64_t)a.n + a.m + a.R > 4096) return MGP_EUNSUPPORTED;
   const size_t lds = solve_multi_lds_bytes<T>(a.n, a.m, a.R);
-  if (lds > kShearMaxLds) return MGP_EUNSUPPORTED;
-  int rc = allow_lds(&solve_multi_kernel<T>, lds);
-  if (rc != MGP_OK) return rc;
-  const int grid = shear_grid_for(a.b, lds);
-  hipLaunchKernelGGL(solve_multi_kernel<T>, dim3(grid), dim3(shear_block_threads(a.n + a.m + a.R)), lds, stream, a);
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::solve_multi_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
-  note_launch_geometry(grid, lds);
-  return MGP_OK;
+  if (lds > kCuLdsBytes) return MGP_EUNSUPPORTED;
+  const LaunchLabel label(a.b, a.n, -1, a.R, "mgp::solve_multi_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return launch_capacity(&solve_multi_kernel<T>, lds_factor_threads(a.n + a.m + a.R), lds, a.b, Capacity{16}, stream, &label, a).status;
 }
 
 template <typename T>
@@ -273,29 +247,14 @@ int launch_shear_posterior(const ShearArgs& a, hipStream_t stream) {
   // (sizing is O(rows) host work per call; a packed system of more than 4096 rows is tens of MB: refused outright)
   if ((int64_t)a.k * a.in_count > 4096) return MGP_EUNSUPPORTED;
   const size_t lds = shear_lds_bytes<T>(a.k, a.in_count);
-  if (lds > kShearMaxLds) return MGP_EUNSUPPORTED;
-  const int grid = shear_grid_for(a.b, lds), NT = shear_block_threads(a.in_count * a.k + 4);
-  const char* t = sizeof(T) == 4 ? "float" : "double";
-  int rc;
-  if (a.in_count == 3) {
-    if ((rc = allow_lds(&shear_posterior_kernel<T, 3>, lds)) != MGP_OK) return rc;
-    hipLaunchKernelGGL((shear_posterior_kernel<T, 3>), dim3(grid), dim3(NT), lds, stream, a);
-  } else {
-    if ((rc = allow_lds(&shear_posterior_kernel<T, 2>, lds)) != MGP_OK) return rc;
-    hipLaunchKernelGGL((shear_posterior_kernel<T, 2>), dim3(grid), dim3(NT), lds, stream, a);
-  }
-  MGP_HIP_CHECK_LAUNCH();
-  note_launch("mgp::shear_posterior_kernel<%s,%d>", t, a.in_count);
-  note_launch_geometry(grid, lds);
-  return MGP_OK;
+  if (lds > kCuLdsBytes) return MGP_EUNSUPPORTED;
+  const LaunchLabel label(a.b, a.k, -1, -1, "mgp::shear_posterior_kernel<%s,%d>", sizeof(T) == 4 ? "float" : "double", a.in_count);
+  const auto kernel = a.in_count == 3 ? &shear_posterior_kernel<T, 3> : &shear_posterior_kernel<T, 2>;
+  return launch_capacity(kernel, lds_factor_threads(a.in_count * a.k + 4), lds, a.b, Capacity{16}, stream, &label, a).status;
 }
 
 int shear_max_nn_count(int elem_size, int in_count) {
-  int k = 1;
-  while ((elem_size == 4 ? shear_lds_bytes<float>(k + 1, in_count) : shear_lds_bytes<double>(k + 1, in_count)) <=
-         kShearMaxLds)
-    ++k;
-  return k;
+  return largest_k([&](int k) { return (elem_size == 4 ? shear_lds_bytes<float>(k, in_count) : shear_lds_bytes<double>(k, in_count)) <= kCuLdsBytes; });
 }
 
 template int launch_shear_tensor<float>(const float*, int64_t, int, int, int, double, float*, hipStream_t);

@@ -189,15 +189,7 @@ static int launch_solve_np(const SolveArgs& a, hipStream_t stream) {
   const uintptr_t base = reinterpret_cast<uintptr_t>(a.Kin);
   const int vec_ok = (row_bytes % 16 == 0 && base % 16 == 0) ? 2 : ((row_bytes % 8 == 0 && base % 8 == 0) ? 1 : 0);
   static Residency res;
-  int per_cu = 0, cus = 0;
-  const int rc = res.lookup(reinterpret_cast<const void*>(&solve_wave_kernel<T, NP>), 64, 0, &per_cu, &cus);
-  if (rc != MGP_OK) return rc;
-  const int64_t ntasks = (a.b + NH - 1) / NH;
-  int64_t grid = (int64_t)cus * per_cu;
-  if (grid > ntasks) grid = ntasks;
-  hipLaunchKernelGGL((solve_wave_kernel<T, NP>), dim3((unsigned)grid), dim3(64), 0, stream, a, q, vec_ok);
-  MGP_HIP_CHECK_LAUNCH();
-  return MGP_OK;
+  return launch_resident(&solve_wave_kernel<T, NP>, res, 64, 0, (a.b + NH - 1) / NH, nullptr, stream, nullptr, a, q, vec_ok).status;
 }
 
 template <typename T>

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "mgp_device.h"
+#include "mgp_launch.h"
 #include "mgp_loocv_tree.h"
 
 namespace mgp {
@@ -13,7 +14,7 @@ static const int kBlock = 256;
 
 static inline int grid_1d(int64_t n) {
   int64_t g = ceil_div(n, kBlock);
-  const int64_t cap = 256LL * 32;  // 256 CUs x 32 resident waves; grid-stride beyond
+  const int64_t cap = kAssumedCus * 32;  // 32 resident waves per CU; grid-stride beyond
   return (int)(g < cap ? (g < 1 ? 1 : g) : cap);
 }
 
@@ -585,15 +586,13 @@ int launch_pairwise_dists(const T* f, int d, const int64_t* ni, int64_t b, int k
     constexpr int E = 16 / (int)sizeof(T);
     const int vec_ok = (d % E == 0) && (reinterpret_cast<uintptr_t>(f) % 16 == 0);
     const int dg = (d + E - 1) / E;  // 16-byte groups per row
+    int rc = MGP_OK;
     auto go = [&](auto npc, auto dgc) {
       constexpr int NP = decltype(npc)::value, DG = decltype(dgc)::value;
       const size_t lds = (size_t)64 * (DG * E + E) * sizeof(T);
       const int64_t ntasks = (b + 64 / NP - 1) / (64 / NP);
-      int64_t g = 256LL * (int64_t)((160 * 1024) / (((lds + 1279) / 1280) * 1280));
-      if (g > 256LL * 16) g = 256LL * 16;
-      if (g > ntasks) g = ntasks;
-      hipLaunchKernelGGL((pairwise_dists_wave_kernel<T, NP, DG>), dim3((unsigned)g), dim3(64), lds, s, f, d, ni, b, k, metric,
-                         out, vec_ok);
+      rc = launch_capacity(&pairwise_dists_wave_kernel<T, NP, DG>, 64, lds, ntasks, Capacity{16}, s, nullptr, f, d, ni, b, k, metric, out,
+                           vec_ok).status;
     };
     constexpr int G16 = 16 / E * 1;  // groups per 16 features: 4 (fp32) / 8 (fp64)
     const int steps = (dg + G16 - 1) / G16;  // 1 .. 4 blocks of 16 features
@@ -608,17 +607,11 @@ int launch_pairwise_dists(const T* f, int d, const int64_t* ni, int64_t b, int k
       else if (steps == 3) go(icn<64>{}, icn<3 * G16>{});
       else go(icn<64>{}, icn<4 * G16>{});
     }
-    MGP_HIP_CHECK_LAUNCH();
-    return MGP_OK;
+    return rc;
   }
   const size_t lds = (size_t)k * (d | 1) * sizeof(T);
   if (lds <= 40 * 1024) {  // the neighbourhood's rows fit LDS: gather them once
-    const int64_t cap = 256LL * (lds ? (int64_t)((160 * 1024) / (((lds + 1279) / 1280) * 1280)) : 32);
-    int64_t g = cap < 256LL * 32 ? cap : 256LL * 32;
-    if (g > b) g = b;
-    hipLaunchKernelGGL(pairwise_dists_tile_kernel<T>, dim3((unsigned)g), dim3(64), lds, s, f, d, ni, b, k, metric, out);
-    MGP_HIP_CHECK_LAUNCH();
-    return MGP_OK;
+    return launch_capacity(&pairwise_dists_tile_kernel<T>, 64, lds, b, Capacity{32}, s, nullptr, f, d, ni, b, k, metric, out).status;
   }
   hipLaunchKernelGGL(pairwise_dists_kernel<T>, dim3(grid_1d(b * k * k)), dim3(kBlock), 0, s, f, d, ni, b, k, metric,
                      out);
