@@ -192,9 +192,14 @@ int64_t mgp_packed_row_bytes(int d, int R, int elem_size);
  * packed_* NULL) or prepared tables (packed_q / packed_nn with strides; feat_* NULL), responses from the
  * table or already gathered (targets_batch != 0: targets = (b, k, R)).  The covariance is evaluated inside
  * the fused kernel (trapezoidal rule on the integral representation of K_nu, csrc/mgp_wave_common.h), so a
- * free-smoothness objective evaluation is ONE launch with nothing materialised.  fp32 tables,
- * k + 1 + R <= 32 or a shape the static kernels serve, nu <= 30; MGP_EUNSUPPORTED otherwise (the caller
- * falls back to mgp_*_dists_* + mgp_matern_gen_* + mgp_solve_*).
+ * free-smoothness objective evaluation is ONE launch with nothing materialised.  nu <= 30 throughout.
+ *   Up to 64 slots (k + 1 + R <= 64), either table form: the wave kernels -- fp32 with k + 1 + R <= 32 or a
+ *       shape the static kernels serve, fp64 on the static shapes; MGP_EUNSUPPORTED otherwise.
+ *   Beyond 64 slots, plain tables: the general-smoothness instantiation of the LDS workgroup kernel, for every
+ *       k up to mgp_max_nn_count_gen (any d >= 1, any R that fits, both float widths); MGP_EUNSUPPORTED only
+ *       where the system does not fit LDS next to the node table -- mgp_posterior_gen_large_* serves those.
+ *   Beyond 64 slots, prepared tables: MGP_EUNSUPPORTED.
+ * Where every entry refuses, the caller falls back to mgp_*_dists_* + mgp_matern_gen_* + mgp_solve_*.
  * ------------------------------------------------------------------------- */
 int mgp_posterior_gen_f32(const float* feat_q, const float* feat_nn, const void* packed_q, int64_t q_stride_bytes,
                           const void* packed_nn, int64_t nn_stride_bytes, int d,
@@ -210,6 +215,53 @@ int mgp_posterior_gen_f64(const double* feat_q, const double* feat_nn, const voi
                           int noise_mode, double noise_scalar, const double* noise_dev,
                           double smoothness, int metric_id, const double* length_scale, int ls_count,
                           double* mean, double* var, double* ykinvy, int* info, void* stream);
+
+/* The general-smoothness Matern (K3, _matern_gen_fn, _src/gp/kernels/numpy.py:34-43) on the two workgroup kernel
+ * families by name: what mgp_posterior_generic_* and mgp_posterior_large_* are to the closed-form kernels (see there
+ * for T1-T4, D1/D2, N1/N2, S1-S3), with `smoothness` in place of kernel_id.  Plain tables only; targets_batch != 0:
+ * `targets` is the gathered (b, k, R) tensor.  The covariance phase hands every thread of the workgroup the same
+ * number of pairs by a map that depends on k and the workgroup size alone, so a neighbourhood's bits do not depend
+ * on its place in the batch, the batch size, the grid or the workspace.
+ *   mgp_posterior_gen_generic_*: the system in LDS, the node table of the trapezoidal rule behind it; any k >= 1
+ *       that fits (tests and A/B timing, like mgp_posterior_generic_*; mgp_posterior_gen_* reaches the same kernel
+ *       beyond 64 slots).
+ *   mgp_posterior_gen_large_*: the system in a slab of `workspace`; every k >= 1 with k + 1 + R <= 1024.  Workspace
+ *       contract of mgp_posterior_large_* (mgp_large_workspace_bytes; any workspace of at least one slab gives the
+ *       same bits).
+ *   mgp_max_nn_count_gen: the largest k at which the LDS kernel fits with an 8-feature chunk -- below
+ *       mgp_max_nn_count by what the node table costs (1 KiB fp32, 4 KiB fp64); -1 for an elem_size that is not
+ *       4 or 8.
+ *   Order of the checks, all before any HIP call: sizes and a smoothness that is not > 0 (NaN included:
+ *   MGP_EINVAL), the empty batch (MGP_OK, nothing else looked at), pointers, ids and -- the large entry -- the
+ *   workspace (NULL, misaligned, less than one slab: MGP_EINVAL), then smoothness > 30, k + 1 + R > 1024 or a system
+ *   that does not fit LDS: MGP_EUNSUPPORTED. */
+int mgp_max_nn_count_gen(int elem_size, int response_count);
+int mgp_posterior_gen_generic_f32(const float* feat_q, const float* feat_nn, int d,
+                                  const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                  const float* targets, int R, int targets_batch,
+                                  int noise_mode, double noise_scalar, const float* noise_dev,
+                                  double smoothness, int metric_id, const float* length_scale, int ls_count,
+                                  float* mean, float* var, float* ykinvy, int* info, void* stream);
+int mgp_posterior_gen_generic_f64(const double* feat_q, const double* feat_nn, int d,
+                                  const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                  const double* targets, int R, int targets_batch,
+                                  int noise_mode, double noise_scalar, const double* noise_dev,
+                                  double smoothness, int metric_id, const double* length_scale, int ls_count,
+                                  double* mean, double* var, double* ykinvy, int* info, void* stream);
+int mgp_posterior_gen_large_f32(const float* feat_q, const float* feat_nn, int d,
+                                const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                const float* targets, int R, int targets_batch,
+                                int noise_mode, double noise_scalar, const float* noise_dev,
+                                double smoothness, int metric_id, const float* length_scale, int ls_count,
+                                float* mean, float* var, float* ykinvy, int* info,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_posterior_gen_large_f64(const double* feat_q, const double* feat_nn, int d,
+                                const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                const double* targets, int R, int targets_batch,
+                                int noise_mode, double noise_scalar, const double* noise_dev,
+                                double smoothness, int metric_id, const double* length_scale, int ls_count,
+                                double* mean, double* var, double* ykinvy, int* info,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Run-time specialisation.  mgp_posterior_* / mgp_loocv_* serve a shape (k, R, d) with a kernel whose

@@ -56,6 +56,9 @@ PER_FILE_FLAGS = {
     "mgp_knn_cells.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the blocked factorisation beyond LDS: a 32 x 32 diagonal block and a panel row sit in registers)
     "mgp_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the LDS workgroup kernels, whose general-smoothness instantiations carry the Bessel evaluator:
+    # tests/test_gen_beyond64_cpu.py reads their records)
+    "mgp_generic.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the hyper-parameter backward on the same factor)
     "mgp_backward_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the whole vector-Jacobian product there: tests/test_large_full_backward_status_cpu.py reads the record)

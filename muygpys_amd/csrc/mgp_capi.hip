@@ -4,6 +4,7 @@
 #include <cstdio>
 
 #include "mgp_args.h"
+#include "mgp_gen_launch.h"
 
 #include <cstdarg>
 #include <cstring>
@@ -302,13 +303,17 @@ int loocv_finish(int rc, bool served, const LoocvTree& tr, const T* mean, const 
 using namespace mgp;
 #define S_(x) static_cast<hipStream_t>(x)
 
-// General-smoothness Matern through the fused wave kernels (fp32, k + 1 + R <= 32 or a static shape);
-// MGP_EUNSUPPORTED elsewhere: the caller evaluates mgp_matern_gen_* on materialised distances instead.
+// General-smoothness Matern, evaluated inside the fused launch.  Up to 64 slots (k + 1 + R): the wave kernels (fp32:
+// k + 1 + R <= 32 or a static shape; fp64: the static shapes) or MGP_EUNSUPPORTED, on either table form.  Beyond 64
+// slots, plain tables: the general-smoothness instantiation of the LDS workgroup kernel (mgp_generic.hip) wherever it
+// fits LDS with its node table; MGP_EUNSUPPORTED where it does not (the caller goes on to mgp_posterior_gen_large_*)
+// and for prepared tables.  Where everything refuses the caller evaluates mgp_matern_gen_* on materialised distances.
 template <typename T>
 static int posterior_gen(const T* fq, const T* fn, const void* packed_q, int64_t q_stride, const void* packed_nn,
                          int64_t nn_stride, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
                          int R, int targets_batch, int noise_mode, double eps, const T* nd, double smoothness,
-                         int metric_id, const T* ls, int ls_count, T* mean, T* var, T* yk, int* info, void* stream) {
+                         int metric_id, const T* ls, int ls_count, T* mean, T* var, T* yk, int* info, void* stream,
+                         int path = PATH_AUTO) {
   if (!(smoothness > 0.0)) return MGP_EINVAL;  // (in front of the empty-batch return, like the sizes)
   FusedArgs a;
   const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_IS_GEN, fq, fn, d, bi, ni, b, k, tg, R,
@@ -317,7 +322,29 @@ static int posterior_gen(const T* fq, const T* fn, const void* packed_q, int64_t
   if (ready != ARGS_READY) return ready;
   if (smoothness > 30.0) return MGP_EUNSUPPORTED;  // beyond nu = 30 the RBF limit is the better model anyway
   a.smoothness = smoothness;
-  return launch_fused_wave<T>(a, static_cast<hipStream_t>(stream));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (path == PATH_GENERIC) return launch_fused_generic_gen<T>(a, s);  // (mgp_posterior_gen_generic_*: the family by name)
+  // (beyond their 64 slots the wave kernels refuse every shape: on the plain tables the LDS workgroup kernel is next)
+  if (packed_nn || (int64_t)k + 1 + R <= 64) return launch_fused_wave<T>(a, s);
+  return launch_fused_generic_gen<T>(a, s);
+}
+
+// ... and on the slab factor beyond LDS (mgp_large.hip): the checks of posterior_large, then the smoothness limit
+template <typename T>
+static int posterior_gen_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                               const T* tg, int R, int targets_batch, int noise_mode, double eps, const T* nd,
+                               double smoothness, int metric_id, const T* ls, int ls_count, T* mean, T* var, T* yk,
+                               int* info, void* ws, int64_t ws_bytes, void* stream) {
+  if (!(smoothness > 0.0)) return MGP_EINVAL;
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_IS_GEN, fq, fn, d, bi, ni, b, k, tg, R,
+                                  noise_mode, eps, nd, MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, mean, var, yk,
+                                  info, nullptr, 0, nullptr, 0, targets_batch != 0);
+  if (ready != ARGS_READY) return ready;
+  if (!valid_workspace(ws, ws_bytes, sizeof(T), k, R)) return MGP_EINVAL;
+  if (smoothness > 30.0) return MGP_EUNSUPPORTED;
+  a.smoothness = smoothness;
+  return launch_fused_large_gen<T>(a, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses rows > 1024)
 }
 
 template <typename T>
@@ -355,6 +382,10 @@ extern "C" {
 
 const char* mgp_version(void) { return "muygpys_amd-hip 0.1 (gfx950)"; }
 int mgp_max_nn_count(int elem_size, int R) { return max_nn_count(elem_size, R); }
+int mgp_max_nn_count_gen(int elem_size, int R) {
+  if ((elem_size != 4 && elem_size != 8) || R < 0) return MGP_EINVAL;
+  return max_nn_count_gen(elem_size, R);
+}
 int mgp_reduce_scratch_doubles(void) { return reduce_scratch_doubles(); }
 int64_t mgp_loocv_scratch_bytes(void) { return tree_scratch_bytes(); }
 int64_t mgp_loocv_scratch_zero_bytes(void) { return tree_zero_bytes(); }
@@ -492,6 +523,20 @@ int mgp_posterior_f64(const double* fq, const double* fn, int d, const int64_t* 
                               T* yk, int* info, void* st) {                                                          \
     return posterior_gen<T>(fq, fn, packed_q, q_stride, packed_nn, nn_stride, d, bi, ni, b, k, tg, R, targets_batch, \
                             nm, eps, nd, smoothness, mid, ls, lsc, mean, var, yk, info, st);                         \
+  }                                                                                                                  \
+  int mgp_posterior_gen_generic_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,         \
+                                      int64_t b, int k, const T* tg, int R, int targets_batch, int nm, double eps,   \
+                                      const T* nd, double smoothness, int mid, const T* ls, int lsc, T* mean,        \
+                                      T* var, T* yk, int* info, void* st) {                                          \
+    return posterior_gen<T>(fq, fn, nullptr, 0, nullptr, 0, d, bi, ni, b, k, tg, R, targets_batch != 0, nm, eps, nd, \
+                            smoothness, mid, ls, lsc, mean, var, yk, info, st, PATH_GENERIC);                        \
+  }                                                                                                                  \
+  int mgp_posterior_gen_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,           \
+                                    int64_t b, int k, const T* tg, int R, int targets_batch, int nm, double eps,     \
+                                    const T* nd, double smoothness, int mid, const T* ls, int lsc, T* mean, T* var,  \
+                                    T* yk, int* info, void* workspace, int64_t workspace_bytes, void* st) {          \
+    return posterior_gen_large<T>(fq, fn, d, bi, ni, b, k, tg, R, targets_batch, nm, eps, nd, smoothness, mid, ls,   \
+                                  lsc, mean, var, yk, info, workspace, workspace_bytes, st);                         \
   }                                                                                                                  \
   int mgp_loocv_##SUF(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,     \
                       int nm, double eps, const T* nd, int kid, int mid, const T* ls, int lsc, T* mean, T* var,      \

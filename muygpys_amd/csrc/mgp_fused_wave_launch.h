@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "mgp_fused_wave_kernel.h"
+#include "mgp_gen_launch.h"
 
 namespace mgp {
 
@@ -102,21 +103,17 @@ inline WaveLaunch wave_geometry(const FusedArgs& a, const WaveShape& s) {
   lds = (lds + 15) & ~(size_t)15;
   // general-smoothness Matern: the node table (2 x MGP_GEN_NODES floats) goes behind everything else in LDS; spacing and
   // the log2 of h 2^(1-nu)/Gamma(nu) are launch constants.  (The backward serves no such kernel and reserves nothing.)
+  // (the constants and the table's size: gen_launch_constants / gen_table_bytes, shared with the workgroup families)
   g.gen_h = 0.5f;
   g.gen_h64 = 0.3;
   g.gen_xmin64 = 1e-12;
   if (gen) {
-    const double nu = a.smoothness, h = gen_step(nu);
+    const GenLaunch c = gen_launch_constants(a.smoothness, s.es == 8);
     g.gen_tab = s.bwd ? 0 : (int)lds;
-    g.gen_h = (float)h;
-    g.gen_lc = (float)((log(h) + (1.0 - nu) * log(2.0) - lgamma(nu)) / log(2.0));
-    if (s.es == 8) {  // fp64: finer step, natural logarithms, a larger table
-      const double h64 = gen_step64(nu);
-      g.gen_h64 = h64;
-      g.gen_lc64 = log(h64) + (1.0 - nu) * log(2.0) - lgamma(nu);
-      g.gen_xmin64 = gen_xmin64(nu);
-    }
-    if (!s.bwd) lds += s.es == 8 ? 2 * MGP_GEN_NODES64 * sizeof(double) : 2 * MGP_GEN_NODES * sizeof(float);
+    g.gen_h = c.h;
+    g.gen_lc = c.lc;
+    if (s.es == 8) g.gen_h64 = c.h64, g.gen_lc64 = c.lc64, g.gen_xmin64 = c.xmin64;
+    if (!s.bwd) lds += gen_table_bytes(s.es);
   }
 #ifdef MGP_DEBUG_HOOKS
   if (!s.bwd && !s.jit) g.mask = g_phase_mask, lds += (size_t)g_lds_pad;

@@ -5,6 +5,7 @@
 // (see mgp_lds_factor.h).  The specialised register-resident kernels in mgp_fused_wave.hip
 // take over for the shapes they cover; this file is the path for everything else.
 #include "mgp_args.h"
+#include "mgp_gen_launch.h"
 #include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
@@ -17,8 +18,10 @@ __host__ __device__ inline int tile_row_stride(int dc) { return dc + 16 / (int)s
 
 // dynamic LDS carve (every array 16-byte aligned):
 // [idx: (k+2 & ~1) int64][S: rows*SP T][X: (k+1)*XP T][il: dc T][piv: k T][flag]
-template <typename T>
-__global__ void fused_generic_kernel(FusedArgs a) {
+// GEN (the general-smoothness Matern, a.smoothness): + [node table: 2 MGP_GEN_NODES float / 2 MGP_GEN_NODES64 double]
+// at byte g.tab, behind everything else; the closed-form instantiations reserve and read nothing of `g`.
+template <typename T, bool GEN>
+__device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const GenLaunch& g) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -48,6 +51,7 @@ __global__ void fused_generic_kernel(FusedArgs a) {
     const T l = ls[0];
     post_scale = a.metric_id == MGP_METRIC_L2 ? T(1) / l : T(1) / (l * l);
   }
+  if constexpr (GEN) gen_build_node_table<T>(reinterpret_cast<T*>(smem + g.tab), a.smoothness, g, tid);
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
@@ -92,13 +96,19 @@ __global__ void fused_generic_kernel(FusedArgs a) {
       __syncthreads();
     }
     // distances -> covariances (in place), nugget on the diagonal, responses into the tail rows
-    for (int p = tid; p < npairs; p += NT) {
-      int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-      while (a_ * (a_ - 1) / 2 > p) --a_;
-      while ((a_ + 1) * a_ / 2 <= p) ++a_;
-      const int c_ = p - a_ * (a_ - 1) / 2;
-      T* dst = S + a_ * SP + c_;
-      *dst = kernel_eval<T>(a.kernel_id, metric_arg<T>(*dst, a.metric_id, post_scale));
+    if constexpr (GEN) {
+      // (whole strips of NT x 4 / NT x 2 pairs, every thread in every evaluator call: mgp_gen_launch.h)
+      gen_covariance_phase<T>([&](int r, int c) { return S + r * SP + c; }, k, a.metric_id, post_scale, a.smoothness, g,
+                              reinterpret_cast<const T*>(smem + g.tab), tid, NT);
+    } else {
+      for (int p = tid; p < npairs; p += NT) {
+        int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
+        while (a_ * (a_ - 1) / 2 > p) --a_;
+        while ((a_ + 1) * a_ / 2 <= p) ++a_;
+        const int c_ = p - a_ * (a_ - 1) / 2;
+        T* dst = S + a_ * SP + c_;
+        *dst = kernel_eval<T>(a.kernel_id, metric_arg<T>(*dst, a.metric_id, post_scale));
+      }
     }
     for (int r = tid; r < k; r += NT) {
       T eps;
@@ -121,6 +131,13 @@ __global__ void fused_generic_kernel(FusedArgs a) {
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
 }
+
+// the closed-form kernels, and the general-smoothness Matern under a name of its own (its constants: an argument of
+// its own)
+template <typename T>
+__global__ void fused_generic_kernel(FusedArgs a) { fused_generic_body<T, false>(a, GenLaunch{}); }
+template <typename T>
+__global__ void fused_generic_gen_kernel(FusedArgs a, GenLaunch g) { fused_generic_body<T, true>(a, g); }
 
 // LDS carve: [S: rows*SP T][piv: k T][flag]
 template <typename T>
@@ -189,16 +206,31 @@ static size_t solve_lds_bytes(int k, int R) {
 }
 
 // (at most 16 workgroups per CU: mgp_launch.h, capacity_grid)
-template <typename T>
-int launch_fused_generic(const FusedArgs& in, hipStream_t stream) {
+// GEN: the general-smoothness Matern (a.smoothness); the LDS rule is "fits with the node table", which lies behind what
+// the closed-form launch of the same shape and chunk takes
+template <typename T, bool GEN>
+static int launch_fused_generic_impl(const FusedArgs& in, hipStream_t stream) {
   FusedArgs a = in;
+  if ((int64_t)a.k + 1 + a.R > kLargeMaxRows && GEN) return MGP_EUNSUPPORTED;  // (64 bits: k or R near INT_MAX)
+  const size_t table = GEN ? gen_table_bytes(sizeof(T)) : 0;
   // feature chunk: as wide as fits next to the factor (bounded so small problems stay small)
-  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, a.R, dc); });
+  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, a.R, dc) + table; });
   if (!fc.fits) return MGP_EUNSUPPORTED;
   a.dc = fc.dc;
-  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
-  return launch_capacity(&fused_generic_kernel<T>, lds_factor_threads(a.k + 1 + a.R), fc.lds, a.b, Capacity{16}, stream, &label, a).status;
+  GenLaunch g{};
+  if (GEN) {
+    g = gen_launch_constants(a.smoothness, sizeof(T) == 8);
+    g.tab = (int)(fc.lds - table);
+  }
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic%s_kernel<%s>", GEN ? "_gen" : "", sizeof(T) == 4 ? "float" : "double");
+  const int threads = lds_factor_threads(a.k + 1 + a.R);
+  if constexpr (GEN) return launch_capacity(&fused_generic_gen_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a, g).status;
+  else return launch_capacity(&fused_generic_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a).status;
 }
+template <typename T>
+int launch_fused_generic(const FusedArgs& a, hipStream_t stream) { return launch_fused_generic_impl<T, false>(a, stream); }
+template <typename T>
+int launch_fused_generic_gen(const FusedArgs& a, hipStream_t stream) { return launch_fused_generic_impl<T, true>(a, stream); }
 
 template <typename T>
 int launch_solve_generic(const SolveArgs& a, hipStream_t stream) {
@@ -209,11 +241,19 @@ int launch_solve_generic(const SolveArgs& a, hipStream_t stream) {
 
 template int launch_fused_generic<float>(const FusedArgs&, hipStream_t);
 template int launch_fused_generic<double>(const FusedArgs&, hipStream_t);
+template int launch_fused_generic_gen<float>(const FusedArgs&, hipStream_t);
+template int launch_fused_generic_gen<double>(const FusedArgs&, hipStream_t);
 template int launch_solve_generic<float>(const SolveArgs&, hipStream_t);
 template int launch_solve_generic<double>(const SolveArgs&, hipStream_t);
 
 int max_nn_count(int elem_size, int R) {
   return largest_k([&](int k) { return (elem_size == 4 ? fused_lds_bytes<float>(k, R, 8) : fused_lds_bytes<double>(k, R, 8)) <= kCuLdsBytes; });
+}
+// the largest k at which the general-smoothness launch fits: the same with the node table
+int max_nn_count_gen(int elem_size, int R) {
+  return largest_k([&](int k) {
+    return (elem_size == 4 ? fused_lds_bytes<float>(k, R, 8) : fused_lds_bytes<double>(k, R, 8)) + gen_table_bytes(elem_size) <= kCuLdsBytes;
+  });
 }
 
 }  // namespace mgp

@@ -21,6 +21,7 @@
 //      coming out of LDS as 16-byte broadcasts
 // Four workgroup barriers per panel.  The diagonal holds the INVERSE pivots afterwards (nothing reads the diagonal of
 // L but the back-substitution of the coefficient output, which wants the inverse).
+#include "mgp_gen_launch.h"
 #include "mgp_large_factor.h"
 
 namespace mgp {
@@ -53,8 +54,10 @@ __device__ __forceinline__ void emit_outputs_slab(SlabRows<T> row, int k, int R,
 }
 
 // dynamic LDS carve (every array 16-byte aligned): [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T]
-template <typename T>
-__global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* workspace, int slab_elems) {
+// GEN (the general-smoothness Matern, a.smoothness): + [node table: 2 MGP_GEN_NODES float / 2 MGP_GEN_NODES64 double]
+// at byte g.tab, behind everything else; the closed-form instantiations reserve and read nothing of `g`.
+template <typename T, bool GEN>
+__device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspace, int slab_elems, const GenLaunch& g) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -79,6 +82,7 @@ __global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* worksp
     const T l = ls[0];
     post_scale = a.metric_id == MGP_METRIC_L2 ? T(1) / l : T(1) / (l * l);
   }
+  if constexpr (GEN) gen_build_node_table<T>(reinterpret_cast<T*>(smem + g.tab), a.smoothness, g, tid);
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
@@ -126,10 +130,16 @@ __global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* worksp
         T* dst = row(a_) + c_;
         if (d0 > 0) acc += *dst;
         // the last chunk turns the distance into the covariance
-        *dst = d0 + dc >= d ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
+        if constexpr (GEN) *dst = acc;  // (the general smoothness: a phase of its own below)
+        else *dst = d0 + dc >= d ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
       }
       __syncthreads();
     }
+    // the general smoothness: distances out of the slab, covariances back into it, each pair by the thread that wrote
+    // its distance (whole strips of NT x 4 / NT x 2 pairs, every thread in every evaluator call: mgp_gen_launch.h)
+    if constexpr (GEN)
+      gen_covariance_phase<T>([&](int r, int c) { return row(r) + c; }, k, a.metric_id, post_scale, a.smoothness, g,
+                              reinterpret_cast<const T*>(smem + g.tab), tid, NT);
     // nugget on the diagonal, responses into the tail rows
     for (int r = tid; r < k; r += NT) {
       T eps;
@@ -151,6 +161,17 @@ __global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* worksp
                          yk ? yk + nb * R : nullptr, tid);
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
+}
+
+// the closed-form kernels, and the general-smoothness Matern under a name of its own (its constants: an argument of
+// its own)
+template <typename T>
+__global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* workspace, int slab_elems) {
+  fused_large_body<T, false>(a, workspace, slab_elems, GenLaunch{});
+}
+template <typename T>
+__global__ void __launch_bounds__(512) fused_large_gen_kernel(FusedArgs a, T* workspace, int slab_elems, GenLaunch g) {
+  fused_large_body<T, true>(a, workspace, slab_elems, g);
 }
 
 template <typename T>
@@ -234,21 +255,41 @@ int64_t large_workspace_bytes(int elem_size, int k, int R, int64_t b) {
   return n * slab > kMaxWorkspace ? kMaxWorkspace : n * slab;
 }
 
-template <typename T>
-int launch_fused_large(const FusedArgs& in, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+// GEN: the general-smoothness Matern (a.smoothness), which the closed-form entry refuses (it has no smoothness argument);
+// its node table lies behind what the closed-form launch of the same shape and chunk takes
+template <typename T, bool GEN>
+static int launch_fused_large_impl(const FusedArgs& in, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   FusedArgs a = in;
   const int64_t rows = (int64_t)a.k + 1 + a.R;  // (64 bits: k or R near INT_MAX must not wrap past the limit)
-  if (rows > kLargeMaxRows || a.kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
+  if (rows > kLargeMaxRows || (a.kernel_id == MGP_KERNEL_MATERN_GEN) != GEN) return MGP_EUNSUPPORTED;
   const int64_t slab = large_slab_bytes(sizeof(T), a.k, a.R);
+  const size_t table = GEN ? gen_table_bytes(sizeof(T)) : 0;
   // feature chunk: a multiple of 8, as wide as fits the CU's LDS (one workgroup per CU: nothing to share it with; every
   // further chunk is one more pass over the slab's triangle: at k = 1000, d = 40 five chunks of 8 cost as much as
   // the factorisation), at least 8
-  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, dc); });
+  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, dc) + table; });
   if (!fc.fits) return MGP_EUNSUPPORTED;
   a.dc = fc.dc;
-  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
-  return launch_capacity(&fused_large_kernel<T>, slab_block_threads((int)rows), fc.lds, a.b, Capacity{kMaxPerCu, workspace_bytes / slab}, stream,
-                         &label, a, static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T))).status;
+  GenLaunch g{};
+  if (GEN) {
+    g = gen_launch_constants(a.smoothness, sizeof(T) == 8);
+    g.tab = (int)(fc.lds - table);
+  }
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large%s_kernel<%s>", GEN ? "_gen" : "", sizeof(T) == 4 ? "float" : "double");
+  const int threads = slab_block_threads((int)rows), slab_elems = (int)(slab / (int64_t)sizeof(T));
+  const Capacity cap{kMaxPerCu, workspace_bytes / slab};
+  if constexpr (GEN)
+    return launch_capacity(&fused_large_gen_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems, g).status;
+  else
+    return launch_capacity(&fused_large_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems).status;
+}
+template <typename T>
+int launch_fused_large(const FusedArgs& a, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  return launch_fused_large_impl<T, false>(a, workspace, workspace_bytes, stream);
+}
+template <typename T>
+int launch_fused_large_gen(const FusedArgs& a, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  return launch_fused_large_impl<T, true>(a, workspace, workspace_bytes, stream);
 }
 
 template <typename T>
@@ -263,6 +304,8 @@ int launch_solve_large(const SolveArgs& a, void* workspace, int64_t workspace_by
 
 template int launch_fused_large<float>(const FusedArgs&, void*, int64_t, hipStream_t);
 template int launch_fused_large<double>(const FusedArgs&, void*, int64_t, hipStream_t);
+template int launch_fused_large_gen<float>(const FusedArgs&, void*, int64_t, hipStream_t);
+template int launch_fused_large_gen<double>(const FusedArgs&, void*, int64_t, hipStream_t);
 template int launch_solve_large<float>(const SolveArgs&, void*, int64_t, hipStream_t);
 template int launch_solve_large<double>(const SolveArgs&, void*, int64_t, hipStream_t);
 

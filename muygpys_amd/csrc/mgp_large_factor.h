@@ -10,6 +10,7 @@
 #include "mgp_args.h"
 #include "mgp_launch.h"
 #include "mgp_lds_factor.h"
+#include "mgp_wave_common.h"
 
 namespace mgp {
 
@@ -53,14 +54,8 @@ struct SlabRows {
   __device__ __forceinline__ T* operator()(int i) const { return S + large_row_off(i, k); }
 };
 
-// the value lane `src` (a compile-time constant after unrolling) holds, as a wave-uniform scalar
-__device__ __forceinline__ float lane_value(float v, int src) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-}
-__device__ __forceinline__ double lane_value(double v, int src) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src),
-                          __builtin_amdgcn_readlane(__double2loint(v), src));
-}
+// (lane_value -- the value lane `src`, a compile-time constant after unrolling, holds, as a wave-uniform scalar --
+// is the one of mgp_wave_common.h, which the general-smoothness front end brings in anyway)
 
 // step 1 of a panel, fp32: 32-row tiles on v_mfma_f32_32x32x2_f32.  Lane l feeds row (l & 31) of either operand; the
 // instruction contracts over two columns per issue and the order of the columns is free as long as both operands

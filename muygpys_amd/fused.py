@@ -57,8 +57,9 @@ class KernelSpec:
 
 
 class FusedUnsupported(RuntimeError):
-    """The fused kernels do not serve this model / shape (general-smoothness Matern beyond nu = 30, or with more
-    than 32 slots in a batch too small to compile a kernel for ...): evaluate through the per-function kernels instead."""
+    """The fused kernels do not serve this model / shape (general-smoothness Matern beyond nu = 30, with 33 to 64
+    slots in a batch too small to compile a kernel for, with more than 1024 rows ...): evaluate through the
+    per-function kernels instead."""
 
 
 # device-resident length scales of host-valued hyper-parameters, keyed by (values, device, dtype): an
@@ -368,6 +369,23 @@ def _posterior_large(spec: KernelSpec, inp: _Inputs, gathered: bool, outs: tuple
     )
 
 
+def _posterior_gen_family(spec: KernelSpec, inp: _Inputs, gathered: bool, outs: tuple, large: bool) -> int:
+    """One general-smoothness launch on a workgroup kernel family by name, plain tables: ``mgp_posterior_gen_large_*``
+    (the slab factor beyond LDS, with a workspace of :func:`_large_workspace`) or ``mgp_posterior_gen_generic_*`` (the
+    system in LDS).  ``outs`` as for :func:`_posterior_call`.  Returns the status; ``MGP_EUNSUPPORTED`` without a call
+    for a system of more than 1024 rows."""
+    P = _lib.ptr
+    head = (P(inp.fq), P(inp.fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, int(gathered),
+            inp.mode, inp.eps, P(inp.nz), float(spec.smoothness), spec.metric_id(), P(inp.ls), inp.ls.numel())
+    if not large:
+        return _lib.fn("posterior_gen_generic", inp.fn.dtype)(*head, *outs)
+    try:
+        ws = _large_workspace(inp.fn.dtype, inp.k, inp.R, inp.b, inp.fn.device)
+    except ValueError:
+        return _lib.EUNSUPPORTED
+    return _lib.fn("posterior_gen_large", inp.fn.dtype)(*head, *outs[:4], P(ws), ws.numel(), outs[4])
+
+
 def posterior_mean_var(
     spec: KernelSpec,
     test_features: torch.Tensor,
@@ -395,6 +413,11 @@ def posterior_mean_var(
     "auto" hands a closed-form kernel whose system no longer fits LDS (``nn_count`` beyond ``mgp_max_nn_count``) to the
     blocked factorisation in global memory (``mgp_posterior_large_*``), up to ``nn_count + 1 + R = 1024`` rows;
     beyond that: ``ValueError``.
+    The general-smoothness Matern (``kernel="matern_gen"``): up to 64 slots (``nn_count + 1 + R``) "auto" is the wave
+    kernels or :class:`FusedUnsupported`; beyond, on the plain tables, ``mgp_posterior_gen_*`` (the LDS workgroup
+    kernel) and, where the system does not fit LDS, ``mgp_posterior_gen_large_*`` -- :class:`FusedUnsupported` only for
+    more than 1024 rows or a smoothness above 30.  "generic" / "large" name those two entries at any ``nn_count``
+    (gathered responses included); "rhs" is a ``ValueError``.
     ``packed``: "auto" reads the tables through prepared copies (:class:`PackedTable`, cached per
     tensor) when the shape allows it and the batch touches the table often enough to pay for the
     one-time pack; True forces, False disables.
@@ -410,32 +433,42 @@ def posterior_mean_var(
     if path not in ("auto", "generic", "rhs", "large"):
         raise ValueError(f"unknown kernel path {path!r}")
     gen = spec.kernel == "matern_gen"  # one entry point for every table form (mgp_posterior_gen_*)
-    if gen and path != "auto":
+    if gen and path == "rhs":
         raise ValueError("the general-smoothness Matern goes through the dispatcher (path='auto')")
     if gen and (spec.smoothness is None or not float(spec.smoothness) > 0.0):
         raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
-    if gathered and path not in ("auto", "large"):
+    if gathered and path not in ("auto", "large") and not (gen and path == "generic"):
         raise ValueError("gathered responses go through the dispatcher (path='auto') or path='large'")
+    # the general smoothness beyond the 64 slots of the wave kernels: the workgroup families, plain tables only
+    gen_beyond = gen and inp.k + 1 + R > 64
     # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
     rows = fn.shape[0] + (0 if test_features is train_features else inp.fq.shape[0])
-    use_packed = path == "auto" and _use_packed(packed, inp, train_features, train_targets, rows, gathered)
+    use_packed = (path == "auto" and not gen_beyond
+                  and _use_packed(packed, inp, train_features, train_targets, rows, gathered))
     outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
     rc = -2
-    if use_packed:
+    if gen and path != "auto":  # one workgroup family by name (mgp_posterior_gen_generic_* / mgp_posterior_gen_large_*)
+        rc = _posterior_gen_family(spec, inp, gathered, outs, large=path == "large")
+    elif use_packed:
         pn = pack_table(train_features, None if gathered else train_targets, query=False)
         pq = pn if test_features is train_features else pack_table(test_features, None)
         call, args = _posterior_call(spec, inp, gathered, path, pq, pn, outs)
         rc = call(*args)
     # MGP_EUNSUPPORTED on the prepared tables (or not tried): the plain tables -- for the closed-form kernels only
     # (matern_gen does NOT retry on the plain tables: the caller gets FusedUnsupported)
-    if path == "large":
+    if gen and path != "auto":
+        pass
+    elif path == "large":
         rc = _posterior_large(spec, inp, gathered, outs)
     elif rc == _lib.EUNSUPPORTED and not (gen and use_packed):
         call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
         rc = call(*args)
-        # a closed-form kernel whose system does not fit LDS: the blocked factorisation in global memory
+        # a system that does not fit LDS: the blocked factorisation in global memory -- of a closed-form kernel, or of
+        # the general smoothness beyond 64 slots (up to 64 a refusal of the wave kernels is the caller's to handle)
         if rc == _lib.EUNSUPPORTED and path == "auto" and not gen:
             rc = _posterior_large(spec, inp, gathered, outs)
+        elif rc == _lib.EUNSUPPORTED and gen_beyond:
+            rc = _posterior_gen_family(spec, inp, gathered, outs, large=True)
     if gen and rc == _lib.EUNSUPPORTED:
         raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={inp.k}, R={R}, d={inp.d}")
     _lib.check(rc, "mgp_posterior_gen" if gen else "mgp_posterior")

@@ -76,8 +76,10 @@ def _spec(Kin: lazy.LazyCov):
 def fused(Kin: lazy.LazyCov, Kcross: lazy.LazyCov, nn_targets, differentiable: Optional[bool] = None):
     """(mean, var_unscaled_with_Kout_1, ykinvy, info) of a lazy triple, computed once per
     (noise, Kcross, responses) and cached on the shared Kin cache -- or None when no fused kernel serves
-    the model (:class:`muygpys_amd.fused.FusedUnsupported`: the general-smoothness Matern on fp64 tables
-    or in an oversized small batch); the caller then materialises.
+    the model (:class:`muygpys_amd.fused.FusedUnsupported`: the general-smoothness Matern with up to 64 slots,
+    ``nn_count + 1 + R``, on a shape the wave kernels refuse -- fp64 tables off the static shapes, an oversized
+    small batch -- or with more than 1024 rows or a smoothness above 30; from 65 slots to 1024 rows it is ONE launch
+    of the workgroup kernels, ``mgp_posterior_gen_*`` / ``mgp_posterior_gen_large_*``); the caller then materialises.
 
     ``nn_targets``: a :class:`lazy.LazyTargets` handle (responses gathered inside the kernel) or the
     already gathered (b, k[, R]) tensor (``mgp_posterior_gathered_*``).  When a feature table, the
