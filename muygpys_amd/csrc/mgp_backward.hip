@@ -14,6 +14,7 @@
 // kappa and the metric is applied per pair, and the per-point feature cotangents leave with one
 // atomic add per (point, feature).
 #include "mgp_args.h"
+#include "mgp_assemble.h"
 #include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
@@ -24,14 +25,6 @@ int g_bwd_stage = 0;  // timing ablations only: stop every neighbourhood after s
 #else
 static const int g_bwd_stage = 0;
 #endif
-
-__device__ __forceinline__ void tri_decode(int p, int& row, int& col) {
-  int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-  while (a_ * (a_ - 1) / 2 > p) --a_;
-  while ((a_ + 1) * a_ / 2 <= p) ++a_;
-  row = a_;
-  col = p - a_ * (a_ - 1) / 2;
-}
 
 // Single-wave form of "factor, then solve for two right-hand sides" (k + 2 <= 64 rows, 64 threads): the
 // row-per-lane register elimination of mgp_fused_wave.hip (column broadcast through a 64-entry LDS
@@ -113,7 +106,7 @@ __global__ __launch_bounds__(256) void backward_kernel(BackwardArgs g, int stage
   const int k = a.k, d = a.d, R = a.R, dc = a.dc;
   const int rows = k + 2;
   const int SP = lds_row_stride<T>(k);
-  const int XP = dc + E;
+  const int XP = tile_row_stride<T>(dc);
   int64_t* idx = reinterpret_cast<int64_t*>(smem);
   T* S = reinterpret_cast<T*>(idx + ((k + 2) & ~1));
   T* Q = S + rows * SP;
@@ -127,8 +120,6 @@ __global__ __launch_bounds__(256) void backward_kernel(BackwardArgs g, int stage
 
   const T* feat_q = static_cast<const T*>(a.feat_q);
   const T* feat_nn = static_cast<const T*>(a.feat_nn);
-  const T* targets = static_cast<const T*>(a.targets);
-  const T* noise_dev = static_cast<const T*>(a.noise_dev);
   const T* ls = static_cast<const T*>(a.length_scale);
   const T* gmean = static_cast<const T*>(g.grad_mean);
   const T* gvar = static_cast<const T*>(g.grad_var);
@@ -144,70 +135,27 @@ __global__ __launch_bounds__(256) void backward_kernel(BackwardArgs g, int stage
   const int npairs = (k + 1) * k / 2;
   const bool vec_ok = d % E == 0 && dc % E == 0 && ((uintptr_t)feat_q | (uintptr_t)feat_nn) % 16 == 0;
 
-  T post_scale = T(1), inv_l = T(1);
-  if (!aniso) {
-    inv_l = T(1) / ls[0];
-    post_scale = l2 ? inv_l : inv_l * inv_l;
-  }
+  const StridedRows<T> row{S, SP};
+  const IsoScale<T> iso = iso_scale<T, true>(a);
+  const T post_scale = iso.post_scale, inv_l = iso.inv_l;
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();
-    for (int r = tid; r <= k; r += NT)
-      idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
+    fill_index_list(idx, a, nb, k, tid, NT);
     if (tid == 0) red[0] = T(0);
     __syncthreads();
 
     // ---- forward recomputation: acc (kept in Q), covariances (S), combined right-hand side ----
-    for (int d0 = 0; d0 < d; d0 += dc) {
-      const int w = min(dc, d - d0);
-      const int wp = (w + E - 1) / E * E;  // zero-padded to whole 16-byte pieces
-      gather_tile_lds<T>(X, XP, feat_q, feat_nn, idx, k, d, d0, w, wp, vec_ok, tid, NT);
-      if (aniso)
-        for (int c = tid; c < wp; c += NT) il[c] = c < w ? T(1) / ls[d0 + c] : T(0);
-      __syncthreads();
-      for (int p = tid; p < npairs; p += NT) {
-        int a_, c_;
-        tri_decode(p, a_, c_);
-        const T* xa = X + a_ * XP;
-        const T* xc = X + c_ * XP;
-        T acc = T(0);
-        if (aniso) {
-#pragma unroll 2
-          for (int j = 0; j < wp; j += E) {
-            const V df = (*reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j)) *
-                         *reinterpret_cast<const V*>(il + j);
-            acc += vec_dot(df, df);
-          }
-        } else {
-#pragma unroll 2
-          for (int j = 0; j < wp; j += E) {
-            const V df = *reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j);
-            acc += vec_dot(df, df);
-          }
-        }
-        T* dst = Q + a_ * SP + c_;
-        *dst = d0 == 0 ? acc : *dst + acc;
-      }
-      __syncthreads();
-    }
+    pair_distances<T>(a, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool) {
+      T* dst = Q + r * SP + c;
+      *dst = d0 == 0 ? acc : *dst + acc;
+    });
     for (int p = tid; p < npairs; p += NT) {
       int a_, c_;
       tri_decode(p, a_, c_);
       S[a_ * SP + c_] = kernel_eval<T>(a.kernel_id, metric_arg<T>(Q[a_ * SP + c_], a.metric_id, post_scale));
     }
-    for (int r = tid; r < k; r += NT) {
-      T eps;
-      if (a.noise_mode == MGP_NOISE_SCALAR) eps = (T)a.noise_scalar;
-      else if (a.noise_mode == MGP_NOISE_TABLE) eps = noise_dev[idx[r]];
-      else eps = noise_dev[nb * k + r];
-      S[r * SP + r] = T(1) + eps;
-      T yt = T(0);
-      if (gyk)
-        yt = targets[idx[r] * (int64_t)R];
-      else if (gmean)
-        for (int q = 0; q < R; ++q) yt += gmean[nb * R + q] * targets[idx[r] * (int64_t)R + q];
-      S[(k + 1) * SP + r] = yt;
-    }
+    fill_diagonal_and_rhs<T>(row, a, gmean, gyk, idx, nb, k, tid, NT);
     __syncthreads();
     if (stage == 1) continue;
     const bool wave_path = NT == 64 && rows <= 64;  // uniform
@@ -250,16 +198,11 @@ __global__ __launch_bounds__(256) void backward_kernel(BackwardArgs g, int stage
     for (int p = tid; p < npairs; p += NT) {
       int a_, c_;
       tri_decode(p, a_, c_);
-      T gK;
-      if (a_ < k) gK = T(2) * gv * av[a_] * av[c_] - gm1 * (av[a_] * wv[c_] + av[c_] * wv[a_]) - T(2) * gyv * wv[a_] * wv[c_];
-      else gK = gm1 * wv[c_] - T(2) * gv * av[c_];
+      const T gK = pair_cotangent<T>(av, wv, a_, c_, k, gv, gm1, gyv);
       const T acc = Q[a_ * SP + c_];
       const T x = metric_arg<T>(acc, a.metric_id, post_scale);
       const T kp = kernel_deriv<T>(a.kernel_id, x);
-      T dk_dacc;
-      if (l2) dk_dacc = x > T(0) ? kp * post_scale * post_scale / (T(2) * x) : T(0);
-      else dk_dacc = kp * post_scale;
-      const T q = gK * dk_dacc;
+      const T q = gK * dk_dacc<T>(x, kp, post_scale, l2);
       Q[a_ * SP + c_] = q;  // symmetric, zero diagonal: the per-point sweep below runs a uniform loop
       Q[c_ * SP + a_] = q;
       liso += gK * kp * x;
@@ -271,7 +214,7 @@ __global__ __launch_bounds__(256) void backward_kernel(BackwardArgs g, int stage
       if ((tid & 63) == 0) atomicAdd(&red[0], liso);
     }
     if (gnz)
-      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = gv * av[r] * av[r] - gm1 * av[r] * wv[r] - gyv * wv[r] * wv[r];
+      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = noise_cotangent<T>(av[r], wv[r], gv, gm1, gyv);
     if (gtg && gmean)
       for (int t = tid; t < k * R; t += NT) {
         const int c = t / R, r = t - c * R;

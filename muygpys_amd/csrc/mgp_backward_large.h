@@ -1,10 +1,11 @@
 // The phases the two backward kernels on the slab factor share (mgp_backward_large.hip: the hyper-parameter partials;
-// mgp_backward_large_full.hip: the whole vector-Jacobian product): the LDS carve, the assembly of a backward slab, the
-// back-substitution of its two tail rows, the cotangent of a pair, the per-feature length-scale sums of one feature
-// chunk, and the launch rule.  Every sum here is per-thread partials in a fixed pair order -> wave_sum -> the waves'
+// mgp_backward_large_full.hip: the whole vector-Jacobian product): the LDS carve, the assembly of a backward slab (out
+// of the pieces of mgp_assemble.h, where the cotangent of a pair lives too), the back-substitution of its two tail
+// rows, the per-feature length-scale sums of one feature chunk, and the launch rule.  Every sum here is per-thread partials in a fixed pair order -> wave_sum -> the waves'
 // totals in wave order through LDS: no floating-point atomic.
 #pragma once
 
+#include "mgp_assemble.h"
 #include "mgp_large_factor.h"
 
 namespace mgp {
@@ -40,7 +41,7 @@ __device__ __forceinline__ BackwardLargeLds<T> backward_large_carve(char* smem, 
   constexpr int E = 16 / (int)sizeof(T);
   const int KA = (k + E - 1) / E * E;
   BackwardLargeLds<T> s;
-  s.XP = dc + E;
+  s.XP = tile_row_stride<T>(dc);
   s.Lb = reinterpret_cast<T*>(smem);
   s.idx = reinterpret_cast<int64_t*>(s.Lb + LNB * large_lp<T>());
   s.X = reinterpret_cast<T*>(s.idx + ((k + 2) & ~1));
@@ -67,75 +68,20 @@ static FeatureChunk backward_large_chunk(int k, int d) {
 }
 
 // ---- 1. the index list, squared distances (kept in Dst when keep_acc), covariances, nugget, the two tail rows: c, and
-// ONE combined right-hand side yt = y (gyk given: the LOOCV form) or Y gm ----
+// ONE combined right-hand side yt = y (gyk given: the LOOCV form) or Y gm -- the pieces of mgp_assemble.h ----
 template <typename T>
 __device__ __forceinline__ void backward_large_assemble(const FusedArgs& a, const T* gmean, const T* gyk, bool keep_acc,
                                                         T post_scale, int64_t nb, int k, SlabRows<T> row, T* Dst,
                                                         const BackwardLargeLds<T>& s, int tid, int NT) {
-  using V = typename lds_vec<T>::type;
-  constexpr int E = 16 / (int)sizeof(T);
-  const int d = a.d, R = a.R, dc = a.dc, XP = s.XP;
-  const T* feat_q = static_cast<const T*>(a.feat_q);
-  const T* feat_nn = static_cast<const T*>(a.feat_nn);
-  const T* targets = static_cast<const T*>(a.targets);
-  const T* noise_dev = static_cast<const T*>(a.noise_dev);
-  const T* ls = static_cast<const T*>(a.length_scale);
-  const bool aniso = a.ls_count > 1;
-  const bool vec_ok = d % E == 0 && dc % E == 0 && ((uintptr_t)feat_q | (uintptr_t)feat_nn) % 16 == 0;
-  const int npairs = (k + 1) * k / 2;
-  int64_t* idx = s.idx;
-  T *X = s.X, *il = s.il;
-  for (int r = tid; r <= k; r += NT)
-    idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
+  fill_index_list(s.idx, a, nb, k, tid, NT);
   __syncthreads();
-
-  for (int d0 = 0; d0 < d; d0 += dc) {
-    const int w = min(dc, d - d0);
-    const int wp = (w + E - 1) / E * E;  // zero-padded to whole 16-byte pieces
-    gather_tile_lds<T>(X, XP, feat_q, feat_nn, idx, k, d, d0, w, wp, vec_ok, tid, NT);
-    if (aniso)
-      for (int c = tid; c < wp; c += NT) il[c] = c < w ? T(1) / ls[d0 + c] : T(0);
-    __syncthreads();
-    for (int p = tid; p < npairs; p += NT) {
-      int a_, c_;
-      large_tri_decode(p, a_, c_);
-      const T* xa = X + a_ * XP;
-      const T* xc = X + c_ * XP;
-      T acc = T(0);
-      if (aniso) {
-#pragma unroll 2
-        for (int j = 0; j < wp; j += E) {
-          const V df = (*reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j)) *
-                       *reinterpret_cast<const V*>(il + j);
-          acc += vec_dot(df, df);
-        }
-      } else {
-#pragma unroll 2
-        for (int j = 0; j < wp; j += E) {
-          const V df = *reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j);
-          acc += vec_dot(df, df);
-        }
-      }
-      if (d0 > 0) acc += Dst[p];
-      if (keep_acc) Dst[p] = acc;
-      // the last chunk also writes the covariance into the system
-      if (d0 + dc >= d) row(a_)[c_] = kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale));
-    }
-    __syncthreads();
-  }
-  for (int r = tid; r < k; r += NT) {
-    T eps;
-    if (a.noise_mode == MGP_NOISE_SCALAR) eps = (T)a.noise_scalar;
-    else if (a.noise_mode == MGP_NOISE_TABLE) eps = noise_dev[idx[r]];
-    else eps = noise_dev[nb * k + r];
-    row(r)[r] = T(1) + eps;  // kernel(0) == 1 for every kernel on the path
-    T yt = T(0);
-    if (gyk)
-      yt = targets[idx[r] * (int64_t)R];
-    else if (gmean)
-      for (int q = 0; q < R; ++q) yt += gmean[nb * R + q] * targets[idx[r] * (int64_t)R + q];
-    row(k + 1)[r] = yt;
-  }
+  pair_distances<T>(a, k, s.idx, s.X, s.XP, s.il, tid, NT, [&](int p, int r, int c, T acc, int d0, bool last) {
+    if (d0 > 0) acc += Dst[p];
+    if (keep_acc) Dst[p] = acc;
+    // the last chunk also writes the covariance into the system
+    if (last) row(r)[c] = kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale));
+  });
+  fill_diagonal_and_rhs<T>(row, a, gmean, gyk, s.idx, nb, k, tid, NT);
   __syncthreads();
 }
 
@@ -193,18 +139,6 @@ __device__ __forceinline__ void backward_large_solve_tails(SlabRows<T> row, int 
   __syncthreads();
 }
 
-// d loss / d K_ac of the pair (a_, c_), a_ > c_, of the (k+1)-point set (point k is the query: d loss / d c)
-template <typename T>
-__device__ __forceinline__ T backward_large_pair_cotangent(const T* av, const T* wv, int a_, int c_, int k, T gv, T gm1,
-                                                           T gyv) {
-  const T ac = av[c_], wc = wv[c_];
-  if (a_ < k) {
-    const T aa = av[a_], wa = wv[a_];
-    return T(2) * gv * aa * ac - gm1 * (aa * wc + ac * wa) - T(2) * gyv * wa * wc;
-  }
-  return gm1 * wc - T(2) * gv * ac;
-}
-
 // ---- 5. Anisotropy, one feature chunk whose rows are staged in X: grad_ls[c] = -2 / l_c^3 sum_pairs q_ij (x_ic - x_jc)^2
 // with q in the triangle Dst, eight features per pass.  gls_row / ls: at the chunk's first feature ----
 template <typename T>
@@ -218,7 +152,7 @@ __device__ __forceinline__ void backward_large_ls_chunk(const T* Dst, const T* X
     for (int u = 0; u < kBwdGroup / E; ++u) s[u] = V(0);
     for (int p = tid; p < npairs; p += NT) {
       int a_, c_;
-      large_tri_decode(p, a_, c_);
+      tri_decode(p, a_, c_);
       const T q = Dst[p];
       const T* xa = X + a_ * XP + c0;
       const T* xc = X + c_ * XP + c0;

@@ -9,14 +9,15 @@
 //
 // Per neighbourhood (the phases are in mgp_backward_large.h, shared with the whole vector-Jacobian product of
 // mgp_backward_large_full.hip):
-//   1. assemble as fused_large_kernel does (feature chunks of dc columns through LDS); the squared distances
-//      accumulate in the triangle and stay there, the last chunk writes the covariances into the trapezoid.  Two tail
-//      rows whatever R is: c, and ONE combined right-hand side yt = y (LOOCV form) or Y gm
+//   1. assemble with the front end of fused_large_kernel (mgp_assemble.h: feature chunks of dc columns through LDS);
+//      the squared distances accumulate in the triangle and stay there, the last chunk writes the covariances into the
+//      trapezoid.  Two tail rows whatever R is: c, and ONE combined right-hand side yt = y (LOOCV form) or Y gm
 //   2. factor_augmented_slab, unchanged
 //   3. back-substitution L^T [a w] = [z zy] by the scheme of solve_large_kernel's coefficient output (column by column
 //      from the last, row j of L read contiguously, the inverse pivot on its diagonal) with both tail rows in LDS: the
 //      chain of k dependent steps runs through LDS, and row j - 1 of L is on its way from the slab while step j runs
-//   4. cotangent of every pair (mgp_backward.hip), grad_noise, the isotropic length-scale sum
+//   4. cotangent of every pair (the formulas of mgp_backward.hip, their shared pieces in mgp_assemble.h), grad_noise,
+//      the isotropic length-scale sum
 //   5. Anisotropy: the triangle now holds q = gK dkappa/dacc; per feature chunk the rows are staged in LDS again and
 //      eight features at a time are summed over all pairs
 // Every sum is per-thread partials in a fixed pair order -> wave_sum -> the waves' totals in wave order through LDS:
@@ -50,11 +51,8 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
   // whose features fit one chunk stores none
   const bool keep_acc = gls != nullptr || d > dc;
 
-  T post_scale = T(1), inv_l = T(1);
-  if (!aniso) {
-    inv_l = T(1) / ls[0];
-    post_scale = l2 ? inv_l : inv_l * inv_l;
-  }
+  const IsoScale<T> iso = iso_scale<T, true>(a);
+  const T post_scale = iso.post_scale, inv_l = iso.inv_l;
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
@@ -87,15 +85,12 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
       T liso = T(0);
       for (int p = tid; p < npairs; p += NT) {
         int a_, c_;
-        large_tri_decode(p, a_, c_);
-        const T gK = backward_large_pair_cotangent<T>(av, wv, a_, c_, k, gv, gm1, gyv);
+        tri_decode(p, a_, c_);
+        const T gK = pair_cotangent<T>(av, wv, a_, c_, k, gv, gm1, gyv);
         const T x = metric_arg<T>(Dst[p], a.metric_id, post_scale);
         const T kp = kernel_deriv<T>(a.kernel_id, x);
         if (aniso) {
-          T dk_dacc;
-          if (l2) dk_dacc = x > T(0) ? kp * post_scale * post_scale / (T(2) * x) : T(0);
-          else dk_dacc = kp * post_scale;
-          Dst[p] = gK * dk_dacc;
+          Dst[p] = gK * dk_dacc<T>(x, kp, post_scale, l2);
         } else {
           liso += gK * kp * x;
         }
@@ -106,7 +101,7 @@ __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs 
       }
     }
     if (gnz)
-      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = gv * av[r] * av[r] - gm1 * av[r] * wv[r] - gyv * wv[r] * wv[r];
+      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = noise_cotangent<T>(av[r], wv[r], gv, gm1, gyv);
     if (!(gls && aniso)) continue;  // uniform
 
     // ---- 5. Anisotropy: grad_ls[c] = -2 / l_c^3 sum_pairs q_ij (x_ic - x_jc)^2 ----

@@ -120,11 +120,8 @@ __global__ void __launch_bounds__(512) posterior_backward_large_kernel(BackwardA
   // the distances are read again by the next feature chunk and by every cotangent through the kernel function
   const bool keep_acc = gls != nullptr || sweep || d > dc;
 
-  T post_scale = T(1), inv_l = T(1);
-  if (!aniso) {
-    inv_l = T(1) / ls[0];
-    post_scale = l2 ? inv_l : inv_l * inv_l;
-  }
+  const IsoScale<T> iso = iso_scale<T, true>(a);
+  const T post_scale = iso.post_scale, inv_l = iso.inv_l;
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
@@ -156,16 +153,11 @@ __global__ void __launch_bounds__(512) posterior_backward_large_kernel(BackwardA
       T liso = T(0);
       for (int p = tid; p < npairs; p += NT) {
         int a_, c_;
-        large_tri_decode(p, a_, c_);
-        const T gK = backward_large_pair_cotangent<T>(av, wv, a_, c_, k, gv, T(1), T(0));
+        tri_decode(p, a_, c_);
+        const T gK = pair_cotangent<T>(av, wv, a_, c_, k, gv, T(1), T(0));
         const T x = metric_arg<T>(Dst[p], a.metric_id, post_scale);
         const T kp = kernel_deriv<T>(a.kernel_id, x);
-        if (want_q) {
-          T dk_dacc;
-          if (l2) dk_dacc = x > T(0) ? kp * post_scale * post_scale / (T(2) * x) : T(0);
-          else dk_dacc = kp * post_scale;
-          Dst[p] = gK * dk_dacc;
-        }
+        if (want_q) Dst[p] = gK * dk_dacc<T>(x, kp, post_scale, l2);
         liso += gK * kp * x;
       }
       if (gls && !aniso) {
@@ -174,7 +166,7 @@ __global__ void __launch_bounds__(512) posterior_backward_large_kernel(BackwardA
       }
     }
     if (gnz)
-      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = gv * av[r] * av[r] - av[r] * wv[r];
+      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = noise_cotangent<T>(av[r], wv[r], gv);
     if (!want_q) continue;  // uniform
 
     // ---- 5, 6. per feature chunk: the per-feature length-scale sums, the per-point sweep ----

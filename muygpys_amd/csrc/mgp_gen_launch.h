@@ -7,6 +7,7 @@
 #pragma once
 #include <cmath>
 
+#include "mgp_assemble.h"
 #include "mgp_wave_common.h"
 
 namespace mgp {
@@ -66,11 +67,9 @@ __device__ __forceinline__ void gen_covariance_phase(At at, int k, int metric_id
       v[u] = T(1);
       dst[u] = nullptr;
       if (p < npairs) {
-        // p -> (row a_, col c_) of the strict lower triangle of the (k+1)-point set
-        int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-        while (a_ * (a_ - 1) / 2 > p) --a_;
-        while ((a_ + 1) * a_ / 2 <= p) ++a_;
-        dst[u] = at(a_, p - a_ * (a_ - 1) / 2);
+        int a_, c_;
+        tri_decode(p, a_, c_);
+        dst[u] = at(a_, c_);
         v[u] = *dst[u];
         live |= 1u << u;
       }

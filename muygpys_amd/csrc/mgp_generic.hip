@@ -2,19 +2,16 @@
 //   * fused gather -> distances -> kernel -> nugget -> factor -> mean/var/yKinvy
 //   * the same factorisation on a materialised Kin (API parity: S1/S2/S3 + fast precompute)
 // One workgroup owns one neighbourhood at a time; its whole local system lives in LDS
-// (see mgp_lds_factor.h).  The specialised register-resident kernels in mgp_fused_wave.hip
+// (see mgp_lds_factor.h); the assembly of the system is the one of mgp_assemble.h, shared with mgp_large.hip and the
+// backward kernels.  The specialised register-resident kernels in mgp_fused_wave.hip
 // take over for the shapes they cover; this file is the path for everything else.
 #include "mgp_args.h"
+#include "mgp_assemble.h"
 #include "mgp_gen_launch.h"
 #include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
 namespace mgp {
-
-// feature-tile row stride for a chunk of dc features (dc a multiple of 2E): 16-byte aligned rows, odd
-// number of 16-byte slots
-template <typename T>
-__host__ __device__ inline int tile_row_stride(int dc) { return dc + 16 / (int)sizeof(T); }
 
 // dynamic LDS carve (every array 16-byte aligned):
 // [idx: (k+2 & ~1) int64][S: rows*SP T][X: (k+1)*XP T][il: dc T][piv: k T][flag]
@@ -22,10 +19,8 @@ __host__ __device__ inline int tile_row_stride(int dc) { return dc + 16 / (int)s
 // at byte g.tab, behind everything else; the closed-form instantiations reserve and read nothing of `g`.
 template <typename T, bool GEN>
 __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const GenLaunch& g) {
-  using V = typename lds_vec<T>::type;
-  constexpr int E = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int k = a.k, d = a.d, R = a.R, dc = a.dc;
+  const int k = a.k, R = a.R, dc = a.dc;
   const int rows = k + 1 + R;
   const int SP = lds_row_stride<T>(k);
   const int XP = tile_row_stride<T>(dc);
@@ -35,99 +30,48 @@ __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const Gen
   T* il = X + (k + 1) * XP;
   T* piv = il + dc;
   int* flag = reinterpret_cast<int*>(piv + k);
+  const StridedRows<T> row{S, SP};
 
-  const T* feat_q = static_cast<const T*>(a.feat_q);
-  const T* feat_nn = static_cast<const T*>(a.feat_nn);
-  const T* targets = static_cast<const T*>(a.targets);
-  const T* noise_dev = static_cast<const T*>(a.noise_dev);
-  const T* ls = static_cast<const T*>(a.length_scale);
   const int tid = threadIdx.x, NT = blockDim.x;
-  const bool aniso = a.ls_count > 1;
-  const int npairs = (k + 1) * k / 2;
-  const bool vec_ok = d % E == 0 && dc % E == 0 && ((uintptr_t)feat_q | (uintptr_t)feat_nn) % 16 == 0;
-
-  T post_scale = T(1);
-  if (!aniso) {
-    const T l = ls[0];
-    post_scale = a.metric_id == MGP_METRIC_L2 ? T(1) / l : T(1) / (l * l);
-  }
+  const T post_scale = iso_scale<T, false>(a).post_scale;
   if constexpr (GEN) gen_build_node_table<T>(reinterpret_cast<T*>(smem + g.tab), a.smoothness, g, tid);
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
-    for (int r = tid; r <= k; r += NT)
-      idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
+    fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
 
-    for (int d0 = 0; d0 < d; d0 += dc) {
-      const int w = min(dc, d - d0);
-      const int wp = (w + E - 1) / E * E;  // zero-padded to whole 16-byte pieces
-      // coalesced gather of the (k+1) x w feature tile: consecutive lanes walk a row
-      gather_tile_lds<T>(X, XP, feat_q, feat_nn, idx, k, d, d0, w, wp, vec_ok, tid, NT);
-      if (aniso)
-        for (int c = tid; c < wp; c += NT) il[c] = c < w ? T(1) / ls[d0 + c] : T(0);
-      __syncthreads();
-      for (int p = tid; p < npairs; p += NT) {
-        // p -> (row a_, col c_) of the strict lower triangle of the (k+1)-point set
-        int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-        while (a_ * (a_ - 1) / 2 > p) --a_;
-        while ((a_ + 1) * a_ / 2 <= p) ++a_;
-        const int c_ = p - a_ * (a_ - 1) / 2;
-        const T* xa = X + a_ * XP;
-        const T* xc = X + c_ * XP;
-        T acc = T(0);
-        if (aniso) {
-#pragma unroll 2
-          for (int j = 0; j < wp; j += E) {
-            const V df = (*reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j)) *
-                         *reinterpret_cast<const V*>(il + j);
-            acc += vec_dot(df, df);
-          }
-        } else {
-#pragma unroll 2
-          for (int j = 0; j < wp; j += E) {
-            const V df = *reinterpret_cast<const V*>(xa + j) - *reinterpret_cast<const V*>(xc + j);
-            acc += vec_dot(df, df);
-          }
-        }
-        T* dst = S + a_ * SP + c_;
-        *dst = d0 == 0 ? acc : *dst + acc;
-      }
-      __syncthreads();
-    }
-    // distances -> covariances (in place), nugget on the diagonal, responses into the tail rows
+    // ---- assemble: squared distances summed over the feature chunks in S, covariances in place in a second pass, the
+    // nugget on the diagonal, the responses into the tail rows ----
+    pair_distances<T>(a, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool) {
+      T* dst = row(r) + c;
+      *dst = d0 == 0 ? acc : *dst + acc;
+    });
     if constexpr (GEN) {
       // (whole strips of NT x 4 / NT x 2 pairs, every thread in every evaluator call: mgp_gen_launch.h)
-      gen_covariance_phase<T>([&](int r, int c) { return S + r * SP + c; }, k, a.metric_id, post_scale, a.smoothness, g,
+      gen_covariance_phase<T>([&](int r, int c) { return row(r) + c; }, k, a.metric_id, post_scale, a.smoothness, g,
                               reinterpret_cast<const T*>(smem + g.tab), tid, NT);
     } else {
-      for (int p = tid; p < npairs; p += NT) {
-        int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-        while (a_ * (a_ - 1) / 2 > p) --a_;
-        while ((a_ + 1) * a_ / 2 <= p) ++a_;
-        const int c_ = p - a_ * (a_ - 1) / 2;
-        T* dst = S + a_ * SP + c_;
+      for (int p = tid; p < (k + 1) * k / 2; p += NT) {
+        int r, c;
+        tri_decode(p, r, c);
+        T* dst = row(r) + c;
         *dst = kernel_eval<T>(a.kernel_id, metric_arg<T>(*dst, a.metric_id, post_scale));
       }
     }
-    for (int r = tid; r < k; r += NT) {
-      T eps;
-      if (a.noise_mode == MGP_NOISE_SCALAR) eps = (T)a.noise_scalar;
-      else if (a.noise_mode == MGP_NOISE_TABLE) eps = noise_dev[idx[r]];
-      else eps = noise_dev[nb * k + r];
-      S[r * SP + r] = T(1) + eps;  // kernel(0) == 1 for every kernel on the path
-    }
-    for (int t = tid; t < k * R; t += NT) {
-      const int c = t / R, r = t - c * R;
-      S[(k + 1 + r) * SP + c] = targets[(a.targets_batch ? nb * k + c : idx[c]) * (int64_t)R + r];
-    }
+    // (responses first: the two loops are independent, and fused_generic_kernel<float> at k = 192, d = 40 measured 3 %
+    // faster in this order than in the other -- the same loops elsewhere, placed differently)
+    fill_responses<T>(row, a, idx, nb, k, R, tid, NT);
+    fill_diagonal<T>(row, a, idx, nb, k, tid, NT);
     __syncthreads();
-    const bool bad = factor_augmented_lds<T>(S, SP, k, rows, piv, flag, tid, NT);
+
+    // ---- factor, finish ----
+    const bool bad = factor_augmented_rows<T>(row, k, rows, piv, flag, tid, NT);
     T* mean = static_cast<T*>(a.mean);
     T* var = static_cast<T*>(a.var);
     T* yk = static_cast<T*>(a.ykinvy);
-    emit_outputs_lds<T>(S, SP, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
-                        yk ? yk + nb * R : nullptr, tid, NT);
+    emit_outputs<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
+                    yk ? yk + nb * R : nullptr, tid);
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
 }
@@ -171,8 +115,8 @@ __global__ void solve_generic_kernel(SolveArgs a) {
     T* mean = static_cast<T*>(a.mean);
     T* var = static_cast<T*>(a.var);
     T* yk = static_cast<T*>(a.ykinvy);
-    emit_outputs_lds<T>(S, SP, k, R, (T)a.kout, bad, Kcross != nullptr, mean ? mean + nb * R : nullptr,
-                        var ? var + nb : nullptr, yk ? yk + nb * R : nullptr, tid, NT);
+    emit_outputs<T>(StridedRows<T>{S, SP}, k, R, (T)a.kout, bad, Kcross != nullptr, mean ? mean + nb * R : nullptr,
+                    var ? var + nb : nullptr, yk ? yk + nb * R : nullptr, tid);
     if (a.coeffs) {
       // back-substitution L^T x = (L^-1 y_r), one response per thread, in place in row k+1+r
       T* co = static_cast<T*>(a.coeffs) + nb * (int64_t)k * R;

@@ -21,43 +21,19 @@
 //      coming out of LDS as 16-byte broadcasts
 // Four workgroup barriers per panel.  The diagonal holds the INVERSE pivots afterwards (nothing reads the diagonal of
 // L but the back-substitution of the coefficient output, which wants the inverse).
+#include "mgp_assemble.h"
 #include "mgp_gen_launch.h"
 #include "mgp_large_factor.h"
 
 namespace mgp {
 
-// mean (R), var, ykinvy (R) from the factored slab: the inner products of emit_outputs_lds, same order
+// The general-smoothness instantiations keep the body they had before the closed-form kernels' front end moved to
+// mgp_assemble.h (its chunk loop, nugget and responses written out): on the shared one fused_large_gen_kernel<float>
+// measured 0.3 - 0.4 % behind this code at k = 300, d = 8, outside its own run-to-run spread, though the loops that take
+// the time were the same instructions.  A model parameter that touches the assembly is written here as well.
+// (LDS carve: as fused_large_body below, + the node table at byte g.tab, behind everything else)
 template <typename T>
-__device__ __forceinline__ void emit_outputs_slab(SlabRows<T> row, int k, int R, T kout, bool bad, bool has_cross, T* mean, T* var,
-                                         T* ykinvy, int tid) {
-  if (tid >= MGP_WAVE) return;
-  const T* z = row(k);
-  for (int o = 0; o < 1 + 2 * R; ++o) {
-    const T* x = z;
-    const T* y = z;
-    T* dst = nullptr;
-    if (o == 0) {
-      if (var != nullptr && has_cross) dst = var;
-    } else if (o <= R) {
-      y = row(k + o);
-      if (mean != nullptr && has_cross) dst = mean + (o - 1);
-    } else {
-      x = y = row(k + 1 + (o - R - 1));
-      if (ykinvy != nullptr) dst = ykinvy + (o - R - 1);
-    }
-    if (dst == nullptr) continue;  // uniform
-    T s = T(0);
-    for (int m = tid; m < k; m += MGP_WAVE) s += x[m] * y[m];
-    s = wave_sum(s);
-    if (tid == 0) *dst = bad ? num<T>::nan() : (o == 0 ? kout - s : s);
-  }
-}
-
-// dynamic LDS carve (every array 16-byte aligned): [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T]
-// GEN (the general-smoothness Matern, a.smoothness): + [node table: 2 MGP_GEN_NODES float / 2 MGP_GEN_NODES64 double]
-// at byte g.tab, behind everything else; the closed-form instantiations reserve and read nothing of `g`.
-template <typename T, bool GEN>
-__device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspace, int slab_elems, const GenLaunch& g) {
+__device__ __forceinline__ void fused_large_gen_body(const FusedArgs& a, T* workspace, int slab_elems, const GenLaunch& g) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -82,7 +58,7 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
     const T l = ls[0];
     post_scale = a.metric_id == MGP_METRIC_L2 ? T(1) / l : T(1) / (l * l);
   }
-  if constexpr (GEN) gen_build_node_table<T>(reinterpret_cast<T*>(smem + g.tab), a.smoothness, g, tid);
+  gen_build_node_table<T>(reinterpret_cast<T*>(smem + g.tab), a.smoothness, g, tid);
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
@@ -91,12 +67,9 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
     const int rows = k + 1 + R;
     const int npairs = (k + 1) * k / 2;
     const SlabRows<T> row{workspace + (int64_t)blockIdx.x * slab_elems, k};
-    for (int r = tid; r <= k; r += NT)
-      idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
+    fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
-
-    // squared distances of the (k+1)-point set, one chunk of dc features at a time: the chunk's rows are staged in
-    // LDS, the partial sums live in the slab
+    // squared distances, one chunk of dc features at a time, the partial sums in the slab (pair_distances, written out)
     for (int d0 = 0; d0 < d; d0 += dc) {
       const int w = min(dc, d - d0);
       const int wp = (w + E - 1) / E * E;  // zero-padded to whole 16-byte pieces
@@ -105,11 +78,8 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
         for (int c = tid; c < wp; c += NT) il[c] = c < w ? T(1) / ls[d0 + c] : T(0);
       __syncthreads();
       for (int p = tid; p < npairs; p += NT) {
-        // p -> (row a_, col c_) of the strict lower triangle of the (k+1)-point set
-        int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-        while (a_ * (a_ - 1) / 2 > p) --a_;
-        while ((a_ + 1) * a_ / 2 <= p) ++a_;
-        const int c_ = p - a_ * (a_ - 1) / 2;
+        int a_, c_;
+        tri_decode(p, a_, c_);
         const T* xa = X + a_ * XP;
         const T* xc = X + c_ * XP;
         T acc = T(0);
@@ -129,18 +99,14 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
         }
         T* dst = row(a_) + c_;
         if (d0 > 0) acc += *dst;
-        // the last chunk turns the distance into the covariance
-        if constexpr (GEN) *dst = acc;  // (the general smoothness: a phase of its own below)
-        else *dst = d0 + dc >= d ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
+        *dst = acc;  // (the covariances: a phase of its own below)
       }
       __syncthreads();
     }
-    // the general smoothness: distances out of the slab, covariances back into it, each pair by the thread that wrote
-    // its distance (whole strips of NT x 4 / NT x 2 pairs, every thread in every evaluator call: mgp_gen_launch.h)
-    if constexpr (GEN)
-      gen_covariance_phase<T>([&](int r, int c) { return row(r) + c; }, k, a.metric_id, post_scale, a.smoothness, g,
-                              reinterpret_cast<const T*>(smem + g.tab), tid, NT);
-    // nugget on the diagonal, responses into the tail rows
+    // distances out of the slab, covariances back into it, each pair by the thread that wrote its distance (whole
+    // strips of NT x 4 / NT x 2 pairs, every thread in every evaluator call: mgp_gen_launch.h)
+    gen_covariance_phase<T>([&](int r, int c) { return row(r) + c; }, k, a.metric_id, post_scale, a.smoothness, g,
+                            reinterpret_cast<const T*>(smem + g.tab), tid, NT);
     for (int r = tid; r < k; r += NT) {
       T eps;
       if (a.noise_mode == MGP_NOISE_SCALAR) eps = (T)a.noise_scalar;
@@ -157,8 +123,53 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
     T* mean = static_cast<T*>(a.mean);
     T* var = static_cast<T*>(a.var);
     T* yk = static_cast<T*>(a.ykinvy);
-    emit_outputs_slab<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
-                         yk ? yk + nb * R : nullptr, tid);
+    emit_outputs<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
+                    yk ? yk + nb * R : nullptr, tid);
+    if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
+  }
+}
+
+// dynamic LDS carve (every array 16-byte aligned): [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T]
+template <typename T>
+__device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspace, int slab_elems) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int k_ = a.k, R_ = a.R, dc = a.dc;
+  const int XP = tile_row_stride<T>(dc);
+  T* Lb = reinterpret_cast<T*>(smem);
+  int64_t* idx = reinterpret_cast<int64_t*>(Lb + LNB * large_lp<T>());
+  T* X = reinterpret_cast<T*>(idx + ((k_ + 2) & ~1));
+  T* il = X + (k_ + 1) * XP;
+
+  const int tid = threadIdx.x, NT = blockDim.x;
+  const T post_scale = iso_scale<T, false>(a).post_scale;
+
+  for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
+    __syncthreads();  // previous neighbourhood fully consumed
+    int k = k_, R = R_;
+    asm volatile("" : "+s"(k), "+s"(R));
+    const int rows = k + 1 + R;
+    const SlabRows<T> row{workspace + (int64_t)blockIdx.x * slab_elems, k};
+    fill_index_list(idx, a, nb, k, tid, NT);
+    __syncthreads();
+
+    // ---- assemble: the chunks' rows are staged in LDS, the partial sums of the squared distances live in the slab,
+    // and the last chunk turns a distance into the covariance ----
+    pair_distances<T>(a, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool last) {
+      T* dst = row(r) + c;
+      if (d0 > 0) acc += *dst;
+      *dst = last ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
+    });
+    fill_diagonal<T>(row, a, idx, nb, k, tid, NT);
+    fill_responses<T>(row, a, idx, nb, k, R, tid, NT);
+    __syncthreads();
+
+    // ---- factor, finish ----
+    const bool bad = factor_augmented_slab<T>(row, k, rows, Lb, tid, NT);
+    T* mean = static_cast<T*>(a.mean);
+    T* var = static_cast<T*>(a.var);
+    T* yk = static_cast<T*>(a.ykinvy);
+    emit_outputs<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
+                    yk ? yk + nb * R : nullptr, tid);
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
 }
@@ -167,11 +178,11 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
 // its own)
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* workspace, int slab_elems) {
-  fused_large_body<T, false>(a, workspace, slab_elems, GenLaunch{});
+  fused_large_body<T>(a, workspace, slab_elems);
 }
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_gen_kernel(FusedArgs a, T* workspace, int slab_elems, GenLaunch g) {
-  fused_large_body<T, true>(a, workspace, slab_elems, g);
+  fused_large_gen_body<T>(a, workspace, slab_elems, g);
 }
 
 template <typename T>
@@ -205,8 +216,8 @@ __global__ void __launch_bounds__(512) solve_large_kernel(SolveArgs a, T* worksp
     T* mean = static_cast<T*>(a.mean);
     T* var = static_cast<T*>(a.var);
     T* yk = static_cast<T*>(a.ykinvy);
-    emit_outputs_slab<T>(row, k, R, (T)a.kout, bad, Kcross != nullptr, mean ? mean + nb * R : nullptr,
-                         var ? var + nb : nullptr, yk ? yk + nb * R : nullptr, tid);
+    emit_outputs<T>(row, k, R, (T)a.kout, bad, Kcross != nullptr, mean ? mean + nb * R : nullptr,
+                    var ? var + nb : nullptr, yk ? yk + nb * R : nullptr, tid);
     if (a.coeffs) {
       // back-substitution L^T x = L^-1 y_r of all R responses at once, in place in rows k+1+r, column by column
       // from the last: x[j] = w[j] / L[j][j], then w[m] -= L[j][m] x[j] for every m < j -- row j of L, read
@@ -237,7 +248,7 @@ __global__ void __launch_bounds__(512) solve_large_kernel(SolveArgs a, T* worksp
 template <typename T>
 static size_t fused_lds_bytes(int k, int dc) {
   size_t n = (size_t)((k + 2) & ~1) * sizeof(int64_t);
-  n += ((size_t)LNB * large_lp<T>() + (size_t)(k + 1) * (dc + 16 / sizeof(T)) + dc) * sizeof(T);
+  n += ((size_t)LNB * large_lp<T>() + (size_t)(k + 1) * tile_row_stride<T>(dc) + dc) * sizeof(T);
   return (n + 15) & ~(size_t)15;
 }
 

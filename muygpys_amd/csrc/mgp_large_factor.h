@@ -1,5 +1,5 @@
 // The slab of a local system beyond LDS and its blocked factorisation, shared by the forward kernels (mgp_large.hip)
-// and the hyper-parameter backward (mgp_backward_large.hip).
+// and the backward kernels on the slab (mgp_backward_large.h).  (The pair decoder of the triangle: mgp_assemble.h.)
 //
 // Slab: the lower trapezoid of the augmented system of mgp_lds_factor.h, row by row.  Row i < k holds its columns up
 // to the end of its 32-column block (32 (i / 32 + 1) elements), the trailing rows hold KP = 32 ceil(k / 32) each; every
@@ -36,16 +36,6 @@ static const int kMaxPerCu = 1;
 static inline int slab_block_threads(int rows) { return rows <= 128 ? 256 : 512; }
 // the slabs worth recommending for b systems: one per workgroup of a full grid
 static inline int64_t slab_count(int64_t b) { return capacity_grid(b < 1 ? 1 : b, 0, Capacity{kMaxPerCu}); }
-
-// p -> (row, col) of the strict lower triangle of the (k+1)-point set (8 p + 1 is an exact float for every p here,
-// p < 2^20; the two loops settle the last unit)
-__device__ __forceinline__ void large_tri_decode(int p, int& row, int& col) {
-  int a_ = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-  while (a_ * (a_ - 1) / 2 > p) --a_;
-  while ((a_ + 1) * a_ / 2 <= p) ++a_;
-  row = a_;
-  col = p - a_ * (a_ - 1) / 2;
-}
 
 template <typename T>
 struct SlabRows {

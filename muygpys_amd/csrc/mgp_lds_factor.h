@@ -248,14 +248,14 @@ __device__ inline bool factor_augmented_lds(T* S, int SP, int k, int rows, T* pi
   return factor_augmented_rows<T>(StridedRows<T>{S, SP}, k, rows, piv, bad_flag, tid, NT);
 }
 
-// mean (R), var, ykinvy (R) from the factored S: 1 + 2 R inner products of length k, each taken by
-// the whole first wave (lanes stride over the k entries, one cross-lane sum) -- one thread per output
-// walked its k entries alone, a serial chain of k LDS round trips at the end of every neighbourhood.
-template <typename T>
-__device__ inline void emit_outputs_lds(const T* S, int SP, int k, int R, T kout, bool bad, bool has_cross,
-                                        T* mean, T* var, T* ykinvy, int tid, int NT) {
+// mean (R), var, ykinvy (R) from the factored system, on any row layout: 1 + 2 R inner products of length k, each taken
+// by the whole first wave (lanes stride over the k entries, one cross-lane sum) -- one thread per output walked its k
+// entries alone, a serial chain of k round trips at the end of every neighbourhood.
+template <typename T, typename Rows>
+__device__ __forceinline__ void emit_outputs(Rows row, int k, int R, T kout, bool bad, bool has_cross, T* mean, T* var, T* ykinvy,
+                                             int tid) {
   if (tid >= MGP_WAVE) return;
-  const T* z = S + k * SP;
+  const T* z = row(k);
   for (int o = 0; o < 1 + 2 * R; ++o) {
     const T* x = z;
     const T* y = z;
@@ -263,10 +263,10 @@ __device__ inline void emit_outputs_lds(const T* S, int SP, int k, int R, T kout
     if (o == 0) {
       if (var != nullptr && has_cross) dst = var;
     } else if (o <= R) {
-      y = S + (k + o) * SP;
+      y = row(k + o);
       if (mean != nullptr && has_cross) dst = mean + (o - 1);
     } else {
-      x = y = S + (k + 1 + (o - R - 1)) * SP;
+      x = y = row(k + 1 + (o - R - 1));
       if (ykinvy != nullptr) dst = ykinvy + (o - R - 1);
     }
     if (dst == nullptr) continue;  // uniform

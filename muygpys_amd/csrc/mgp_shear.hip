@@ -13,6 +13,7 @@
 // n elimination steps of factor_augmented_rows leave K_c^T K^-1 K_c, the 3 means and y^T K^-1 y as
 // inner products of the trailing rows (emit_block_outputs): no back-substitution.
 #include "mgp_args.h"
+#include "mgp_assemble.h"
 #include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
@@ -169,10 +170,8 @@ __global__ void __launch_bounds__(256) shear_posterior_kernel(ShearArgs a) {
     __syncthreads();
     // strictly lower pairs (i, j), i > j, of the k + 1 points (point k = the query): one exp per pair
     for (int p = tid; p < npairs; p += NT) {
-      int i = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)p)) * 0.5f);
-      while (i * (i - 1) / 2 > p) --i;
-      while ((i + 1) * i / 2 <= p) ++i;
-      const int j = p - i * (i - 1) / 2;
+      int i, j;
+      tri_decode(p, i, j);
       T B[3][3];
       shear_block<T>(pts[2 * i] - pts[2 * j], pts[2 * i + 1] - pts[2 * j + 1], ell, B);
       if (i < k) {
