@@ -440,6 +440,34 @@ int mgp_fast_coefficients_f64(const double* feat, int d, const int64_t* nn_idx, 
                               int kernel_id, int metric_id, const double* length_scale, int ls_count,
                               double* coeffs, int* info, void* stream);
 
+/* The same precompute for any k >= 1 and any response count with k + 1 + response_count <= 1024:
+ * coeffs (b, k, R) = (K_b + eps)^-1 Y_b, Y_b the rows nn_idx[b] of targets (n, R) -- gather -> distances -> kernel ->
+ * nugget -> Cholesky -> back-substitution of all R columns in one launch, nothing of size (b, k, k) in memory.
+ *   k <= mgp_max_nn_count(elem_size, R): the workgroup kernel with the system in LDS; needs no workspace
+ *       (mgp_fast_coefficients_workspace_bytes returns 0, `workspace` may be NULL and is not looked at).
+ *   beyond: the blocked factorisation on a slab of the caller's workspace, under the workspace contract of
+ *       mgp_posterior_large_* (16-byte aligned, at least one slab = mgp_fast_coefficients_workspace_bytes(elem_size, k,
+ *       R, 1); any workspace of at least one slab gives the same bits, a smaller one is only slower).
+ *   mgp_fast_coefficients_workspace_bytes: the recommended size for a batch of b (at most 512 MiB); 0 where none is
+ *       needed and for arguments the entry does not serve.
+ * What a neighbourhood returns does not depend on its place in the batch, the grid or the workspace.  A neighbourhood
+ * that is not positive definite returns NaN in its (k, R) block and counts one in *info (info may be NULL).  The five
+ * closed-form kernels, both metrics, scalar or per-feature length scale, the three noise modes.
+ * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), the empty batch (MGP_OK, nothing else looked at),
+ * pointers, ids, a noise mode without noise_dev, ls_count not in {1, d} and a needed workspace that is NULL, misaligned
+ * or under one slab (MGP_EINVAL), then k + 1 + R > 1024 or MGP_KERNEL_MATERN_GEN: MGP_EUNSUPPORTED. */
+int64_t mgp_fast_coefficients_workspace_bytes(int elem_size, int k, int response_count, int64_t b);
+int mgp_fast_coefficients_any_f32(const float* feat, int d, const int64_t* nn_idx, int64_t b, int k,
+                                  const float* targets, int R, int noise_mode, double noise_scalar,
+                                  const float* noise_dev, int kernel_id, int metric_id, const float* length_scale,
+                                  int ls_count, float* coeffs, int* info, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+int mgp_fast_coefficients_any_f64(const double* feat, int d, const int64_t* nn_idx, int64_t b, int k,
+                                  const double* targets, int R, int noise_mode, double noise_scalar,
+                                  const double* noise_dev, int kernel_id, int metric_id, const double* length_scale,
+                                  int ls_count, double* coeffs, int* info, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 /* The selection steps around the scans (round 6; torch's topk / argsort did them until then: a quarter of a search's time).
  * Reference: scikit-learn's brute-force kneighbors behind NN_Wrapper.get_nns / get_batch_nns
  * (src/MuyGPyS/neighbors.py:129-211): exact neighbours in ascending order of distance.
@@ -832,6 +860,8 @@ int mgp_posterior_backward_large_f64(const double* feat_q, const double* feat_nn
  * coeffs (n_train, k, R) = mgp_solve_* `coeffs` output of the self-including neighbourhoods
  * (_muygps_fast_posterior_mean_precompute, numpy.py:88-95); coeff_row (b) = the closest
  * training point of each test point; nn_idx (b, k) = that point's neighbourhood.
+ * Every k >= 1: up to k + 1 <= 64 one test point per 32 or 64 lanes, beyond that one test point per wave in passes of
+ * 64 neighbours; no workspace.  MGP_KERNEL_MATERN_GEN is not a kernel id of this entry (MGP_EINVAL).
  * ------------------------------------------------------------------------- */
 int mgp_fast_posterior_mean_f32(const float* feat_q, const float* feat_nn, int d, const int64_t* batch_idx,
                                 const int64_t* nn_idx, int64_t b, int k, const float* coeffs,

@@ -156,8 +156,34 @@ def _muygps_diagonal_variance(Kin, Kcross, Kout, batch_size: int = 1, **kwargs):
     return var
 
 
+def _precompute_fused(Kin, train_nn_targets_fast):
+    """A lazy pairwise covariance handle and the lazy gather of one response table over the same index list -- what
+    ``pairwise_tensor -> kernel -> noise.perturb`` and ``train_targets[nn_indices_fast]`` leave on lazy handles --
+    through the fused coefficient launch (``muygpys_amd.fused._fused_coefficients``: nothing of size (b, k, k) is
+    formed).  None when the handles are not such a pair (the recognisers of ``lazy.fused_triple``, without a
+    crosswise side) or the library refuses the model: the caller then forces the handles and solves."""
+    from muygpys_amd.fused import _fused_coefficients, _normalize
+    from muygpys_amd.lazy_eval import _spec
+
+    if not (isinstance(Kin, lazy.LazyCov) and isinstance(train_nn_targets_fast, lazy.LazyTargets)):
+        return None
+    a, t = Kin.diffs, train_nn_targets_fast
+    if Kin.kernel == "matern_gen":  # (no fused coefficient kernel evaluates the general nu: force and solve)
+        return None
+    if not (a.kind == "pairwise" and a.reduced and a.metric in ("l2", "F2") and not t.swapped
+            and lazy._same_tensor(a.nn_indices, t.nn_indices) and t.targets.ndim in (1, 2)
+            and t.targets.dtype == a.dtype and t.targets.shape[0] == a.nn_data.shape[0]):
+        return None
+    spec = _spec(Kin)
+    inp = _normalize(spec, a.nn_data, a.nn_data, None, a.nn_indices, t.targets)
+    return _fused_coefficients(spec, inp)
+
+
 def _muygps_fast_posterior_mean_precompute(Kin, train_nn_targets_fast, **kwargs):
-    """numpy.py:88-95: coefficients Kin^-1 Y, squeezed."""
+    """numpy.py:88-95: coefficients Kin^-1 Y, squeezed.  On lazy handles: one fused launch (:func:`_precompute_fused`)."""
+    co = _precompute_fused(Kin, train_nn_targets_fast)
+    if co is not None:
+        return torch.squeeze(co)
     Kin, train_nn_targets_fast = lazy.force(Kin), lazy.force(train_nn_targets_fast)
     Y = train_nn_targets_fast if train_nn_targets_fast.ndim == 3 else train_nn_targets_fast[:, :, None]
     _, _, _, co = _solve(Kin, None, Y, want=("coeffs",))
@@ -167,27 +193,9 @@ def _muygps_fast_posterior_mean_precompute(Kin, train_nn_targets_fast, **kwargs)
 def _fast_mean_fused(Kcross, coeffs_tensor):
     """A lazy crosswise covariance handle and the gathered coefficients ``coeffs[closest_index]`` (b, k[, R]) --
     what the reference's workflow hands over (examples/from_indices.py:113-118) -- through the fused prediction kernel
-    (``mgp_fast_posterior_mean_*``: gather, distances, kernel, dot product in one launch; nothing of size (b, k) is
-    formed).  None when the handle is not a plain crosswise covariance the kernel evaluates, or the neighbourhood has
-    more slots than a wavefront (``k + 1 > 64``: mgp_fast_mean.hip serves one test point per 32 or 64 lanes) -- the
-    caller then materialises the handle and takes the reference's einsum."""
-    from muygpys_amd.fused import FusedUnsupported, KernelSpec, fast_posterior_mean
-
-    c = Kcross.diffs
-    if not (c.kind == "crosswise" and c.reduced and c.metric in ("l2", "F2") and Kcross.kernel != "matern_gen"):
-        return None
-    if not (isinstance(coeffs_tensor, torch.Tensor) and coeffs_tensor.is_cuda and coeffs_tensor.ndim in (2, 3)):
-        return None
-    b, k = c.nn_indices.shape
-    if tuple(coeffs_tensor.shape[:2]) != (b, k) or coeffs_tensor.dtype != c.dtype or k + 1 > 64:
-        return None
-    spec = KernelSpec(Kcross.kernel, c.metric, 1.0 if c.length_scale is None else c.length_scale, 0.0)
-    rows = torch.arange(b, device=coeffs_tensor.device)
-    try:
-        out = fast_posterior_mean(spec, c.data, c.nn_data, c.data_indices, c.nn_indices, coeffs_tensor, rows)
-    except FusedUnsupported:
-        return None
-    return torch.squeeze(out)
+    (:func:`muygpys_amd.lazy_eval.fast_mean`), for any nn_count.  None when the handle is not a plain crosswise
+    covariance the kernel evaluates -- the caller then materialises the handle and takes the reference's einsum."""
+    return lazy_eval.fast_mean(Kcross, coeffs_tensor)
 
 
 def _muygps_fast_posterior_mean(Kcross, coeffs_tensor, **kwargs):

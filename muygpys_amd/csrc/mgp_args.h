@@ -21,7 +21,7 @@ struct FusedArgs {
   int64_t b;
   double noise_scalar;
   int d, k, R, noise_mode, kernel_id, metric_id, ls_count, dc;
-  void* coeffs = nullptr;  // (b, k) K^-1 y per neighbourhood (fused fast-mean precompute), or nullptr
+  void* coeffs = nullptr;  // (b, k, R) K^-1 y per neighbourhood (fused fast-mean precompute: the wave kernels at R = 1, the coefficient instantiations of the LDS and slab kernels), or nullptr
   // prepared tables (mgp_table_pack_*): rows [features d | responses R | pad], byte strides; when
   // packed_nn is set feat_q / feat_nn / targets are not read by the pipelined wave kernels
   // targets_batch != 0: `targets` is the already gathered (b, k, R) tensor (what the reference's

@@ -56,6 +56,11 @@ __device__ __forceinline__ void fill_index_list(int64_t* idx, const FusedArgs& a
   for (int r = tid; r <= k; r += NT)
     idx[r] = r < k ? a.nn_idx[nb * k + r] : (a.batch_idx ? a.batch_idx[nb] : nb);
 }
+// ... of a launch without a query (the coefficient precompute, feat_q == feat_nn): the query slot is fed the first
+// neighbour, whose row exists whatever b is; nothing of that slot is stored
+__device__ __forceinline__ void fill_index_list_no_query(int64_t* idx, const FusedArgs& a, int64_t nb, int k, int tid, int NT) {
+  for (int r = tid; r <= k; r += NT) idx[r] = a.nn_idx[nb * k + (r < k ? r : 0)];
+}
 
 // Squared (scaled, under Anisotropy) distances of the (k+1) k / 2 pairs of the (k+1)-point set, one chunk of a.dc
 // features at a time: the chunk's rows are staged in X (row stride XP = tile_row_stride(dc)), the inverse length

@@ -238,6 +238,30 @@ int posterior_large(const T* fq, const T* fn, int d, const int64_t* bi, const in
   return launch_fused_large<T>(a, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses rows > 1024 and the general nu)
 }
 
+// the fast-mean precompute for any k and response count: the system in LDS up to mgp_max_nn_count (no workspace), on a
+// slab of the caller's workspace beyond; the checks in the order of posterior_large
+// (a system beyond the slab kernel: its workspace is checked like any other before the shape is refused)
+static bool coefficients_need_workspace(int elem_size, int k, int R) {
+  return (int64_t)k + 1 + R > kLargeMaxRows || k > max_nn_count(elem_size, R);
+}
+
+template <typename T>
+int fast_coefficients_any(const T* fn, int d, const int64_t* ni, int64_t b, int k, const T* tg, int R, int noise_mode,
+                          double eps, const T* nd, int kernel_id, int metric_id, const T* ls, int ls_count, T* coeffs,
+                          int* info, void* ws, int64_t ws_bytes, void* stream) {
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | KERNEL_MAY_BE_GEN, fn, fn, d, nullptr, ni, b, k, tg, R, noise_mode, eps,
+                                  nd, kernel_id, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (!coeffs) return MGP_EINVAL;
+  const bool large = coefficients_need_workspace(sizeof(T), k, R);
+  if (large && !valid_workspace(ws, ws_bytes, sizeof(T), k, R)) return MGP_EINVAL;
+  if ((int64_t)k + 1 + R > kLargeMaxRows || kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
+  a.coeffs = coeffs;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return large ? launch_fused_large<T>(a, ws, ws_bytes, s) : launch_fused_generic<T>(a, s);
+}
+
 template <typename T>
 int solve_large(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, double kout, T* mean, T* var, T* yk,
                 T* coeffs, int* info, void* ws, int64_t ws_bytes, void* stream) {
@@ -680,6 +704,20 @@ int mgp_knn_scan_bf16x2_d8(const float* train, const void* packed_train, const f
   }
 MGP_DEFINE_COEF(f32, float)
 MGP_DEFINE_COEF(f64, double)
+
+int64_t mgp_fast_coefficients_workspace_bytes(int elem_size, int k, int R, int64_t b) {
+  if ((elem_size != 4 && elem_size != 8) || k < 1 || R < 1 || b < 0 || (int64_t)k + 1 + R > kLargeMaxRows) return 0;
+  return coefficients_need_workspace(elem_size, k, R) ? large_workspace_bytes(elem_size, k, R, b) : 0;
+}
+#define MGP_DEFINE_COEF_ANY(SUF, T)                                                                                 \
+  int mgp_fast_coefficients_any_##SUF(const T* fn, int d, const int64_t* ni, int64_t b, int k, const T* tg, int R,   \
+                                      int nm, double eps, const T* nd, int kid, int mid, const T* ls, int lsc,       \
+                                      T* coeffs, int* info, void* workspace, int64_t workspace_bytes, void* st) {    \
+    return fast_coefficients_any<T>(fn, d, ni, b, k, tg, R, nm, eps, nd, kid, mid, ls, lsc, coeffs, info, workspace, \
+                                    workspace_bytes, st);                                                            \
+  }
+MGP_DEFINE_COEF_ANY(f32, float)
+MGP_DEFINE_COEF_ANY(f64, double)
 
 #define MGP_DEFINE_BWD(SUF, T)                                                                                      \
   int mgp_posterior_backward_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, \

@@ -17,6 +17,12 @@
 // LDS with the same row-walking 16-byte gather as the fused kernel, lane i then owns neighbour
 // i: difference-form distance to the query row, kernel, product with its coefficient(s), and a
 // cross-lane sum.
+//
+// Beyond 64 slots (any k, fast_mean_wide_kernel): one wave owns one test point and walks its neighbours in passes of
+// 64 through the same tile; the covariances of all k neighbours wait in LDS and one cross-lane sum per response closes
+// the point.  The wave-per-point form is the one kept for every k > 63: a workgroup-per-point form for the widest
+// lists was not built -- the kernel moves (k+1) d s bytes per point whatever the form, and the persistent grid already
+// holds sixteen independent waves per CU.
 #include "mgp_args.h"
 #include "mgp_launch.h"
 
@@ -161,6 +167,140 @@ static int launch_fast_np(FastArgs a, hipStream_t stream) {
   return MGP_OK;
 }
 
+// k + 1 > 64: one test point per wave, the neighbours in passes of 64 (lane i owns neighbours i, i + 64, ...).  Per
+// feature chunk the query row is staged once (tile row 64) and every pass gathers its 64 neighbour rows into rows
+// 0 .. 63 with the row-walking gather above; a neighbour's partial squared distance waits in kv[] between chunks (its
+// own lane writes and reads it), the last chunk leaves the covariance there.  Then, per response, every lane sums its
+// products over the passes and ONE cross-lane reduction closes the sum.
+// The gather of a pass is fast_mean_kernel's, written out a second time with the pass's row count and source in place
+// of (k + 1 rows, the query among them): sharing it as a device function would put the 32- and 64-slot instantiations
+// through a new inlining decision, and their code is to stay what it was (same bits, same rate); a change to the
+// gather's layout has to be made in both places.
+// dynamic LDS carve: [idx: 64 int64][tile: 65 * xs T][il: dst T][kv: 64 ceil(k / 64) T]
+template <typename T>
+__global__ __launch_bounds__(64) void fast_mean_wide_kernel(FastArgs a) {
+  constexpr int E = fv16<T>::N;
+  constexpr int CH = 2 * E;
+  using V = typename fv16<T>::type;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int k = a.k, d = a.d, R = a.R, xs = a.xs, dst = a.dst;
+  const int npass = (k + 63) / 64;
+  int64_t* idxbuf = reinterpret_cast<int64_t*>(smem);
+  T* tile = reinterpret_cast<T*>(idxbuf + 64);
+  T* xq = tile + 64 * xs;
+  T* ilbuf = tile + 65 * xs;
+  T* kv = ilbuf + dst;
+
+  const T* feat_q = static_cast<const T*>(a.feat_q);
+  const T* feat_nn = static_cast<const T*>(a.feat_nn);
+  const T* coeffs = static_cast<const T*>(a.coeffs);
+  const T* ls = static_cast<const T*>(a.length_scale);
+  T* mean = static_cast<T*>(a.mean);
+  const bool aniso = a.ls_count > 1;
+  T post_scale = T(1);
+  if (!aniso) {
+    const T l = ls[0];
+    post_scale = a.metric_id == MGP_METRIC_L2 ? T(1) / l : T(1) / (l * l);
+  }
+  const int lane = threadIdx.x;
+
+  for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
+    const int64_t* nrow = a.nn_idx + nb * k;
+    const T* qrow = feat_q + (a.batch_idx ? a.batch_idx[nb] : nb) * (int64_t)d;
+    const int64_t crow = a.coeff_row[nb];
+    for (int d0 = 0; d0 < d; d0 += dst) {
+      const int w = min(dst, d - d0);
+      const int wp = (w + CH - 1) / CH * CH;
+      const bool last = d0 + dst >= d;
+      __syncthreads();  // the tile's and kv's readers of the chunk / the test point before are done
+      if (a.vec_ok) {
+        if (lane < wp / E) *reinterpret_cast<V*>(xq + lane * E) = lane < w / E ? *reinterpret_cast<const V*>(qrow + d0 + lane * E) : V(0);
+      } else {
+        for (int c = lane; c < wp; c += 64) xq[c] = c < w ? qrow[d0 + c] : T(0);
+      }
+      if (aniso)
+        for (int c = lane; c < wp; c += 64) ilbuf[c] = c < w ? T(1) / ls[d0 + c] : T(0);
+      for (int p = 0; p < npass; ++p) {
+        const int i = p * 64 + lane;
+        const int nrows = min(64, k - p * 64);
+        if (p > 0) __syncthreads();  // the pass before has read its rows
+        idxbuf[lane] = i < k ? nrow[i] * (int64_t)d : 0;
+        __syncthreads();
+        if (a.vec_ok) {
+          const int c16 = w / E, c16p = wp / E;
+          const int rpr = 64 / c16p;
+          const int sub = (int)(((unsigned)lane * ((1u << 16) / (unsigned)c16p + 1u)) >> 16);
+          const int c = lane - sub * c16p;
+          const bool lane_on = sub < rpr;
+          constexpr int U = 6;
+          for (int r0 = 0; r0 < nrows; r0 += U * rpr) {
+            V v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              const int row = r0 + u * rpr + sub;
+              v[u] = V(0);
+              if (lane_on && row < nrows && c < c16) v[u] = *reinterpret_cast<const V*>(feat_nn + idxbuf[row] + d0 + c * E);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              const int row = r0 + u * rpr + sub;
+              if (lane_on && row < nrows) *reinterpret_cast<V*>(tile + row * xs + c * E) = v[u];
+            }
+          }
+        } else {
+          const unsigned magic = (1u << 20) / (unsigned)wp + 1u;
+          for (int t = lane; t < nrows * wp; t += 64) {
+            const int row = (int)(((unsigned)t * magic) >> 20);
+            const int c = t - row * wp;
+            tile[row * xs + c] = c < w ? (feat_nn + idxbuf[row] + d0)[c] : T(0);
+          }
+        }
+        __syncthreads();
+        if (i < k) {
+          const T* xo = tile + lane * xs;
+          T acc = d0 > 0 ? kv[i] : T(0);
+          for (int c0 = 0; c0 < wp; c0 += E) {
+            V df = *reinterpret_cast<const V*>(xq + c0) - *reinterpret_cast<const V*>(xo + c0);
+            if (aniso) df = df * *reinterpret_cast<const V*>(ilbuf + c0);
+#pragma unroll
+            for (int e = 0; e < E; ++e) acc += df[e] * df[e];
+          }
+          kv[i] = last ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
+        }
+      }
+    }
+    __syncthreads();
+    const T* co = coeffs + crow * (int64_t)k * R;
+    for (int r = 0; r < R; ++r) {
+      T part = T(0);
+      for (int i = lane; i < k; i += 64) part += kv[i] * co[i * (int64_t)R + r];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+      if (lane == 0) mean[nb * R + r] = part;
+    }
+  }
+}
+
+template <typename T>
+static int launch_fast_wide(FastArgs a, hipStream_t stream) {
+  constexpr int E = fv16<T>::N;
+  constexpr int CH = 2 * E;
+  const int dpad = (a.d + CH - 1) / CH * CH;
+  a.dst = dpad < 64 ? dpad : 64;
+  a.xs = a.dst + E;
+  const uintptr_t align = (uintptr_t)a.feat_q | (uintptr_t)a.feat_nn;
+  a.vec_ok = (a.d % E == 0) && (align % 16 == 0);
+  // at most 64 (8) + 65 * 66 + 64 + 1024 fp64 elements = 44 KiB (k <= 1023, the chunk of 64 features); d = 8, k = 100
+  // in fp32: 4.4 KiB, as many waves per CU as the grid below asks for
+  size_t lds = 64 * sizeof(int64_t) + ((size_t)65 * a.xs + a.dst + (size_t)(a.k + 63) / 64 * 64) * sizeof(T);
+  lds = (lds + 15) & ~(size_t)15;
+  int64_t grid = kAssumedCus * 16;  // memory-bound: grid-stride over plenty of resident waves
+  if (grid > a.b) grid = a.b;
+  hipLaunchKernelGGL((fast_mean_wide_kernel<T>), dim3((unsigned)grid), dim3(64), lds, stream, a);
+  MGP_HIP_CHECK_LAUNCH();
+  return MGP_OK;
+}
+
 template <typename T>
 int launch_fast_mean(const void* fq, const void* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
                      const void* coeffs, const int64_t* crow, int R, int kernel_id, int metric_id, const void* ls,
@@ -168,7 +308,7 @@ int launch_fast_mean(const void* fq, const void* fn, int d, const int64_t* bi, c
   FastArgs a{fq, fn, bi, ni, coeffs, crow, ls, mean, b, d, k, R, kernel_id, metric_id, ls_count, 0, 0, 0};
   if (k + 1 <= 32) return launch_fast_np<T, 32>(a, stream);
   if (k + 1 <= 64) return launch_fast_np<T, 64>(a, stream);
-  return MGP_EUNSUPPORTED;
+  return launch_fast_wide<T>(a, stream);
 }
 
 template int launch_fast_mean<float>(const void*, const void*, int, const int64_t*, const int64_t*, int64_t, int,

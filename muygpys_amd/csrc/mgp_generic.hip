@@ -8,6 +8,7 @@
 #include "mgp_args.h"
 #include "mgp_assemble.h"
 #include "mgp_gen_launch.h"
+#include "mgp_large_factor.h"
 #include "mgp_launch.h"
 #include "mgp_lds_factor.h"
 
@@ -17,7 +18,10 @@ namespace mgp {
 // [idx: (k+2 & ~1) int64][S: rows*SP T][X: (k+1)*XP T][il: dc T][piv: k T][flag]
 // GEN (the general-smoothness Matern, a.smoothness): + [node table: 2 MGP_GEN_NODES float / 2 MGP_GEN_NODES64 double]
 // at byte g.tab, behind everything else; the closed-form instantiations reserve and read nothing of `g`.
-template <typename T, bool GEN>
+// COEFFS (a.coeffs set, no query, no mean / var / yKinvy: the fast-mean precompute): the back-substitution behind the
+// factorisation, K^-1 y_r into a.coeffs (b, k, R).  An instantiation of its own, so that the kernels of every other
+// entry are compiled from what they always were.
+template <typename T, bool GEN, bool COEFFS = false>
 __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const GenLaunch& g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int k = a.k, R = a.R, dc = a.dc;
@@ -38,7 +42,8 @@ __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const Gen
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
-    fill_index_list(idx, a, nb, k, tid, NT);
+    if constexpr (COEFFS) fill_index_list_no_query(idx, a, nb, k, tid, NT);
+    else fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
 
     // ---- assemble: squared distances summed over the feature chunks in S, covariances in place in a second pass, the
@@ -72,14 +77,21 @@ __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const Gen
     T* yk = static_cast<T*>(a.ykinvy);
     emit_outputs<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
                     yk ? yk + nb * R : nullptr, tid);
+    if constexpr (COEFFS) {
+      // all R responses at once, column by column across the workgroup (piv: the inverse pivots)
+      if (a.coeffs)
+        back_substitute_columns<T>(row, k, R, [&](int j) { return piv[j]; }, bad, static_cast<T*>(a.coeffs) + nb * (int64_t)k * R, tid, NT);
+    }
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
 }
 
-// the closed-form kernels, and the general-smoothness Matern under a name of its own (its constants: an argument of
-// its own)
+// the closed-form kernels, the same with the coefficient output, and the general-smoothness Matern under a name of its
+// own (its constants: an argument of its own)
 template <typename T>
 __global__ void fused_generic_kernel(FusedArgs a) { fused_generic_body<T, false>(a, GenLaunch{}); }
+template <typename T>
+__global__ void fused_generic_coeffs_kernel(FusedArgs a) { fused_generic_body<T, false, true>(a, GenLaunch{}); }
 template <typename T>
 __global__ void fused_generic_gen_kernel(FusedArgs a, GenLaunch g) { fused_generic_body<T, true>(a, g); }
 
@@ -166,9 +178,10 @@ static int launch_fused_generic_impl(const FusedArgs& in, hipStream_t stream) {
     g = gen_launch_constants(a.smoothness, sizeof(T) == 8);
     g.tab = (int)(fc.lds - table);
   }
-  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic%s_kernel<%s>", GEN ? "_gen" : "", sizeof(T) == 4 ? "float" : "double");
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic%s_kernel<%s>", GEN ? "_gen" : a.coeffs ? "_coeffs" : "", sizeof(T) == 4 ? "float" : "double");
   const int threads = lds_factor_threads(a.k + 1 + a.R);
-  if constexpr (GEN) return launch_capacity(&fused_generic_gen_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a, g).status;
+  if constexpr (GEN) return a.coeffs ? MGP_EUNSUPPORTED : launch_capacity(&fused_generic_gen_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a, g).status;
+  else if (a.coeffs) return launch_capacity(&fused_generic_coeffs_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a).status;
   else return launch_capacity(&fused_generic_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a).status;
 }
 template <typename T>

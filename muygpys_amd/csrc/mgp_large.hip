@@ -130,7 +130,9 @@ __device__ __forceinline__ void fused_large_gen_body(const FusedArgs& a, T* work
 }
 
 // dynamic LDS carve (every array 16-byte aligned): [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T]
-template <typename T>
+// COEFFS (a.coeffs set, no query, no mean / var / yKinvy: the fast-mean precompute): the back-substitution behind the
+// factorisation, K^-1 y_r into a.coeffs (b, k, R) -- an instantiation of its own, as in mgp_generic.hip.
+template <typename T, bool COEFFS = false>
 __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspace, int slab_elems) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int k_ = a.k, R_ = a.R, dc = a.dc;
@@ -149,7 +151,8 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
     asm volatile("" : "+s"(k), "+s"(R));
     const int rows = k + 1 + R;
     const SlabRows<T> row{workspace + (int64_t)blockIdx.x * slab_elems, k};
-    fill_index_list(idx, a, nb, k, tid, NT);
+    if constexpr (COEFFS) fill_index_list_no_query(idx, a, nb, k, tid, NT);
+    else fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
 
     // ---- assemble: the chunks' rows are staged in LDS, the partial sums of the squared distances live in the slab,
@@ -170,15 +173,23 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
     T* yk = static_cast<T*>(a.ykinvy);
     emit_outputs<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
                     yk ? yk + nb * R : nullptr, tid);
+    if constexpr (COEFFS) {
+      if (a.coeffs)  // (the diagonal holds the inverse pivots)
+        back_substitute_columns<T>(row, k, R, [&](int j) { return row(j)[j]; }, bad, static_cast<T*>(a.coeffs) + nb * (int64_t)k * R, tid, NT);
+    }
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
 }
 
-// the closed-form kernels, and the general-smoothness Matern under a name of its own (its constants: an argument of
-// its own)
+// the closed-form kernels, the same with the coefficient output, and the general-smoothness Matern under a name of its
+// own (its constants: an argument of its own)
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* workspace, int slab_elems) {
   fused_large_body<T>(a, workspace, slab_elems);
+}
+template <typename T>
+__global__ void __launch_bounds__(512) fused_large_coeffs_kernel(FusedArgs a, T* workspace, int slab_elems) {
+  fused_large_body<T, true>(a, workspace, slab_elems);
 }
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_gen_kernel(FusedArgs a, T* workspace, int slab_elems, GenLaunch g) {
@@ -219,23 +230,8 @@ __global__ void __launch_bounds__(512) solve_large_kernel(SolveArgs a, T* worksp
     emit_outputs<T>(row, k, R, (T)a.kout, bad, Kcross != nullptr, mean ? mean + nb * R : nullptr,
                     var ? var + nb : nullptr, yk ? yk + nb * R : nullptr, tid);
     if (a.coeffs) {
-      // back-substitution L^T x = L^-1 y_r of all R responses at once, in place in rows k+1+r, column by column
-      // from the last: x[j] = w[j] / L[j][j], then w[m] -= L[j][m] x[j] for every m < j -- row j of L, read
-      // contiguously by consecutive threads
-      T* co = static_cast<T*>(a.coeffs) + nb * (int64_t)k * R;
-      for (int j = k - 1; j >= 0; --j) {
-        __syncthreads();  // the outputs' reads / the updates of column j + 1 are done
-        const T* Lj = row(j);
-        const T ivj = Lj[j];
-        for (int r = tid; r < R; r += NT) co[j * (int64_t)R + r] = bad ? num<T>::nan() : row(k + 1 + r)[j] * ivj;
-        for (int m = tid; m < j; m += NT) {
-          const T l = Lj[m] * ivj;
-          for (int r = 0; r < R; ++r) {
-            T* w = row(k + 1 + r);
-            w[m] -= l * w[j];
-          }
-        }
-      }
+      // back-substitution of all R responses at once, in place in rows k+1+r (the diagonal holds the inverse pivots)
+      back_substitute_columns<T>(row, k, R, [&](int j) { return row(j)[j]; }, bad, static_cast<T*>(a.coeffs) + nb * (int64_t)k * R, tid, NT);
     }
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
@@ -286,11 +282,13 @@ static int launch_fused_large_impl(const FusedArgs& in, void* workspace, int64_t
     g = gen_launch_constants(a.smoothness, sizeof(T) == 8);
     g.tab = (int)(fc.lds - table);
   }
-  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large%s_kernel<%s>", GEN ? "_gen" : "", sizeof(T) == 4 ? "float" : "double");
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large%s_kernel<%s>", GEN ? "_gen" : a.coeffs ? "_coeffs" : "", sizeof(T) == 4 ? "float" : "double");
   const int threads = slab_block_threads((int)rows), slab_elems = (int)(slab / (int64_t)sizeof(T));
   const Capacity cap{kMaxPerCu, workspace_bytes / slab};
   if constexpr (GEN)
-    return launch_capacity(&fused_large_gen_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems, g).status;
+    return a.coeffs ? MGP_EUNSUPPORTED : launch_capacity(&fused_large_gen_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems, g).status;
+  else if (a.coeffs)
+    return launch_capacity(&fused_large_coeffs_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems).status;
   else
     return launch_capacity(&fused_large_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems).status;
 }

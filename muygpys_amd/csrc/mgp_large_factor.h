@@ -286,4 +286,27 @@ __device__ __forceinline__ bool factor_augmented_slab(SlabRows<T> row, int k, in
   return bad;
 }
 
+// Back-substitution L^T x = L^-1 y_r of all R responses at once behind a factorisation that left L^-1 y_r in rows
+// k + 1 + r (factor_augmented_slab, factor_augmented_rows), on any row layout, in place, column by column from the
+// last: x[j] = w[j] / L[j][j], then w[m] -= L[j][m] x[j] for every m < j -- row j of L, read contiguously by consecutive
+// threads, one barrier per column.  inv_pivot(j) = 1 / L[j][j] (the slab keeps it on the diagonal, the LDS factor in a
+// list of its own).  co: the (k, R) coefficients of this neighbourhood; NaN behind a bad pivot.  The first barrier
+// stands between the caller's reads of the tail rows and their updates.
+template <typename T, typename Rows, typename InvPivot>
+__device__ __forceinline__ void back_substitute_columns(Rows row, int k, int R, InvPivot inv_pivot, bool bad, T* co, int tid, int NT) {
+  for (int j = k - 1; j >= 0; --j) {
+    __syncthreads();  // the outputs' reads / the updates of column j + 1 are done
+    const T* Lj = row(j);
+    const T ivj = inv_pivot(j);
+    for (int r = tid; r < R; r += NT) co[j * (int64_t)R + r] = bad ? num<T>::nan() : row(k + 1 + r)[j] * ivj;
+    for (int m = tid; m < j; m += NT) {
+      const T l = Lj[m] * ivj;
+      for (int r = 0; r < R; ++r) {
+        T* w = row(k + 1 + r);
+        w[m] -= l * w[j];
+      }
+    }
+  }
+}
+
 }  // namespace mgp

@@ -932,7 +932,9 @@ def fast_posterior_mean(
     ``closest_set (b, k)`` is the self-including neighbourhood of each test point's closest
     training point ``closest_neighbor (b,)`` and ``coeffs (n_train, k[, R])`` the coefficient
     table (reference workflow: examples/fast_posterior_mean.py:373-400; maths
-    _src/gp/muygps/numpy.py:70-77).  Returns ``(b,)`` or ``(b, R)``."""
+    _src/gp/muygps/numpy.py:70-77).  Returns ``(b,)`` or ``(b, R)``.  Any ``nn_count``: up to 64 slots one test point per
+    32 or 64 lanes, beyond that one test point per wave in passes of 64 neighbours (csrc/mgp_fast_mean.hip);
+    :class:`FusedUnsupported` only follows a status the library really returns."""
     _lib.require_cuda(coeffs, closest_neighbor)
     inp = _normalize(spec, test_features, train_features, test_indices, closest_set, want_noise=False)
     fq, fn, bi, ni, b, k, d, ls, dtype = inp.fq, inp.fn, inp.bi, inp.ni, inp.b, inp.k, inp.d, inp.ls, inp.fn.dtype
@@ -948,9 +950,51 @@ def fast_posterior_mean(
         spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(mean), _lib.stream_ptr(),
     )
     if rc == _lib.EUNSUPPORTED:
-        raise FusedUnsupported(f"mgp_fast_posterior_mean serves k + 1 <= 64 slots; got nn_count = {k}")
+        raise FusedUnsupported(f"mgp_fast_posterior_mean refused kernel {spec.kernel!r} at nn_count = {k}, {R} response column(s)")
     _lib.check(rc, "mgp_fast_posterior_mean")
     return mean.reshape(b) if squeeze else mean
+
+
+def _coefficients_workspace(dtype, k: int, R: int, b: int, device) -> Optional[torch.Tensor]:
+    """The workspace of one ``mgp_fast_coefficients_any_*`` call (``mgp_fast_coefficients_workspace_bytes``), from torch's
+    stream-ordered allocator; None where the system fits LDS and the call needs none."""
+    size = int(_lib.load().mgp_fast_coefficients_workspace_bytes(4 if dtype == torch.float32 else 8, k, R, b))
+    return torch.empty(size, dtype=torch.uint8, device=device) if size > 0 else None
+
+
+def _fused_coefficients(spec: KernelSpec, inp: _Inputs) -> Optional[torch.Tensor]:
+    """``(K_b + eps)^-1 Y_b`` (b, k, R) of the neighbourhoods ``inp.ni`` of one table in ONE launch: the wave kernel
+    (``mgp_fast_coefficients_*``: one response, k <= 62) where it serves the shape, else ``mgp_fast_coefficients_any_*``
+    (the system in LDS, or on a slab of a workspace beyond ``mgp_max_nn_count``).  None, without a call, for what no fused
+    coefficient kernel serves -- the general-smoothness Matern (not a kernel id of the wave entry at all) and systems of
+    more than 1024 rows (``nn_count + 1 + R``) -- and when the library refuses (``MGP_EUNSUPPORTED``): the caller
+    materialises."""
+    P = _lib.ptr
+    fn, b, k, R, dtype = inp.fn, inp.b, inp.k, inp.R, inp.fn.dtype
+    if spec.kernel == "matern_gen" or k + 1 + R > 1024:
+        return None
+    out = torch.empty((b, k, R), device=fn.device, dtype=dtype)
+    info = torch.zeros(1, device=fn.device, dtype=torch.int32)
+    model = (inp.mode, inp.eps, P(inp.nz), spec.kernel_id(), spec.metric_id(), P(inp.ls), inp.ls.numel())
+    if R == 1 and k <= 62:
+        # mgp_fast_coefficients_* (fused gather .. LDL^T .. back-substitution on the wave kernel)
+        rc = _lib.fn("fast_coefficients", dtype)(
+            P(fn), inp.d, P(inp.ni), b, k, P(inp.tg), *model, P(out), P(info), _lib.stream_ptr(),
+        )
+        if rc != _lib.EUNSUPPORTED:
+            _lib.check(rc, "mgp_fast_coefficients")
+            _lib.raise_if_not_spd(info, "fast_coefficients")
+            return out
+    ws = _coefficients_workspace(dtype, k, R, b, fn.device)
+    rc = _lib.fn("fast_coefficients_any", dtype)(
+        P(fn), inp.d, P(inp.ni), b, k, P(inp.tg), R, *model, P(out), P(info), P(ws), 0 if ws is None else ws.numel(),
+        _lib.stream_ptr(),
+    )
+    if rc == _lib.EUNSUPPORTED:
+        return None
+    _lib.check(rc, "mgp_fast_coefficients_any")
+    _lib.raise_if_not_spd(info, "fast_coefficients")
+    return out
 
 
 def fast_coefficients(spec: KernelSpec, train_features: torch.Tensor, train_targets: torch.Tensor,
@@ -958,9 +1002,11 @@ def fast_coefficients(spec: KernelSpec, train_features: torch.Tensor, train_targ
     """Coefficient table ``C_i = (K_i + eps)^-1 y_i`` over the self-including neighbourhoods
     ``[i, nn[i][:-1]]`` (_fast_nn_update + _muygps_fast_posterior_mean_precompute,
     _src/gp/tensors/numpy.py:97-108, _src/gp/muygps/numpy.py:88-95), computed once per model: one
-    fused launch (``mgp_fast_coefficients_*``: one response, k <= 62) or, with ``fused=False`` / for
-    other shapes, row chunks through the per-function kernels.  Returns ``(n, k)`` or ``(n, k, R)`` together
-    with the updated index table ``(n, k)``."""
+    fused launch for any ``nn_count`` and response count with ``nn_count + 1 + R <= 1024`` (``mgp_fast_coefficients_*``
+    for one response and k <= 62, ``mgp_fast_coefficients_any_*`` otherwise) or, with ``fused=False`` / for what no
+    fused kernel serves (the general-smoothness Matern, through ``mgp_matern_gen_*``; more than 1024 rows), row chunks
+    through the per-function kernels.  Returns ``(n, k)`` or ``(n, k, R)`` together with the updated index table
+    ``(n, k)``."""
     from muygpys_amd._src.gp.kernels import hip as K
     from muygpys_amd._src.gp.muygps import hip as M
     from muygpys_amd._src.gp.noise import hip as N
@@ -972,33 +1018,25 @@ def fast_coefficients(spec: KernelSpec, train_features: torch.Tensor, train_targ
     d = 1 if train_features.ndim == 1 else train_features.shape[1]
     squeeze = train_targets.ndim == 1
     R = 1 if squeeze else train_targets.shape[1]
-    if R == 1 and fused:
-        # one launch: mgp_fast_coefficients_* (fused gather .. LDL^T .. back-substitution)
+    if fused:
         inp = _normalize(spec, train_features, train_features, None, nn_fast, train_targets.to(train_features.dtype))
-        fn, tg, ls, mode, eps, nz = inp.fn, inp.tg, inp.ls, inp.mode, inp.eps, inp.nz
-        out = torch.empty((n, k), device=fn.device, dtype=fn.dtype)
-        info = torch.zeros(1, device=fn.device, dtype=torch.int32)
-        rc = _lib.fn("fast_coefficients", fn.dtype)(
-            _lib.ptr(fn), d, _lib.ptr(nn_fast), n, k, _lib.ptr(tg), mode, eps, _lib.ptr(nz),
-            spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(out), _lib.ptr(info),
-            _lib.stream_ptr(),
-        )
-        if rc != -2:  # anything but MGP_EUNSUPPORTED (shape outside the fused kernel)
-            _lib.check(rc, "mgp_fast_coefficients")
-            _lib.raise_if_not_spd(info, "fast_coefficients")
-            return (out if squeeze else out[:, :, None]), nn_fast
+        out = _fused_coefficients(spec, inp)
+        if out is not None:
+            return (out.reshape(n, k) if squeeze else out), nn_fast
     out = torch.empty((n, k, R), device=train_features.device, dtype=train_features.dtype)
     aniso = not isinstance(spec.length_scale, (int, float)) and len(spec.length_scale) > 1
+    gen = spec.kernel == "matern_gen"  # (mgp_kernel_apply_* knows the closed forms only)
     for s in range(0, n, chunk):
         idx = nn_fast[s:s + chunk].contiguous()
         if aniso:
             ls = _length_scale_tensor(spec.length_scale, d, train_features)
             dist = T._reduce(T._pairwise_tensor(train_features, idx), spec.metric_id(), ls)
-            Kin = K._apply(dist, spec.kernel, 1.0)
+            Kin = K._matern_gen_fn(dist, spec.smoothness) if gen else K._apply(dist, spec.kernel, 1.0)
         else:
             ell = float(spec.length_scale if isinstance(spec.length_scale, (int, float)) else spec.length_scale[0])
             scale = 1.0 / ell if spec.metric == "l2" else 1.0 / ell**2
-            Kin = K._apply(T._pairwise_distances(train_features, idx, spec.metric), spec.kernel, scale)
+            dist = T._pairwise_distances(train_features, idx, spec.metric)
+            Kin = K._matern_gen_fn(dist * scale, spec.smoothness) if gen else K._apply(dist, spec.kernel, scale)
         if isinstance(spec.noise, torch.Tensor) and spec.noise.ndim >= 1:
             Kin = N._heteroscedastic_perturb(Kin, spec.noise[idx] if spec.noise.ndim == 1 else spec.noise[s:s + chunk])
         else:

@@ -199,6 +199,42 @@ def analytic_scale(Kin: lazy.LazyCov, nn_targets):
     return val.reshape(1) if config.state.lazy_tensors else val
 
 
+def fast_mean(Kcross: lazy.LazyCov, coeffs: torch.Tensor, rows: Optional[torch.Tensor] = None):
+    """The fast posterior mean ``sum_j Kcross[t, j] coeffs[row(t), j]`` of a lazy crosswise covariance handle through the
+    fused prediction kernel (``mgp_fast_posterior_mean_*``: gather, distances, kernel, dot product in one launch; nothing
+    of size (b, k) is formed), for any nn_count.
+
+    ``rows`` None: ``coeffs`` (b, k[, R]) is already gathered, one row per test point (what the reference's workflow
+    hands over, examples/from_indices.py:113-118).  ``rows`` (b,): ``coeffs`` is the whole table (n_train, k[, R]) and the
+    kernel picks row ``rows[t]`` for test point t itself -- no gathered copy.  Returns (b,) or (b, R), squeezed like the
+    reference; None when the handle is not a plain crosswise covariance the kernel evaluates (the general-smoothness
+    Matern included) or the shapes / dtypes do not fit: the caller then materialises the handle."""
+    from .fused import FusedUnsupported, KernelSpec, fast_posterior_mean
+
+    if not isinstance(Kcross, lazy.LazyCov):
+        return None
+    c = Kcross.diffs
+    if not (c.kind == "crosswise" and c.reduced and c.metric in ("l2", "F2") and Kcross.kernel != "matern_gen"):
+        return None
+    if not (isinstance(coeffs, torch.Tensor) and coeffs.is_cuda and coeffs.ndim in (2, 3)):
+        return None
+    b, k = c.nn_indices.shape
+    if coeffs.shape[1] != k or coeffs.dtype != c.dtype:
+        return None
+    if rows is None:
+        if coeffs.shape[0] != b:
+            return None
+        rows = torch.arange(b, device=coeffs.device)
+    elif tuple(rows.shape) != (b,):
+        return None
+    spec = KernelSpec(Kcross.kernel, c.metric, 1.0 if c.length_scale is None else c.length_scale, 0.0)
+    try:
+        out = fast_posterior_mean(spec, c.data, c.nn_data, c.data_indices, c.nn_indices, coeffs, rows)
+    except FusedUnsupported:
+        return None
+    return torch.squeeze(out)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The shear models: one mgp_shear_posterior_* launch per (noise, Kcross, responses), shared by the mean and the
 # variance of one evaluation through the Kin cache, as above.
