@@ -94,6 +94,51 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def elem_size(dtype) -> int:
+    """Bytes per element of a table dtype: the ``elem_size`` argument of the library's limit and size queries."""
+    return dtype.itemsize
+
+
+def run_ladder(rungs):
+    """Call ``rungs`` (zero-argument callables that return a status) in order while the answer is ``MGP_EUNSUPPORTED``;
+    ``(status, index)`` of the rung that ended the ladder -- the last one when all refused -- for the caller's error."""
+    at = -1
+    for rung in rungs:
+        at += 1
+        rc = rung()
+        if rc != EUNSUPPORTED:
+            return rc, at
+    return EUNSUPPORTED, at
+
+
+def workspace(size_entry_name: str, dtype, *shape, device):
+    """The uint8 workspace of one call, sized by the library's ``size_entry_name(elem_size, *shape)`` (a
+    ``mgp_*_workspace_bytes`` query), from torch's stream-ordered allocator; None where the query answers 0.  The caller
+    keeps it referenced until its foreign call has returned."""
+    size = int(getattr(load(), size_entry_name)(elem_size(dtype), *shape))
+    return torch.empty(size, dtype=torch.uint8, device=device) if size > 0 else None
+
+
+def large_workspace(dtype, k: int, R: int, b: int, device) -> "torch.Tensor":
+    """One slab per workgroup of a ``mgp_*_large_*`` forward / solve call; ``ValueError`` for a system beyond the kernel."""
+    ws = workspace("mgp_large_workspace_bytes", dtype, k, R, b, device=device)
+    if ws is None:
+        kmax = load().mgp_large_max_nn_count(elem_size(dtype), R)
+        raise ValueError(f"nn_count = {k} with {R} response column(s) exceeds mgp_large_max_nn_count = {kmax} "
+                         "(a local system holds at most 1024 rows: nn_count + 1 + response_count)")
+    return ws
+
+
+def backward_large_workspace(dtype, k: int, b: int, device) -> "torch.Tensor":
+    """One backward slab per workgroup of a ``mgp_*_backward_large_*`` call; ``ValueError`` beyond the kernel."""
+    ws = workspace("mgp_backward_large_workspace_bytes", dtype, k, b, device=device)
+    if ws is None:
+        kmax = load().mgp_large_max_nn_count(elem_size(dtype), 1)
+        raise ValueError(f"nn_count = {k} exceeds the limit of the analytic hyper-parameter gradient, mgp_large_max_nn_count = "
+                         f"{kmax} (a local system holds at most 1024 rows: nn_count + 2 in the backward)")
+    return ws
+
+
 def raw_stream() -> int:
     """The current HIP stream of the current device as an integer (torch.cuda.current_stream().cuda_stream without the
     Stream object: 0.2 instead of 1.5 us -- it sits in front of every launch of an optimiser's loop)."""
@@ -110,8 +155,7 @@ def stream_ptr():
 def served_by(d: int, k: int, R: int, dtype, packed: bool = False, path: str = "auto") -> str:
     """Name of the kernel instantiation the dispatcher picks for a shape (``mgp_posterior_kernel_name``)."""
     buf = C.create_string_buffer(256)
-    es = 4 if dtype == torch.float32 else 8
-    rc = load().mgp_posterior_kernel_name(es, d, k, R, int(bool(packed)), {"auto": 0, "generic": 1, "rhs": 2}[path], buf, 256)
+    rc = load().mgp_posterior_kernel_name(elem_size(dtype), d, k, R, int(bool(packed)), {"auto": 0, "generic": 1, "rhs": 2}[path], buf, 256)
     if rc == EUNSUPPORTED and packed:
         return served_by(d, k, R, dtype, False, path)
     check(rc, "mgp_posterior_kernel_name")
@@ -120,7 +164,7 @@ def served_by(d: int, k: int, R: int, dtype, packed: bool = False, path: str = "
 
 def shear_max_nn_count(dtype, in_count: int) -> int:
     """Largest nn_count the fused shear posterior accepts (``mgp_shear_max_nn_count``)."""
-    return load().mgp_shear_max_nn_count(4 if dtype == torch.float32 else 8, int(in_count))
+    return load().mgp_shear_max_nn_count(elem_size(dtype), int(in_count))
 
 
 def last_kernel() -> str:

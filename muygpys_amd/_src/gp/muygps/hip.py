@@ -31,20 +31,16 @@ def _solve(Kin, Kcross, Y, kout=1.0, want=("mean",)):
     yk = torch.empty((b, R), device=dev, dtype=dt) if "ykinvy" in want else None
     co = torch.empty((b, k, R), device=dev, dtype=dt) if "coeffs" in want else None
     info = torch.zeros(1, device=dev, dtype=torch.int32)
-    rc = _lib.fn("solve", dt)(
-        _lib.ptr(K), _lib.ptr(Kc), _lib.ptr(Yc), b, k, R, float(kout), _lib.ptr(mean), _lib.ptr(var),
-        _lib.ptr(yk), _lib.ptr(co), _lib.ptr(info), _lib.stream_ptr(),
-    )
-    if rc == _lib.EUNSUPPORTED:
+    args = (_lib.ptr(K), _lib.ptr(Kc), _lib.ptr(Yc), b, k, R, float(kout), _lib.ptr(mean), _lib.ptr(var),
+            _lib.ptr(yk), _lib.ptr(co), _lib.ptr(info))
+
+    def slab():
         # a system beyond LDS: the blocked factorisation on a slab of global memory (mgp_solve_large_*), with the
         # back-substitution of the coefficient output
-        from muygpys_amd.fused import _large_workspace
+        ws = _lib.large_workspace(dt, k, R, b, dev)
+        return _lib.fn("solve_large", dt)(*args, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
 
-        ws = _large_workspace(dt, k, R, b, dev)
-        rc = _lib.fn("solve_large", dt)(
-            _lib.ptr(K), _lib.ptr(Kc), _lib.ptr(Yc), b, k, R, float(kout), _lib.ptr(mean), _lib.ptr(var),
-            _lib.ptr(yk), _lib.ptr(co), _lib.ptr(info), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(),
-        )
+    rc, _ = _lib.run_ladder((lambda: _lib.fn("solve", dt)(*args, _lib.stream_ptr()), slab))
     _lib.check(rc, "mgp_solve")
     _lib.raise_if_not_spd(info, "mgp_solve")
     return mean, var, yk, co

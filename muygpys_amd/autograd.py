@@ -18,7 +18,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .fused import KernelSpec, _backward_large_workspace, _large_workspace, _noise_args, _normalize
+from .fused import KernelSpec, _Inputs, _noise_args, _normalize, _posterior_plain
 
 # whether ``posterior`` serves an nn_count beyond ``mgp_max_nn_count_backward`` on the slab factor when its caller does
 # not say: off unless MUYGPYS_HIP_AUTOGRAD_LARGE=1 (a backward at nn_count = 1022 takes a 512 MiB workspace and runs
@@ -60,16 +60,14 @@ class _FusedPosterior(torch.autograd.Function):
         mean = torch.empty((b, R), device=fn.device, dtype=fn.dtype)
         var = torch.empty((b,), device=fn.device, dtype=fn.dtype)
         info = torch.zeros(1, device=fn.device, dtype=torch.int32)
-        args = (_lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(batch_indices), _lib.ptr(nn_indices), b, k, _lib.ptr(tg), R)
-        model = (mode, eps, _lib.ptr(nz), kernel_id, metric_id, _lib.ptr(ls), ls.numel())
-        outs = (_lib.ptr(mean), _lib.ptr(var), None, _lib.ptr(info))
-        what = "mgp_posterior"
-        rc = _lib.fn("posterior", fn.dtype)(*args, *model, *outs, _lib.stream_ptr())
-        if rc == _lib.EUNSUPPORTED:  # a system beyond LDS: the blocked factorisation on a slab (the (n, R) table: 0)
-            what = "mgp_posterior_large"
-            ws = _large_workspace(fn.dtype, k, R, b, fn.device)
-            rc = _lib.fn("posterior_large", fn.dtype)(*args, 0, *model, *outs, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, what)
+        # the two rungs of posterior_mean_var on the plain tables: the LDS families, then the blocked factorisation on a
+        # slab (the (n, R) table: targets_batch = 0); no ykinvy
+        inp = _Inputs(fq, fn, batch_indices, nn_indices, tg, b, k, d, R, False, ls, mode, eps, nz)
+        model = (kernel_id, metric_id, _lib.ptr(ls), ls.numel())
+        outs = (_lib.ptr(mean), _lib.ptr(var), None, _lib.ptr(info), _lib.stream_ptr())
+        rc, at = _lib.run_ladder((lambda: _posterior_plain("posterior", inp, model, outs),
+                                  lambda: _posterior_plain("posterior_large", inp, model, outs, False, slab=True)))
+        _lib.check(rc, ("mgp_posterior", "mgp_posterior_large")[at])
         _lib.raise_if_not_spd(info, "posterior (autograd forward)")
         ctx.save_for_backward(fq, fn, tg, ls, noise, batch_indices, nn_indices)
         ctx.conf = (mode, eps, kernel_id, metric_id, shared_table, large_backward)
@@ -103,7 +101,7 @@ class _FusedPosterior(torch.autograd.Function):
             _lib.ptr(info),
         )
         if large:  # (decided in `posterior`: nn_count beyond the two LDS triangles)
-            ws = _backward_large_workspace(dt, k, b, dev)
+            ws = _lib.backward_large_workspace(dt, k, b, dev)
             rc = _lib.fn("posterior_backward_large", dt)(*args, _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
             _lib.check(rc, "mgp_posterior_backward_large")
         else:
@@ -157,7 +155,7 @@ def posterior(
     inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, want_noise=False,
                      detach=False)
     fq, fn, ni, tg, b, k, ls = inp.fq, inp.fn, inp.ni, inp.tg, inp.b, inp.k, inp.ls
-    kmax = _lib.load().mgp_max_nn_count_backward(4 if fn.dtype == torch.float32 else 8)
+    kmax = _lib.load().mgp_max_nn_count_backward(fn.element_size())
     large = k > kmax
     if large:
         if not (_BEYOND_LDS if beyond_lds is None else beyond_lds) or spec.kernel == "matern_gen":

@@ -130,7 +130,7 @@ class PackedTable:
 
     @staticmethod
     def supported(d: int, R: int, k: int, dtype) -> bool:
-        es = 4 if dtype == torch.float32 else 8
+        es = dtype.itemsize
         dk = (d * es + 15) // 16 * 16 // es  # (rows are padded to whole 16-byte groups)
         if dk > 64:
             return False
@@ -303,87 +303,57 @@ def _use_packed(packed, inp: _Inputs, features, targets, rows: int, gathered: bo
     return True
 
 
+def _model_args(spec: KernelSpec, ls: torch.Tensor) -> tuple:
+    """kernel id (the general-smoothness entries: the smoothness instead), metric id, length scale(s) and their count."""
+    model = float(spec.smoothness) if spec.kernel == "matern_gen" else spec.kernel_id()
+    return (model, spec.metric_id(), _lib.ptr(ls), ls.numel())
+
+
+def _plain_args(inp: _Inputs, model: tuple, outs: tuple, targets_batch=None) -> tuple:
+    """What every posterior entry on the plain tables starts with, in the ABI's order: tables, shape, responses
+    (``targets_batch`` behind them where the entry takes it), noise triple, ``model`` (:func:`_model_args`), outputs."""
+    P = _lib.ptr
+    head = (P(inp.fq), P(inp.fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R)
+    if targets_batch is not None:
+        head += (int(targets_batch),)
+    return head + (inp.mode, inp.eps, P(inp.nz)) + model + outs[:4]
+
+
+def _posterior_plain(base: str, inp: _Inputs, model: tuple, outs: tuple, targets_batch=None, slab: bool = False) -> int:
+    """One launch of ``mgp_<base>_*`` on the plain tables (``outs`` as for :func:`_posterior_call`); returns the status.
+    ``slab``: a ``*_large_*`` entry (csrc/mgp_large.hip), its workspace allocated here; ``ValueError`` beyond 1024 rows."""
+    args = _plain_args(inp, model, outs, targets_batch)
+    if not slab:
+        return _lib.fn(base, inp.fn.dtype)(*args, outs[4])
+    ws = _lib.large_workspace(inp.fn.dtype, inp.k, inp.R, inp.b, inp.fn.device)
+    return _lib.fn(base, inp.fn.dtype)(*args, _lib.ptr(ws), ws.numel(), outs[4])
+
+
+_PLAIN_ENTRY = {"auto": "posterior", "generic": "posterior_generic", "rhs": "posterior_rhs"}
+
+
 def _posterior_call(spec: KernelSpec, inp: _Inputs, gathered: bool, path: str, pq, pn, outs: tuple):
     """(entry point, arguments) of one posterior launch: ``mgp_posterior_gen_*`` for the general-smoothness Matern,
     else by table form -- prepared (``pn`` / ``pq``: the packed neighbour / query tables) or plain, responses in the
     table or gathered.  ``outs``: the pointers of mean, var, ykinvy, info and the stream, in the ABI's order."""
     P = _lib.ptr
-    ls = inp.ls if pn is None else pn.kernel_length_scale(inp.ls)
-    plain = (None, None) if pn is not None else (P(inp.fq), P(inp.fn))
-    tables = (None, 0, None, 0) if pn is None else (P(pq.data), pq.stride, P(pn.data), pn.stride)
-    shape = (inp.d if pn is None else pn.d_kernel, P(inp.bi), P(inp.ni), inp.b, inp.k)
-    noise = (inp.mode, inp.eps, P(inp.nz))
-    tail = (spec.metric_id(), P(ls), ls.numel()) + outs
-    if spec.kernel == "matern_gen":
-        # (`tg` goes along even when the prepared table carries the responses: the library does not read it then)
-        args = plain + tables + shape + (P(inp.tg), inp.R, int(gathered)) + noise + (float(spec.smoothness),) + tail
-        return _lib.fn("posterior_gen", inp.fn.dtype), args
-    tail = (spec.kernel_id(),) + tail
-    if pn is None:
-        base = "posterior_gathered" if gathered else {"auto": "posterior", "generic": "posterior_generic", "rhs": "posterior_rhs"}[path]
-        args = plain + shape + (P(inp.tg), inp.R) + noise + tail
-    elif gathered:
-        base, args = "posterior_packed_gathered", tables + shape + (P(inp.tg), inp.R) + noise + tail
+    gen = spec.kernel == "matern_gen"
+    model = _model_args(spec, inp.ls if pn is None else pn.kernel_length_scale(inp.ls))
+    if pn is None and not gen:
+        base = "posterior_gathered" if gathered else _PLAIN_ENTRY[path]
+        return _lib.fn(base, inp.fn.dtype), _plain_args(inp, model, outs) + outs[4:]
+    tail = (inp.mode, inp.eps, P(inp.nz)) + model + outs
+    if pn is None:  # (the general smoothness: one entry for both table forms, the absent one NULL)
+        tables, shape = (P(inp.fq), P(inp.fn), None, 0, None, 0), (inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k)
     else:
-        base, args = "posterior_packed", tables + shape + (inp.R,) + noise + tail
-    return _lib.fn(base, inp.fn.dtype), args
-
-
-def _large_workspace(dtype, k: int, R: int, b: int, device) -> torch.Tensor:
-    """The workspace of one ``mgp_*_large_*`` call (``mgp_large_workspace_bytes``: one slab per workgroup of the grid, at
-    most 512 MiB), from torch's stream-ordered allocator.  ``ValueError`` for a system beyond the kernel."""
-    lib = _lib.load()
-    es = 4 if dtype == torch.float32 else 8
-    size = int(lib.mgp_large_workspace_bytes(es, k, R, b))
-    if size == 0:
-        raise ValueError(
-            f"nn_count = {k} with {R} response column(s) exceeds mgp_large_max_nn_count = {lib.mgp_large_max_nn_count(es, R)} "
-            "(a local system holds at most 1024 rows: nn_count + 1 + response_count)"
-        )
-    return torch.empty(size, dtype=torch.uint8, device=device)
-
-
-def _backward_large_workspace(dtype, k: int, b: int, device) -> torch.Tensor:
-    """The workspace of one ``mgp_hyper_backward_large_*`` / ``mgp_posterior_backward_large_*`` call (``mgp_backward_large_workspace_bytes``: one backward
-    slab per workgroup of the grid, at most 512 MiB).  ``ValueError`` for a system beyond the kernel."""
-    lib = _lib.load()
-    es = 4 if dtype == torch.float32 else 8
-    size = int(lib.mgp_backward_large_workspace_bytes(es, k, b))
-    if size == 0:
-        raise ValueError(
-            f"nn_count = {k} exceeds the limit of the analytic hyper-parameter gradient, mgp_large_max_nn_count = "
-            f"{lib.mgp_large_max_nn_count(es, 1)} (a local system holds at most 1024 rows: nn_count + 2 in the backward)"
-        )
-    return torch.empty(size, dtype=torch.uint8, device=device)
-
-
-def _posterior_large(spec: KernelSpec, inp: _Inputs, gathered: bool, outs: tuple) -> int:
-    """One ``mgp_posterior_large_*`` launch on the plain tables (systems beyond LDS, csrc/mgp_large.hip); ``outs`` as
-    for :func:`_posterior_call`.  Returns the status."""
-    P = _lib.ptr
-    ws = _large_workspace(inp.fn.dtype, inp.k, inp.R, inp.b, inp.fn.device)
-    return _lib.fn("posterior_large", inp.fn.dtype)(
-        P(inp.fq), P(inp.fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, int(gathered),
-        inp.mode, inp.eps, P(inp.nz), spec.kernel_id(), spec.metric_id(), P(inp.ls), inp.ls.numel(),
-        *outs[:4], P(ws), ws.numel(), outs[4],
-    )
-
-
-def _posterior_gen_family(spec: KernelSpec, inp: _Inputs, gathered: bool, outs: tuple, large: bool) -> int:
-    """One general-smoothness launch on a workgroup kernel family by name, plain tables: ``mgp_posterior_gen_large_*``
-    (the slab factor beyond LDS, with a workspace of :func:`_large_workspace`) or ``mgp_posterior_gen_generic_*`` (the
-    system in LDS).  ``outs`` as for :func:`_posterior_call`.  Returns the status; ``MGP_EUNSUPPORTED`` without a call
-    for a system of more than 1024 rows."""
-    P = _lib.ptr
-    head = (P(inp.fq), P(inp.fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, int(gathered),
-            inp.mode, inp.eps, P(inp.nz), float(spec.smoothness), spec.metric_id(), P(inp.ls), inp.ls.numel())
-    if not large:
-        return _lib.fn("posterior_gen_generic", inp.fn.dtype)(*head, *outs)
-    try:
-        ws = _large_workspace(inp.fn.dtype, inp.k, inp.R, inp.b, inp.fn.device)
-    except ValueError:
-        return _lib.EUNSUPPORTED
-    return _lib.fn("posterior_gen_large", inp.fn.dtype)(*head, *outs[:4], P(ws), ws.numel(), outs[4])
+        tables, shape = (P(pq.data), pq.stride, P(pn.data), pn.stride), (pn.d_kernel, P(inp.bi), P(inp.ni), inp.b, inp.k)
+    if gen:
+        # (`tg` goes along even when the prepared table carries the responses: the library does not read it then)
+        tables = tables if pn is None else (None, None) + tables
+        return _lib.fn("posterior_gen", inp.fn.dtype), tables + shape + (P(inp.tg), inp.R, int(gathered)) + tail
+    if gathered:
+        return _lib.fn("posterior_packed_gathered", inp.fn.dtype), tables + shape + (P(inp.tg), inp.R) + tail
+    return _lib.fn("posterior_packed", inp.fn.dtype), tables + shape + (inp.R,) + tail
 
 
 def posterior_mean_var(
@@ -409,15 +379,11 @@ def posterior_mean_var(
     (:44-67 with Kout = 1); ``ykinvy (b, R)`` holds ``y_r^T K^-1 y_r`` per neighbourhood
     (the summand of _analytic_scale_optim_unnormalized, scale/numpy.py:9-15).
 
-    ``path``: "auto" (dispatcher), or one kernel family by name -- "generic" / "rhs" / "large" (parity tests).
-    "auto" hands a closed-form kernel whose system no longer fits LDS (``nn_count`` beyond ``mgp_max_nn_count``) to the
-    blocked factorisation in global memory (``mgp_posterior_large_*``), up to ``nn_count + 1 + R = 1024`` rows;
-    beyond that: ``ValueError``.
-    The general-smoothness Matern (``kernel="matern_gen"``): up to 64 slots (``nn_count + 1 + R``) "auto" is the wave
-    kernels or :class:`FusedUnsupported`; beyond, on the plain tables, ``mgp_posterior_gen_*`` (the LDS workgroup
-    kernel) and, where the system does not fit LDS, ``mgp_posterior_gen_large_*`` -- :class:`FusedUnsupported` only for
-    more than 1024 rows or a smoothness above 30.  "generic" / "large" name those two entries at any ``nn_count``
-    (gathered responses included); "rhs" is a ``ValueError``.
+    ``path``: "auto" (dispatcher), or one kernel family by name -- "generic" / "rhs" / "large" (parity tests; the
+    general-smoothness Matern has no "rhs").  Which entry points a call tries, in which order: the lists of rungs in
+    the body, and the table in DESIGN.md §1.  A closed-form kernel is served up to ``nn_count + 1 + R = 1024`` rows
+    (``ValueError`` beyond); the general-smoothness Matern raises :class:`FusedUnsupported` where no fused kernel
+    serves it (33 to 64 slots in a batch too small to compile for, more than 1024 rows, a smoothness above 30).
     ``packed``: "auto" reads the tables through prepared copies (:class:`PackedTable`, cached per
     tensor) when the shape allows it and the batch touches the table often enough to pay for the
     one-time pack; True forces, False disables.
@@ -439,36 +405,50 @@ def posterior_mean_var(
         raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
     if gathered and path not in ("auto", "large") and not (gen and path == "generic"):
         raise ValueError("gathered responses go through the dispatcher (path='auto') or path='large'")
-    # the general smoothness beyond the 64 slots of the wave kernels: the workgroup families, plain tables only
-    gen_beyond = gen and inp.k + 1 + R > 64
     # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
     rows = fn.shape[0] + (0 if test_features is train_features else inp.fq.shape[0])
-    use_packed = (path == "auto" and not gen_beyond
+    # the general smoothness beyond the 64 slots of the wave kernels: the workgroup families, plain tables only
+    beyond_wave = gen and inp.k + 1 + R > 64
+    use_packed = (path == "auto" and not beyond_wave
                   and _use_packed(packed, inp, train_features, train_targets, rows, gathered))
     outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
-    rc = -2
-    if gen and path != "auto":  # one workgroup family by name (mgp_posterior_gen_generic_* / mgp_posterior_gen_large_*)
-        rc = _posterior_gen_family(spec, inp, gathered, outs, large=path == "large")
-    elif use_packed:
+
+    def plain():  # the dispatcher on the plain tables, or a closed-form LDS family by name
+        call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
+        return call(*args)
+
+    def prepared():
         pn = pack_table(train_features, None if gathered else train_targets, query=False)
         pq = pn if test_features is train_features else pack_table(test_features, None)
         call, args = _posterior_call(spec, inp, gathered, path, pq, pn, outs)
-        rc = call(*args)
-    # MGP_EUNSUPPORTED on the prepared tables (or not tried): the plain tables -- for the closed-form kernels only
-    # (matern_gen does NOT retry on the plain tables: the caller gets FusedUnsupported)
-    if gen and path != "auto":
-        pass
+        return call(*args)
+
+    def family(base="posterior_large", slab=True):  # a workgroup family by name, plain tables: on a slab beyond LDS, or in LDS
+        return _posterior_plain(base, inp, _model_args(spec, inp.ls), outs, gathered, slab)
+
+    # the ladders: a rung is tried when the one before it answered MGP_EUNSUPPORTED
+    if gen:
+        def gen_slab():  # (more than 1024 rows: refused without a call)
+            try:
+                return family("posterior_gen_large")
+            except ValueError:
+                return _lib.EUNSUPPORTED
+
+        if path == "generic":
+            rungs = (lambda: family("posterior_gen_generic", slab=False),)
+        elif path == "large":
+            rungs = (gen_slab,)
+        elif beyond_wave:
+            rungs = (plain, gen_slab)
+        else:
+            rungs = (prepared if use_packed else plain,)  # (a refusal on the prepared tables is final: the caller's to handle)
     elif path == "large":
-        rc = _posterior_large(spec, inp, gathered, outs)
-    elif rc == _lib.EUNSUPPORTED and not (gen and use_packed):
-        call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
-        rc = call(*args)
-        # a system that does not fit LDS: the blocked factorisation in global memory -- of a closed-form kernel, or of
-        # the general smoothness beyond 64 slots (up to 64 a refusal of the wave kernels is the caller's to handle)
-        if rc == _lib.EUNSUPPORTED and path == "auto" and not gen:
-            rc = _posterior_large(spec, inp, gathered, outs)
-        elif rc == _lib.EUNSUPPORTED and gen_beyond:
-            rc = _posterior_gen_family(spec, inp, gathered, outs, large=True)
+        rungs = (family,)
+    elif path != "auto":
+        rungs = (plain,)
+    else:
+        rungs = (prepared, plain, family) if use_packed else (plain, family)
+    rc, _ = _lib.run_ladder(rungs)
     if gen and rc == _lib.EUNSUPPORTED:
         raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={inp.k}, R={R}, d={inp.d}")
     _lib.check(rc, "mgp_posterior_gen" if gen else "mgp_posterior")
@@ -517,23 +497,29 @@ def loocv_partials(
     var = torch.empty((b,), device=fn.device, dtype=dtype)
     yk = torch.empty((b,), device=fn.device, dtype=dtype)
     partials = torch.empty(6, device=fn.device, dtype=torch.float64)
-    rest = dict(eps=inp.eps, mean=mean, var=var, yk=yk, info=info, huber_delta=huber_delta, partials=partials,
-                scratch=_lib.loocv_scratch(fn.device, b), stream=_lib.stream_ptr())
-    rc = -2
-    if _use_packed(packed, inp, train_features, train_targets, fn.shape[0]):
-        pn = pack_table(train_features, train_targets)
-        call, args = _loocv_call(pn, inp, spec, pn.kernel_length_scale(inp.ls), **rest)
-        rc = call(*args)
-    if rc == _lib.EUNSUPPORTED:
-        call, args = _loocv_call(None, inp, spec, inp.ls, **rest)
-        rc = call(*args)
-        if rc == _lib.EUNSUPPORTED and spec.kernel != "matern_gen":
-            # a system beyond LDS: the blocked factorisation in global memory, then the same reduction tree over its
-            # outputs on the canonical leaves (what mgp_loocv_* does behind every kernel family but the wave kernels)
-            outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
-            _lib.check(_posterior_large(spec, inp, False, outs), "mgp_posterior_large")
-            partials = loocv_tree_sums(mean, var, yk, inp.tg, inp.bi, huber_delta)
-            rc = 0
+    scratch, stream = _lib.loocv_scratch(fn.device, b), _lib.stream_ptr()
+
+    def plain(table=None):  # mgp_loocv_packed_* on a prepared table, mgp_loocv_* on the plain one
+        ls = inp.ls if table is None else table.kernel_length_scale(inp.ls)
+        call, args = _loocv_call(table, inp, spec, ls, eps=inp.eps, mean=mean, var=var, yk=yk, info=info,
+                                 huber_delta=huber_delta, partials=partials, scratch=scratch, stream=stream)
+        return call(*args)
+
+    def prepared():
+        return plain(pack_table(train_features, train_targets))
+
+    def slab():  # a system beyond LDS: the blocked factorisation in global memory (closed-form kernels)
+        outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
+        return _posterior_plain("posterior_large", inp, _model_args(spec, inp.ls), outs, False, slab=True)
+
+    rungs = (prepared,) if _use_packed(packed, inp, train_features, train_targets, fn.shape[0]) else ()
+    rungs += (plain,) if spec.kernel == "matern_gen" else (plain, slab)
+    rc, at = _lib.run_ladder(rungs)
+    if rungs[at] is slab:
+        # ... then the same reduction tree over its outputs on the canonical leaves (what mgp_loocv_* does behind every
+        # kernel family but the wave kernels)
+        _lib.check(rc, "mgp_posterior_large")
+        partials = loocv_tree_sums(mean, var, yk, inp.tg, inp.bi, huber_delta)
     if rc != 0:
         _lib.loocv_scratch_reset()
     _lib.check(rc, "mgp_loocv")
@@ -710,19 +696,21 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     model = (_lib.NOISE_SCALAR, float(spec.noise), None, spec.kernel_id(), spec.metric_id(), P(ls), ls.numel())
     shape = (inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg))
     out = (P(g_l), P(g_n), P(info))
-    if gyk is not None:
-        what = "mgp_loocv_backward"
-        rc = _lib.fn("loocv_backward", fn.dtype)(P(fn), *shape, *model, P(gm), P(gv), P(gyk), *out, _lib.stream_ptr())
-    else:
-        what = "mgp_posterior_backward"
-        rc = _lib.fn("posterior_backward", fn.dtype)(P(fn), P(fn), *shape, inp.R, *model, P(gm), P(gv), None, None, None,
-                                                     *out, _lib.stream_ptr())
-    if rc == _lib.EUNSUPPORTED and spec.kernel != "matern_gen":
-        what = "mgp_hyper_backward_large"
-        ws = _backward_large_workspace(fn.dtype, inp.k, inp.b, fn.device)
-        rc = _lib.fn("hyper_backward_large", fn.dtype)(P(fn), *shape, inp.R, *model, P(gm), P(gv), P(gyk), *out,
-                                                       P(ws), ws.numel(), _lib.stream_ptr())
-    _lib.check(rc, what)
+    what = ("mgp_posterior_backward" if gyk is None else "mgp_loocv_backward", "mgp_hyper_backward_large")
+
+    def lds():
+        if gyk is not None:
+            return _lib.fn("loocv_backward", fn.dtype)(P(fn), *shape, *model, P(gm), P(gv), P(gyk), *out, _lib.stream_ptr())
+        return _lib.fn("posterior_backward", fn.dtype)(P(fn), P(fn), *shape, inp.R, *model, P(gm), P(gv), None, None, None,
+                                                       *out, _lib.stream_ptr())
+
+    def slab():
+        ws = _lib.backward_large_workspace(fn.dtype, inp.k, inp.b, fn.device)
+        return _lib.fn("hyper_backward_large", fn.dtype)(P(fn), *shape, inp.R, *model, P(gm), P(gv), P(gyk), *out,
+                                                         P(ws), ws.numel(), _lib.stream_ptr())
+
+    rc, at = _lib.run_ladder((lds,) if spec.kernel == "matern_gen" else (lds, slab))
+    _lib.check(rc, what[at])
     return g_l, g_n
 
 
@@ -955,13 +943,6 @@ def fast_posterior_mean(
     return mean.reshape(b) if squeeze else mean
 
 
-def _coefficients_workspace(dtype, k: int, R: int, b: int, device) -> Optional[torch.Tensor]:
-    """The workspace of one ``mgp_fast_coefficients_any_*`` call (``mgp_fast_coefficients_workspace_bytes``), from torch's
-    stream-ordered allocator; None where the system fits LDS and the call needs none."""
-    size = int(_lib.load().mgp_fast_coefficients_workspace_bytes(4 if dtype == torch.float32 else 8, k, R, b))
-    return torch.empty(size, dtype=torch.uint8, device=device) if size > 0 else None
-
-
 def _fused_coefficients(spec: KernelSpec, inp: _Inputs) -> Optional[torch.Tensor]:
     """``(K_b + eps)^-1 Y_b`` (b, k, R) of the neighbourhoods ``inp.ni`` of one table in ONE launch: the wave kernel
     (``mgp_fast_coefficients_*``: one response, k <= 62) where it serves the shape, else ``mgp_fast_coefficients_any_*``
@@ -976,23 +957,24 @@ def _fused_coefficients(spec: KernelSpec, inp: _Inputs) -> Optional[torch.Tensor
     out = torch.empty((b, k, R), device=fn.device, dtype=dtype)
     info = torch.zeros(1, device=fn.device, dtype=torch.int32)
     model = (inp.mode, inp.eps, P(inp.nz), spec.kernel_id(), spec.metric_id(), P(inp.ls), inp.ls.numel())
-    if R == 1 and k <= 62:
-        # mgp_fast_coefficients_* (fused gather .. LDL^T .. back-substitution on the wave kernel)
-        rc = _lib.fn("fast_coefficients", dtype)(
+
+    def wave():  # mgp_fast_coefficients_* (fused gather .. LDL^T .. back-substitution on the wave kernel)
+        return _lib.fn("fast_coefficients", dtype)(
             P(fn), inp.d, P(inp.ni), b, k, P(inp.tg), *model, P(out), P(info), _lib.stream_ptr(),
         )
-        if rc != _lib.EUNSUPPORTED:
-            _lib.check(rc, "mgp_fast_coefficients")
-            _lib.raise_if_not_spd(info, "fast_coefficients")
-            return out
-    ws = _coefficients_workspace(dtype, k, R, b, fn.device)
-    rc = _lib.fn("fast_coefficients_any", dtype)(
-        P(fn), inp.d, P(inp.ni), b, k, P(inp.tg), R, *model, P(out), P(info), P(ws), 0 if ws is None else ws.numel(),
-        _lib.stream_ptr(),
-    )
+
+    def workgroup():  # (a workspace only beyond LDS: None where the system fits)
+        ws = _lib.workspace("mgp_fast_coefficients_workspace_bytes", dtype, k, R, b, device=fn.device)
+        return _lib.fn("fast_coefficients_any", dtype)(
+            P(fn), inp.d, P(inp.ni), b, k, P(inp.tg), R, *model, P(out), P(info), P(ws), 0 if ws is None else ws.numel(),
+            _lib.stream_ptr(),
+        )
+
+    rungs = (wave, workgroup) if R == 1 and k <= 62 else (workgroup,)
+    rc, at = _lib.run_ladder(rungs)
     if rc == _lib.EUNSUPPORTED:
         return None
-    _lib.check(rc, "mgp_fast_coefficients_any")
+    _lib.check(rc, "mgp_fast_coefficients" if rungs[at] is wave else "mgp_fast_coefficients_any")
     _lib.raise_if_not_spd(info, "fast_coefficients")
     return out
 

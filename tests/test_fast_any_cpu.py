@@ -14,9 +14,10 @@ import numpy as np
 import pytest
 import torch
 
-from muygpys_amd import _abi, _lib, fused
+from muygpys_amd import _lib, fused
 from muygpys_amd.fused import KernelSpec
 from oracle import muygps_oracle as orc
+from tests.call_recorder import STREAM, install, vals
 
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 ES = {"f32": 4, "f64": 8}
@@ -117,38 +118,13 @@ def test_the_wave_entry_keeps_its_limits_and_the_prediction_entry_its_refusal():
 
 # ---- what fused.fast_coefficients hands the library -------------------------------------------------------------------
 
-STREAM = 0x5151
 D, N = 3, 40
-
-
-class Recorder:
-    def __init__(self):
-        self.calls, self.statuses = [], {}
-
-    def fn(self, base, dtype):
-        def call(*args):
-            self.calls.append((base, dtype, args))
-            queue = self.statuses.get(base)
-            return queue.pop(0) if queue else 0
-
-        call.argtypes = _abi.signatures()[f"mgp_{base}_{_lib.suffix(dtype)}"][1]
-        return call
 
 
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    _lib.load()
-    monkeypatch.setattr(_lib, "fn", r.fn)
-    monkeypatch.setattr(_lib, "require_cuda", lambda *tensors: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: C.c_void_p(STREAM))
+    yield install(monkeypatch)
     fused.clear_caches()
-    yield r
-    fused.clear_caches()
-
-
-def vals(call):
-    return [a.value if isinstance(a, C._SimpleCData) else a for a in call[2]]
 
 
 def inputs(k, R, dtype=torch.float32, n=N):

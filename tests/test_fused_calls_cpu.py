@@ -8,65 +8,22 @@ check, the stream and the LOOCV scratch are stood in for.  ``mgp_packed_row_byte
 Shapes: fp32, k = 5, d = 3, R = 2, b = 7 -- a prepared table pads the 12-byte feature rows to d_kernel = 4, so the
 prepared-table calls carry d = 4, a 64-byte stride and (Anisotropy) four length scales."""
 
-import ctypes as C
-
 import pytest
 import torch
 
-from muygpys_amd import _abi, _lib, fused
+from muygpys_amd import _lib, fused
 from muygpys_amd.fused import FusedUnsupported, KernelSpec
+from tests.call_recorder import STREAM, install, vals
 
 K, D, R, B, N, NQ = 5, 3, 2, 7, 40, 9
-STREAM = 0x5151
 STRIDE = 64  # mgp_packed_row_bytes(4, R <= 4, 4): 16 bytes of features + the 16-byte response slot, to 64
 F32 = torch.float32
 
 
-class Recorder:
-    """Stands in for ``_lib.fn``: notes (base, dtype, args) of every call and answers with the status queued for
-    that entry point (0 when none is)."""
-
-    def __init__(self, statuses=None):
-        self.calls = []
-        self.statuses = {k: list(v) for k, v in (statuses or {}).items()}
-
-    def fn(self, base, dtype):
-        def call(*args):
-            self.calls.append((base, dtype, args))
-            queue = self.statuses.get(base)
-            return queue.pop(0) if queue else 0
-
-        call.argtypes = _abi.signatures()[f"mgp_{base}_{_lib.suffix(dtype)}"][1]
-        return call
-
-    def of(self, *skip):
-        """The calls made, without the table packs (or whatever else is named)."""
-        return [c for c in self.calls if c[0] not in ("table_pack",) + skip]
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    _lib.load()
-    monkeypatch.setattr(_lib, "fn", r.fn)
-    monkeypatch.setattr(_lib, "require_cuda", lambda *tensors: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: C.c_void_p(STREAM))
-    monkeypatch.setattr(_lib, "raw_stream", lambda: STREAM)
-    monkeypatch.setattr(_lib, "loocv_scratch", lambda device, b=0: torch.zeros(64, dtype=torch.uint8))
-    monkeypatch.setattr(_lib, "loocv_tree_selfcheck", lambda *a, **k: True)
-    monkeypatch.setattr(torch.Tensor, "pin_memory", lambda self: self)  # (LoocvPlan: pinned host words; no device here)
+    yield install(monkeypatch)
     fused.clear_caches()
-    yield r
-    fused.clear_caches()
-
-
-def val(a):
-    """A recorded argument as a plain value: pointers as integers (NULL: None), numbers as numbers."""
-    return a.value if isinstance(a, C._SimpleCData) else a
-
-
-def vals(call):
-    return [val(a) for a in call[2]]
 
 
 def tables(n=N, nq=NQ, b=B, one_response=False, seed=0):

@@ -15,7 +15,7 @@ import torch
 
 from muygpys_amd import _lib, fused
 from muygpys_amd.fused import FusedUnsupported, KernelSpec
-from tests.test_fused_calls_cpu import STREAM, Recorder, vals
+from tests.call_recorder import STREAM, install, vals
 
 OK, EINVAL, EUNSUPPORTED = 0, -1, -2
 ES = {"f32": 4, "f64": 8}
@@ -151,14 +151,7 @@ F32 = torch.float32
 
 @pytest.fixture
 def rec(monkeypatch):
-    r = Recorder()
-    _lib.load()
-    monkeypatch.setattr(_lib, "fn", r.fn)
-    monkeypatch.setattr(_lib, "require_cuda", lambda *tensors: None)
-    monkeypatch.setattr(_lib, "stream_ptr", lambda: C.c_void_p(STREAM))
-    monkeypatch.setattr(_lib, "raw_stream", lambda: STREAM)
-    fused.clear_caches()
-    yield r
+    yield install(monkeypatch)
     fused.clear_caches()
 
 

@@ -396,8 +396,7 @@ def test_functor_layer_precompute_is_the_fused_launch_and_stays_small(monkeypatc
     """Lazy pairwise_tensor -> m.kernel -> m.fast_coefficients at k = 100, n = 20 000, fp32: one fused launch whose
     peak allocation stays below 4 n k R s + the workspace -- the materialising route needs n k k s = 800 MB for Kin
     alone."""
-    from muygpys_amd import lazy
-    from muygpys_amd.fused import _coefficients_workspace
+    from muygpys_amd import _lib, lazy
 
     rng = np.random.default_rng(3)
     n, d, k, R, s = 20_000, 8, 100, 1, 4
@@ -407,7 +406,7 @@ def test_functor_layer_precompute_is_the_fused_launch_and_stays_small(monkeypatc
     offsets = np.concatenate([[0], rng.choice(np.arange(1, n), size=k - 1, replace=False)])
     ni = to_dev((np.arange(n)[:, None] + offsets[None, :]) % n)
     m = model(LS, NUGGET)
-    ws = _coefficients_workspace(torch.float32, k, R, n, "cuda")
+    ws = _lib.workspace("mgp_fast_coefficients_workspace_bytes", torch.float32, k, R, n, device="cuda")
     ws_bytes = 0 if ws is None else ws.numel()
     del ws
     calls = spy_on_library(monkeypatch)

@@ -64,8 +64,6 @@ def beyond64(out_path, rounds=3):
     mgp_matern_gen_* on both, mgp_perturb_*, mgp_solve_* / mgp_solve_large_* -- in one process, alternating after a
     warm-up of each, device events around each; and the closed-form nu = 3/2 launch of the same kernel family as the
     floor.  Every buffer of the materialising route is allocated outside the timed region (its best case)."""
-    from muygpys_amd.fused import _large_workspace
-
     P, lib = _lib.ptr, _lib.load()
     gen = torch.Generator(device="cuda").manual_seed(5)
     N, eps = 400_000, 1e-3
@@ -85,7 +83,7 @@ def beyond64(out_path, rounds=3):
             cd, Kc = (torch.empty((b, k), device="cuda", dtype=td) for _ in range(2))
             mean, var = torch.empty((b, 1), device="cuda", dtype=td), torch.empty(b, device="cuda", dtype=td)
             info = torch.zeros(1, device="cuda", dtype=torch.int32)
-            ws = _large_workspace(td, k, 1, b, X.device) if family == "large" else None
+            ws = _lib.large_workspace(td, k, 1, b, X.device) if family == "large" else None
             st = _lib.stream_ptr()
 
             def materialised(nu):
