@@ -552,6 +552,35 @@ int mgp_knn_scan_wide(const float* train, const float* train_sqn, int64_t n, int
 int mgp_knn_finish_wide(const float* queries, const float* train, int d, const int32_t* candidates, int64_t m, int k,
                         const int64_t* row_map, int64_t* out_idx, float* out_dist, void* stream);
 
+/* The two scans above for LONG rows (csrc/mgp_knn_long.hip): d % 4 == 0, 68 <= d <= mgp_knn_long_max_features().  The
+ * reference's NN_Wrapper takes any feature count (src/MuyGPyS/neighbors.py:89-107); its torch tutorial searches a
+ * 100-dimensional embedding.
+ *   mgp_knn_long_max_features   the widest row the two entries below take: 256.
+ *   mgp_knn_scan_long           (fp32 like every k-NN entry; named like mgp_knn_scan_wide, without a type suffix: there
+ *       is no fp64 twin) the parameters and the whole contract of mgp_knn_scan_f32 (k <= 64, IN / OUT Gram-form
+ *       lists, unordered, start % 64 == 0, the 16-entry queues and the `overflow` flag: a flagged query's list is
+ *       incomplete and the caller recomputes it).
+ *   mgp_knn_scan_long_wide      the parameters and the whole contract of mgp_knn_scan_wide (k <= 1024, whole IN lists:
+ *       start >= k, + 1 with self_idx; one queue slot per tile column, drained after every tile, `overflow` accepted,
+ *       not NULL, never written).
+ * Same arithmetic (v_mfma_f32_32x32x2_f32, the accumulator starts at -|x|^2/2, one compare acc > (|q|^2 - tau)/2 per
+ * pair); a 64-row tile is staged in ceil(d / 64) chunks of 8 ceil(d / (8 ceil(d / 64))) features and the accumulators
+ * carry across them.  d <= 64 is MGP_EUNSUPPORTED here: the entries above own those widths (and keep refusing d > 64).
+ * The winners go through mgp_knn_finish_f32 / mgp_knn_finish_wide, which take any d % 4 == 0.
+ * Order of the checks, all before any HIP call, as in the entry each one mirrors: sizes (MGP_EINVAL), nothing to do
+ * (m == 0 or start >= n: MGP_OK, pointers not looked at), NULL pointers (MGP_EINVAL; self_idx and the stream are
+ * optional), then MGP_EUNSUPPORTED for k > 64 (1024), d outside {68, 72, .. 256}, alignment, n >= 2^31, start % 64 != 0
+ * and (the wide entry) k + 1 > start with self_idx, k > start without. */
+int mgp_knn_long_max_features(void);
+int mgp_knn_scan_long(const float* train, const float* train_sqn, int64_t n, int d,
+                          const float* queries, const float* query_sqn, const int64_t* self_idx, int64_t m,
+                          int k, int64_t start, float* best_d, int32_t* best_i, int32_t* overflow,
+                          void* stream);
+int mgp_knn_scan_long_wide(const float* train, const float* train_sqn, int64_t n, int d,
+                           const float* queries, const float* query_sqn, const int64_t* self_idx, int64_t m,
+                           int k, int64_t start, float* best_d, int32_t* best_i, int32_t* overflow,
+                           void* stream);
+
 /* Same search with a split-bf16 pre-filter on the matrix cores (3 bf16 MFMA chains
  * hi.hi + hi.lo + lo.hi, error < 2^-14 |q||x|, folded into the threshold) and an
  * exact fp32 difference-form re-measurement of every survivor: exact results,

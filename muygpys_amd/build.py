@@ -31,6 +31,8 @@ PER_FILE_FLAGS = {
     "mgp_knn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     # (the wide-list scan too; its registers, LDS and scratch go into the report: DESIGN sec. 4.6)
     "mgp_knn_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
+    # (... and the long-row scans: tests/test_knn_long_resources.py reads their records)
+    "mgp_knn_long.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
     # the 64-step elimination must unroll completely (the fp64 / 16-response body exceeds the default
     # pragma-unroll budget, and a rolled loop indexes the 128-register row at run time = in scratch)
     "mgp_fused_rhs.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],

@@ -133,6 +133,11 @@ constexpr int KNN_WIDE_MAX_K = 1024;
 int launch_knn_scan_wide(const KnnArgs&, hipStream_t);
 int launch_knn_finish_wide(const float* queries, const float* train, int d, const int* cand, int64_t m, int k,
                            const int64_t* perm, int64_t* out_idx, float* out_dist, hipStream_t);
+// the two scans for rows of 68 to KNN_LONG_MAX_D features (mgp_knn_long.hip): the tile staged chunk by chunk, the
+// accumulators carried across the chunks; the finish steps above serve these rows as they are
+constexpr int KNN_LONG_MAX_D = 256;
+int launch_knn_scan_long(const KnnArgs&, hipStream_t);
+int launch_knn_scan_long_wide(const KnnArgs&, hipStream_t);
 
 template <typename T> int launch_fused_generic(const FusedArgs&, hipStream_t);
 template <typename T> int launch_solve_generic(const SolveArgs&, hipStream_t);

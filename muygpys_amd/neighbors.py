@@ -6,20 +6,29 @@ interface -- ``get_nns(test)`` / ``get_batch_nns(batch_indices)`` returning ``(i
 squared-l2 distances)`` with the self-match dropped for batch queries (neighbors.py:207-211,
 246-250) -- and computes it exactly.
 
-* fp32, ``d % 4 == 0``, ``d <= 64``, ``k <= 64`` (the shapes of the hot path): the fused MFMA
+* fp32, ``d <= 64``, ``k <= 64`` (the shapes of the hot path): the fused MFMA
   scan ``mgp_knn_scan_f32`` (``csrc/mgp_knn.hip``) -- distances on the matrix cores, one compare
   per pair against the query's running k-th best, rare survivors merged into per-query k-best
   lists -- after the lists have been initialised from the first rows of the table on the dense
-  path.  Nothing of size (queries x train) is ever materialised.
+  path.  Nothing of size (queries x train) is ever materialised.  The kernels take rows of a multiple of four
+  features: the table is stored zero-padded to ``_width`` = max(4, 4 ceil(d / 4)) after centring and the queries are
+  padded alike (distances do not change; ``feature_count`` stays the caller's d) -- d = 1, 2, 3 (spatial tables), 5, 10,
+  30 ... run on the scans too; ``MUYGPYS_HIP_KNN_PAD=0`` keeps them on the dense path.
 * the same tables, ``64 < k <= 1024``: the wide-list scan ``mgp_knn_scan_wide`` and its finish step
   ``mgp_knn_finish_wide`` (``csrc/mgp_knn_wide.hip``) -- the same arithmetic, the lists in global memory and held by
   the draining wave as ceil(k / 64) entries per lane, a queue slot per column of the tile, so no queue can overflow;
   the lists start from ``SCAN_INIT_ROWS`` head rows.  3 to 24 times the dense path at 1 M x 1 M
   (``profiles/knn_wide_bench.json``); ``MUYGPYS_HIP_KNN_WIDE=0`` keeps these searches on the dense path.
-* anything else: the dense path, in row chunks, ``|q|^2 + |x|^2 - 2 q.x`` through
-  ``torch.matmul`` (rocBLAS) followed by ``topk``.
+* fp32, ``64 < d <= 256`` (the reference torch tutorial's 100-dimensional embedding), ``k <= 1024``: the long-row scans
+  ``mgp_knn_scan_long`` (k <= 64) / ``mgp_knn_scan_long_wide`` (``csrc/mgp_knn_long.hip``) -- the same arithmetic,
+  a 64-row tile staged in ceil(d / 64) feature chunks with the accumulators carried across them -- from
+  ``SCAN_INIT_ROWS`` head rows, then the same finish entries.  4 to 10 times the dense path at 1 M x 1 M
+  (``profiles/knn_long_bench.json``); ``MUYGPYS_HIP_KNN_LONG=0`` keeps these searches on the dense path.
+* anything else (fp64 tables, tables of up to 8 192 rows, ``use_scan=False``, d > 256): the dense path, in row chunks,
+  ``|q|^2 + |x|^2 - 2 q.x`` through ``torch.matmul`` (rocBLAS) followed by ``topk``.
 
-``last_route`` ("scan" | "wide" | "dense" | "ivf") names what served the most recent search.
+``scan_route(d, k, dtype, train_count, use_scan)`` is the rule, a pure function; ``last_route`` ("scan" | "wide" |
+"long" | "dense" | "ivf") names what served the most recent search.
 
 Either way the k winners are then re-measured in difference form and sorted, so the returned
 distances carry no cancellation error and ties resolve by distance then index order of the sort.
@@ -47,8 +56,39 @@ from . import _lib
 
 SCAN_INIT_ROWS = 4096  # rows of the table the k-best lists are initialised from (dense path)
 WIDE_MAX_K = 1024      # mgp_knn_wide_max_nn_count(): the longest list of the wide scan (64 < k: csrc/mgp_knn_wide.hip)
+LONG_MAX_D = 256       # mgp_knn_long_max_features(): the widest row of the long-row scans (64 < d: csrc/mgp_knn_long.hip)
 CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
 CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
+
+
+def stored_width(d: int) -> int:
+    """The row width the scan kernels see: the next multiple of four, four at least (rows are zero-padded to it)."""
+    return max(4, -(-int(d) // 4) * 4)
+
+
+def _switch(name: str) -> bool:
+    return os.environ.get(name, "1") != "0"  # (read on every call: A/B on a live object)
+
+
+def scan_route(d: int, k: int, dtype, train_count: int, use_scan: bool = True):
+    """Which kernels serve an exact search of ``k`` neighbours in a ``dtype`` table of ``train_count`` rows of ``d``
+    features: "scan" (k <= 64) or "wide" (k <= 1024) at a stored width of up to 64, "long" at 68 to 256, None for the
+    dense path.  A pure function of its arguments and the three A/B switches of the environment
+    (MUYGPYS_HIP_KNN_WIDE / _LONG / _PAD = 0: k > 64 / stored widths > 64 / padded widths stay dense)."""
+    if not use_scan or dtype != torch.float32 or d < 1 or k < 1:
+        return None
+    if not 2 * SCAN_INIT_ROWS < train_count < 2**31:
+        return None
+    width = stored_width(d)
+    if width != d and not _switch("MUYGPYS_HIP_KNN_PAD"):
+        return None
+    if k > (WIDE_MAX_K if _switch("MUYGPYS_HIP_KNN_WIDE") else 64):
+        return None
+    if width <= 64:
+        return "wide" if k > 64 else "scan"
+    if width <= LONG_MAX_D and _switch("MUYGPYS_HIP_KNN_LONG"):
+        return "long"
+    return None
 
 
 def default_cells(train_count: int, nlist=None, nprobe=None) -> Tuple[int, int]:
@@ -97,15 +137,21 @@ class NN_Wrapper:
         # evenly and the first rows are a fair sample for the initial k-best lists.  ``_perm`` maps
         # stored position -> caller's row, ``_inv`` the other way; both are None for the identity.
         self._perm = self._inv = None
-        if (shuffle and use_scan and table.dtype == torch.float32 and self.feature_count % 4 == 0 and 4 <= self.feature_count <= 64
-                and self.train_count > 2 * SCAN_INIT_ROWS):
+        # ... and with their rows zero-padded to the width the kernels take (a multiple of four, four at least; the
+        # queries are padded alike, after centring: distances do not change).  ``feature_count`` stays the caller's.
+        # (k = 1 and every switch on: could a scan ever serve this table?)
+        served = (use_scan and table.dtype == torch.float32 and 2 * SCAN_INIT_ROWS < self.train_count < 2**31
+                  and stored_width(self.feature_count) <= LONG_MAX_D)
+        self._width = stored_width(self.feature_count) if served else self.feature_count
+        table = self._pad_features(table - self._mean)
+        if shuffle and served:
             gen = torch.Generator(device=table.device).manual_seed(0x5CA9)
             self._perm = torch.randperm(self.train_count, device=table.device, generator=gen)
             self._inv = torch.empty_like(self._perm)
             self._inv[self._perm] = torch.arange(self.train_count, device=table.device)
-            self.train = (table[self._perm] - self._mean).contiguous()
+            self.train = table[self._perm].contiguous()
         else:
-            self.train = (table - self._mean).contiguous()
+            self.train = table
         self.nn_count = int(nn_count)
         self.nn_method = "exact"
         self.chunk = int(chunk)
@@ -117,7 +163,7 @@ class NN_Wrapper:
         self.scan_kind = "bf16x3" if scan_kind == "auto" else scan_kind
         self._packed_train, self._packed_qmax, self._packed_layout = None, None, None
         self.last_overflow = None  # per-query overflow flags of the most recent scan (device int32)
-        self.last_route = None     # what served the most recent search: "scan" | "wide" | "dense" | "ivf"
+        self.last_route = None     # what served the most recent search: "scan" | "wide" | "long" | "dense" | "ivf"
         self._sq = (self.train.double() ** 2).sum(1).to(self.train.dtype)
         # the scan kernel reads |x|^2 in whole 64-row tiles: +inf past the end (never a neighbour)
         pad = (-self.train_count) % 64
@@ -141,6 +187,7 @@ class NN_Wrapper:
         if self.nn_method == "ivf":
             self.last_route = "ivf"
             return self._cells_nns(samples, nn_count, exclude)
+        samples = self._pad_features(samples)
         out = self._scan_nns(samples, nn_count, exclude)  # (sets last_route where it serves the call)
         if out is None:
             self.last_route = "dense"
@@ -148,17 +195,14 @@ class NN_Wrapper:
         idx, dist = out
         return (idx if self._perm is None else self._perm[idx]), dist
 
-    def _scan_supported(self, samples, nn_count) -> bool:
-        d = self.feature_count
-        return (
-            self.use_scan and self.train.dtype == torch.float32 and samples.dtype == torch.float32
-            and d % 4 == 0 and 4 <= d <= 64 and 1 <= nn_count <= (WIDE_MAX_K if self._wide_enabled() else 64)
-            and self.train_count > 2 * SCAN_INIT_ROWS and self.train_count < 2**31
-        )
+    def _route(self, samples, nn_count):
+        """scan_route for this table and these (centred, padded) query rows."""
+        if samples.dtype != self.train.dtype or samples.shape[1] != self._width or self._width % 4:
+            return None
+        return scan_route(self.feature_count, int(nn_count), self.train.dtype, self.train_count, self.use_scan)
 
-    @staticmethod
-    def _wide_enabled() -> bool:
-        return os.environ.get("MUYGPYS_HIP_KNN_WIDE", "1") != "0"  # (0: nn_count > 64 stays on the dense path, for A/B)
+    def _scan_supported(self, samples, nn_count) -> bool:
+        return self._route(samples, nn_count) is not None
 
     @staticmethod
     def _split_bf16(v: torch.Tensor):
@@ -197,7 +241,8 @@ class NN_Wrapper:
     def _scan_nns(self, samples, nn_count, exclude=None, force_wide=False):
         """Fused MFMA scan (see the module docstring); None when the shape is not covered.  ``force_wide``: the wide
         pair for k <= 64 too (tools/knnwidebench.py's sanity line; no search is routed that way)."""
-        if not self._scan_supported(samples, nn_count):
+        route = self._route(samples, nn_count)
+        if route is None:
             return None
         q = samples.contiguous()
         m, k = q.shape[0], int(nn_count)
@@ -210,9 +255,12 @@ class NN_Wrapper:
         # over these rows was a fifth of the search's time at 1 M x 1 M, k = 30 (round 5)
         # Lists of more than 64 entries (mgp_knn_scan_wide): its queues cannot overflow whatever the head rows are, and
         # the more rows the lists start from the fewer candidates the scan merges: SCAN_INIT_ROWS for every k
+        # Long rows (mgp_knn_scan_long): SCAN_INIT_ROWS too -- its 16-entry queues then see 64 k / 4096 <= 1 expected
+        # survivor per tile
         wide = k > 64 or force_wide
-        tile_rows = 128 if (self.scan_kind == "bf16x3" and self.feature_count + 2 <= 16) else 64
-        init_rows = SCAN_INIT_ROWS if wide else min(SCAN_INIT_ROWS, max(1024, -(-(tile_rows * k // 2) // 1024) * 1024))
+        long_rows = route == "long"
+        tile_rows = 128 if (self.scan_kind == "bf16x3" and self._width + 2 <= 16) else 64
+        init_rows = SCAN_INIT_ROWS if wide or long_rows else min(SCAN_INIT_ROWS, max(1024, -(-(tile_rows * k // 2) // 1024) * 1024))
         head = self.train[:init_rows]
         best_d = torch.empty((m, k), device=q.device, dtype=torch.float32)
         best_i = torch.empty((m, k), device=q.device, dtype=torch.int32)
@@ -240,8 +288,8 @@ class NN_Wrapper:
         overflow = torch.zeros((m,), device=q.device, dtype=torch.int32)
         ex64 = None if exclude is None else exclude.to(torch.int64).contiguous()
         if wide:
-            return self._wide_nns(q, qn, ex64, exclude, init_rows, best_d, best_i, overflow)
-        if self.scan_kind == "bf16x3":
+            return self._wide_nns(q, qn, ex64, exclude, init_rows, best_d, best_i, overflow, long_rows)
+        if self.scan_kind == "bf16x3" and not long_rows:  # (the long rows have no split-bf16 pre-filter)
             # the split-bf16 kernel keeps exact (difference-form) distances in the lists
             for s in range(0, m, 65536):
                 diff = q[s:s + 65536, None, :] - self.train[best_i[s:s + 65536].to(torch.int64)]
@@ -253,7 +301,7 @@ class NN_Wrapper:
             # exceeds the bound it was packed for, with head-room so that it rarely does
             qmax = float(qn.max().sqrt())
             # d <= 8: the two-chain kernel on 24-slot rows (round 5), else three chains on [hi(KP) | lo(KP)]
-            d8 = self.feature_count <= 8 and os.environ.get("MUYGPYS_HIP_KNN_D8", "1") != "0"  # (0: A/B against the three-chain kernel)
+            d8 = self._width <= 8 and os.environ.get("MUYGPYS_HIP_KNN_D8", "1") != "0"  # (0: A/B against the three-chain kernel)
             pack = self._pack_bf16_d8 if d8 else self._pack_bf16
             scan = _lib.load().mgp_knn_scan_bf16x2_d8 if d8 else _lib.load().mgp_knn_scan_bf16x3
             # (the cache remembers WHICH layout it holds: the A/B switch may be flipped on a live object)
@@ -266,12 +314,13 @@ class NN_Wrapper:
             packed_q = pack(q, 1.0, 0.0)
             rc = scan(
                 _lib.ptr(self.train), _lib.ptr(self._packed_train), _lib.ptr(self._sq_scan), self.train_count,
-                self.feature_count, _lib.ptr(q), _lib.ptr(packed_q), _lib.ptr(qn), _lib.ptr(ex64), m, k,
+                self._width, _lib.ptr(q), _lib.ptr(packed_q), _lib.ptr(qn), _lib.ptr(ex64), m, k,
                 init_rows, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
             )
         else:
-            rc = _lib.load().mgp_knn_scan_f32(
-                _lib.ptr(self.train), _lib.ptr(self._sq_scan), self.train_count, self.feature_count,
+            scan = _lib.load().mgp_knn_scan_long if long_rows else _lib.load().mgp_knn_scan_f32
+            rc = scan(
+                _lib.ptr(self.train), _lib.ptr(self._sq_scan), self.train_count, self._width,
                 _lib.ptr(q), _lib.ptr(qn), _lib.ptr(ex64), m, k, init_rows,
                 _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
             )
@@ -282,7 +331,7 @@ class NN_Wrapper:
         # (csrc/mgp_knn_select.hip) -- was gather (m, k, d) / subtract / square / sum / argsort / gather / gather
         idx = torch.empty((m, k), dtype=torch.int64, device=q.device)
         dist = torch.empty((m, k), dtype=q.dtype, device=q.device)
-        rc_fin = _lib.load().mgp_knn_finish_f32(_lib.ptr(q), _lib.ptr(self.train), self.feature_count, _lib.ptr(best_i), m, k,
+        rc_fin = _lib.load().mgp_knn_finish_f32(_lib.ptr(q), _lib.ptr(self.train), self._width, _lib.ptr(best_i), m, k,
                                                 None, _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr())
         if rc_fin == _lib.EUNSUPPORTED:
             cand = best_i.to(torch.int64)
@@ -300,16 +349,18 @@ class NN_Wrapper:
         if redo.numel():  # queues overflowed (adversarial row order): those queries go dense
             ri, rd = self._dense_nns(q[redo], k, None if exclude is None else exclude[redo])
             idx[redo], dist[redo] = ri, rd
-        self.last_route = "scan"
+        self.last_route = route
         return idx, dist
 
     FINISH_BUDGET_BYTES = 1 << 30  # the (rows, k, d) temporary of the torch finish step, where the kernel declines
 
-    def _wide_nns(self, q, qn, ex64, exclude, init_rows, best_d, best_i, overflow):
-        """The scan and the finish step for 64 < k <= WIDE_MAX_K (csrc/mgp_knn_wide.hip) on lists that hold the exact
-        k-best of the first ``init_rows`` rows (Gram form); None where the scan declines (alignment)."""
-        (m, k), d = best_d.shape, self.feature_count
-        rc = _lib.load().mgp_knn_scan_wide(
+    def _wide_nns(self, q, qn, ex64, exclude, init_rows, best_d, best_i, overflow, long_rows=False):
+        """The scan and the finish step for 64 < k <= WIDE_MAX_K (csrc/mgp_knn_wide.hip; ``long_rows``: stored widths
+        beyond 64, csrc/mgp_knn_long.hip) on lists that hold the exact k-best of the first ``init_rows`` rows (Gram
+        form); None where the scan declines (alignment)."""
+        (m, k), d = best_d.shape, self._width
+        scan = _lib.load().mgp_knn_scan_long_wide if long_rows else _lib.load().mgp_knn_scan_wide
+        rc = scan(
             _lib.ptr(self.train), _lib.ptr(self._sq_scan), self.train_count, d, _lib.ptr(q), _lib.ptr(qn),
             _lib.ptr(ex64), m, k, init_rows, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
         )
@@ -338,7 +389,7 @@ class NN_Wrapper:
         if redo.numel():  # (the contract of the narrow scans; the wide scan's queues cannot overflow)
             ri, rd = self._dense_nns(q[redo], k, None if exclude is None else exclude[redo])
             idx[redo], dist[redo] = ri, rd
-        self.last_route = "wide"
+        self.last_route = "long" if long_rows else "wide"
         return idx, dist
 
     DENSE_BUDGET_BYTES = 4 << 30  # (chunk x train_count) distance matrix + topk temporaries
