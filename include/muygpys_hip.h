@@ -841,6 +841,40 @@ int mgp_hyper_backward_large_f64(const double* features, int d, const int64_t* b
                                  const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
                                  double* grad_ls, double* grad_noise, int* info,
                                  void* workspace, int64_t workspace_bytes, void* stream);
+/* The same for the general-smoothness Matern (K3, _src/gp/kernels/numpy.py:34-43; `smoothness` = nu in place of a
+ * kernel id, as mgp_posterior_gen_large_*), with the partial with respect to nu as a third output: what lets
+ * L-BFGS-B optimise a free smoothness on one extra launch per iteration instead of p + 1 forward evaluations.  Serves
+ * every k >= 1 with k + 2 <= 1024 (mgp_backward_gen_large_max_nn_count(elem_size) = 1022 in both widths: the two node
+ * tables fit LDS next to everything else over the whole range) and 0 < nu <= 30.  Semantics as
+ * mgp_hyper_backward_large_*: the LOOCV and the posterior form, the three noise modes, any d >= 1, both metrics, scalar
+ * or per-feature length scale, one table on both sides, the workspace of mgp_backward_large_workspace_bytes.
+ *   grad_ls (b, ls_count), grad_noise (b, k), grad_nu (b): per-neighbourhood partials, written (not accumulated); any
+ *       may be NULL, not all three.  With grad_nu NULL the kernel evaluates one exponential per quadrature node and
+ *       pair, with it three.  dk/dr = -sqrt(2 nu) c x^nu K_{nu-1}(x) and dk/dnu come from the trapezoidal rule of the
+ *       forward kernels with other node weights (csrc/mgp_wave_common.h); a pair at zero distance contributes
+ *       nothing to grad_ls or grad_nu.  A non-SPD neighbourhood counts in *info and leaves its rows of all three
+ *       untouched; a neighbourhood's partials are the same bits whatever its place in the batch, the batch, the grid,
+ *       the workspace size and the workspace's previous contents (no floating-point atomic).
+ *   Order of the checks, all before any HIP call: sizes b < 0, k < 1, d < 1, R < 1 and a smoothness that is not > 0
+ *   (NaN included) (MGP_EINVAL); the empty batch (MGP_OK, nothing else looked at); required pointers, grad_ykinvy with
+ *   R != 1, all three cotangents NULL, all three outputs NULL, ids, a noise mode without noise_dev, ls_count not in
+ *   {1, d}, the workspace NULL, misaligned or shorter than one slab (MGP_EINVAL); then smoothness > 30 or
+ *   k + 2 > 1024: MGP_EUNSUPPORTED.  mgp_hyper_backward_large_* goes on refusing MGP_KERNEL_MATERN_GEN. */
+int mgp_backward_gen_large_max_nn_count(int elem_size);
+int mgp_hyper_backward_gen_large_f32(const float* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                     int64_t b, int k, const float* targets, int R,
+                                     int noise_mode, double noise_scalar, const float* noise_dev,
+                                     double smoothness, int metric_id, const float* length_scale, int ls_count,
+                                     const float* grad_mean, const float* grad_var, const float* grad_ykinvy,
+                                     float* grad_ls, float* grad_noise, float* grad_nu, int* info,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_hyper_backward_gen_large_f64(const double* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                     int64_t b, int k, const double* targets, int R,
+                                     int noise_mode, double noise_scalar, const double* noise_dev,
+                                     double smoothness, int metric_id, const double* length_scale, int ls_count,
+                                     const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
+                                     double* grad_ls, double* grad_noise, double* grad_nu, int* info,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
 /* The whole vector-Jacobian product of mgp_posterior_backward_* for any such k: what the reference obtains from torch
  * autograd when a deep-kernel model trains through MuyGPs_layer (torch/muygps_layer.py:129-164) with an nn_count beyond
  * mgp_max_nn_count_backward, on the same blocked factor and the same backward slab.  Arguments and semantics as

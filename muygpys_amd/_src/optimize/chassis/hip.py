@@ -76,9 +76,12 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     ``lool_fn``, ``mse_fn``, ``pseudo_huber_fn``, ``looph_fn`` (with their ``boundary_scale``) on one response, or
     ``cross_entropy_fn`` / ``mse_fn`` on the one-hot columns of a classifier (``fused.class_value_and_grad``: the
     posterior, one ``mgp_class_sums_*`` launch, one backward launch); the free parameters
-    length scales (``length_scale`` / ``length_scale{i}``) of a closed-form kernel and / or the homoscedastic ``noise``
-    -- anything else raises (there is no silent fall-back to finite differences: the caller asked for an analytic
-    gradient).  What the reference's torch autograd route differentiates (torch/muygps_layer.py:129-164), here for the
+    length scales (``length_scale`` / ``length_scale{i}``), the homoscedastic ``noise`` and / or the ``smoothness`` of
+    a Matern kernel -- anything else raises (there is no silent fall-back to finite differences: the caller asked for
+    an analytic gradient).  A free smoothness is evaluated by the general-nu kernels at every trial value, 1/2, 3/2 and
+    5/2 included (the closed forms have no gradient with respect to it), its gradient comes from
+    ``mgp_hyper_backward_gen_large_*`` at every nn_count up to 1022, and bounds that leave (0, 30] raise before the
+    first launch; a FIXED smoothness off the closed forms is served by the same kernels.  What the reference's torch autograd route differentiates (torch/muygps_layer.py:129-164), here for the
     numpy-style chassis (_src/optimize/chassis/numpy.py:57-81).
 
     A free ``noise`` follows the reference's objective to the letter: mean and variance take the TRIAL value, the
@@ -117,7 +120,7 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
                          "config.state.lazy_tensors / integration.install())")
     if cross.data is not pair.nn_data and cross.data.data_ptr() != pair.nn_data.data_ptr():
         raise ValueError("analytic_gradient=True: LOOCV differentiates one table (query rows = training rows)")
-    index, noise_at = {}, None
+    index, noise_at, nu_at = {}, None, None
     for j, name in enumerate(x0_names):
         if name == "length_scale":
             index[j] = 0
@@ -125,8 +128,17 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
             index[j] = int(name[len("length_scale"):])
         elif name == "noise":
             noise_at = j
+        elif name == "smoothness" and type(muygps.kernel).__name__ == "Matern":
+            nu_at = j
+            # (the in-kernel evaluators serve 0 < nu <= 30: said here, before the first launch)
+            names, _, bounds = muygps.get_opt_params()
+            lo, hi = (float(v) for v in np.asarray(bounds, dtype=np.float64).reshape(-1, 2)[list(names).index(name)])
+            if not (lo > 0.0 and hi <= 30.0):
+                raise ValueError(f"analytic_gradient=True: the smoothness bounds ({lo}, {hi}) leave (0, 30], the range "
+                                 "of the general-smoothness Matern's gradient kernel")
         else:
-            raise ValueError(f"analytic_gradient=True: {name!r} is neither a length scale nor the homoscedastic noise")
+            raise ValueError(f"analytic_gradient=True: {name!r} is neither a length scale, the homoscedastic noise nor "
+                             "the smoothness of a Matern kernel")
     stored = muygps.noise()
     if getattr(stored, "ndim", 0) >= 1 and getattr(stored, "numel", lambda: 1)() > 1:
         raise ValueError("analytic_gradient=True: homoscedastic noise")
@@ -145,16 +157,22 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
             raise ValueError("analytic_gradient=True: the kernel did not stay a lazy handle")
         spec = lazy_eval._spec(Kin)
         spec.noise = stored if noise_at is None else float(x_array[noise_at])
+        free_nu = {}
+        if nu_at is not None:
+            # a free smoothness is evaluated by the general form even where a trial value lands exactly on 1/2, 3/2 or
+            # 5/2: the closed forms have no gradient with respect to it
+            spec.kernel, spec.smoothness = "matern_gen", float(x_array[nu_at])
+            free_nu = {"grad_smoothness": True}
         if classify:  # (no sigma^2 in these losses: the trial noise is the only noise)
-            value, g_ls, g_noise = class_value_and_grad(spec, pair.nn_data, labels, cross.data_indices, pair.nn_indices,
-                                                        loss=loss, reduce_fn=reduce_fn)
-            grad = [g_noise if j == noise_at else g_ls[index[j]] for j in range(len(x0_names))]
-            return value, np.array(grad, dtype=np.float64)
-        value, g_ls, g_noise = loocv_value_and_grad(spec, pair.nn_data, nn_t.targets, cross.data_indices, pair.nn_indices,
-                                                    loss=loss, reduce_fn=reduce_fn, scale=scale_mode,
-                                                    boundary_scale=boundary_scale,
-                                                    sigma_noise=stored if noise_at is not None else None)
-        grad = [g_noise if j == noise_at else g_ls[index[j]] for j in range(len(x0_names))]
+            value, g_ls, g_noise, *g_nu = class_value_and_grad(spec, pair.nn_data, labels, cross.data_indices,
+                                                               pair.nn_indices, loss=loss, reduce_fn=reduce_fn, **free_nu)
+        else:
+            value, g_ls, g_noise, *g_nu = loocv_value_and_grad(spec, pair.nn_data, nn_t.targets, cross.data_indices,
+                                                               pair.nn_indices, loss=loss, reduce_fn=reduce_fn,
+                                                               scale=scale_mode, boundary_scale=boundary_scale,
+                                                               sigma_noise=stored if noise_at is not None else None,
+                                                               **free_nu)
+        grad = [g_noise if j == noise_at else g_nu[0] if j == nu_at else g_ls[index[j]] for j in range(len(x0_names))]
         return value, np.array(grad, dtype=np.float64)
 
     return value_and_grad

@@ -294,6 +294,29 @@ int hyper_backward_large(const T* feat, int d, const int64_t* bi, const int64_t*
   return launch_hyper_backward_large<T>(g, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024 and the general nu)
 }
 
+// ... of the general-smoothness Matern (mgp_backward_gen_large.hip): the same checks in the same order, the smoothness
+// sign with the sizes (in front of the empty-batch return), its limit with the shapes beyond the kernel; grad_nu is a
+// third output
+template <typename T>
+int hyper_backward_gen_large(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
+                             int R, int noise_mode, double eps, const T* nd, double smoothness, int metric_id, const T* ls,
+                             int ls_count, const T* gmean, const T* gvar, const T* gyk, T* gls, T* gnz, T* gnu, int* info,
+                             void* ws, int64_t ws_bytes, void* stream) {
+  if (!(smoothness > 0.0)) return MGP_EINVAL;
+  BackwardArgs g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES | KERNEL_IS_GEN, feat, feat, d, bi, ni, b, k, tg, R, noise_mode, eps,
+                                  nd, MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (gyk && R != 1) return MGP_EINVAL;  // (the LOOCV losses are defined for one response)
+  if ((!gmean && !gvar && !gyk) || (!gls && !gnz && !gnu)) return MGP_EINVAL;
+  if (!ws || reinterpret_cast<uintptr_t>(ws) % 16 != 0 || ws_bytes < backward_large_slab_bytes(sizeof(T), k))
+    return MGP_EINVAL;
+  if (smoothness > 30.0) return MGP_EUNSUPPORTED;
+  g.f.smoothness = smoothness;
+  g.grad_mean = gmean, g.grad_var = gvar, g.grad_yk = gyk, g.grad_ls = gls, g.grad_noise = gnz;
+  return launch_hyper_backward_gen_large<T>(g, gnu, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024)
+}
+
 // ... and the whole vector-Jacobian product there: two tables, every cotangent of mgp_posterior_backward_*
 template <typename T>
 int posterior_backward_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
@@ -752,7 +775,22 @@ int64_t mgp_backward_large_workspace_bytes(int elem_size, int k, int64_t b) {
   }
 MGP_DEFINE_BWD_LARGE(f32, float)
 MGP_DEFINE_BWD_LARGE(f64, double)
-#define MGP_DEFINE_BWD_LARGE_FULL(SUF, T)                                                                           \
+int mgp_backward_gen_large_max_nn_count(int elem_size) {
+  if (elem_size != 4 && elem_size != 8) return MGP_EINVAL;
+  return backward_gen_large_max_nn_count(elem_size);
+}
+#define MGP_DEFINE_BWD_GEN_LARGE(SUF, T)                                                                            \
+  int mgp_hyper_backward_gen_large_##SUF(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b,      \
+                                         int k, const T* tg, int R, int nm, double eps, const T* nd,                 \
+                                         double smoothness, int mid, const T* ls, int lsc, const T* gmean,           \
+                                         const T* gvar, const T* gyk, T* gls, T* gnz, T* gnu, int* info,             \
+                                         void* workspace, int64_t workspace_bytes, void* st) {                       \
+    return hyper_backward_gen_large<T>(feat, d, bi, ni, b, k, tg, R, nm, eps, nd, smoothness, mid, ls, lsc, gmean,   \
+                                       gvar, gyk, gls, gnz, gnu, info, workspace, workspace_bytes, st);              \
+  }
+MGP_DEFINE_BWD_GEN_LARGE(f32, float)
+MGP_DEFINE_BWD_GEN_LARGE(f64, double)
+#define MGP_DEFINE_BWD_LARGE_FULL(SUF, T)                                                                          \
   int mgp_posterior_backward_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,      \
                                          int64_t b, int k, const T* tg, int R, int nm, double eps, const T* nd,      \
                                          int kid, int mid, const T* ls, int lsc, const T* gmean, const T* gvar,      \

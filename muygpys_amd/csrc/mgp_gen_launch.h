@@ -18,12 +18,27 @@ struct GenLaunch {
   double h64, lc64, xmin64;  // fp64: spacing, ln(h 2^(1-nu) / Gamma(nu)), smallest x of the table
   float h, lc;               // fp32: spacing, log2(h 2^(1-nu) / Gamma(nu))
   int tab;                   // byte offset of the node table in dynamic LDS (behind everything else)
+  int dtab;                  // ... and of the derivative table behind it (the backward, mgp_backward_gen_large.hip)
+  double psi;                // digamma(nu): dk/dnu (read by the backward alone)
 };
+
+// digamma(x), x > 0: the recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 10, then the asymptotic series (its first
+// omitted term is below 1e-13 there)
+inline double gen_digamma(double x) {
+  double s = 0.0;
+  while (x < 10.0) {
+    s -= 1.0 / x;
+    x += 1.0;
+  }
+  const double f = 1.0 / (x * x);
+  return s + log(x) - 0.5 / x - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
+}
 
 // the constants of one smoothness; fp64 = false leaves the fp64 members at values no kernel reads
 inline GenLaunch gen_launch_constants(double nu, bool fp64) {
-  GenLaunch g{0.3, 0.0, 1e-12, 0.5f, 0.0f, 0};
+  GenLaunch g{0.3, 0.0, 1e-12, 0.5f, 0.0f, 0, 0, 0.0};
   const double h = gen_step(nu);
+  g.psi = gen_digamma(nu);
   g.h = (float)h;
   g.lc = (float)((log(h) + (1.0 - nu) * log(2.0) - lgamma(nu)) / log(2.0));
   if (fp64) {  // finer step, natural logarithms, a larger table
@@ -97,9 +112,34 @@ __device__ __forceinline__ void gen_build_node_table(T* tab, double nu, const Ge
   else gen_build_table64(tab, nu, g.h64, tid);
 }
 
+// bytes of the derivative table (gen_build_deriv_table / gen_build_deriv_table64): two more columns per node
+inline size_t gen_deriv_table_bytes(int elem_size) { return gen_table_bytes(elem_size); }
+
+// both tables of the backward, once per workgroup (visible behind the next barrier)
+template <typename T>
+__device__ __forceinline__ void gen_build_deriv_node_table(T* dtab, double nu, const GenLaunch& g, int tid) {
+  if (tid >= MGP_WAVE) return;
+  if constexpr (sizeof(T) == 4) gen_build_deriv_table(dtab, (float)nu, g.h, tid);
+  else gen_build_deriv_table64(dtab, nu, g.h64, tid);
+}
+
+// The derivatives of one strip of pairs (gen_covariance_phase's strip: NT threads x PC pairs, pair p0 + u NT + tid is
+// thread tid's u-th): v[u] = metric argument in, dk/dr out; dnu[u] = dk/dnu when NU.  Every thread of the workgroup
+// calls this the same number of times.
+template <typename T, bool NU>
+__device__ __forceinline__ void gen_deriv_strip(T (&v)[gen_pairs_per_call<T>()], T (&dnu)[gen_pairs_per_call<T>()], unsigned live,
+                                                double nu, const GenLaunch& g, const T* tab, const T* dtab) {
+  constexpr int PC = gen_pairs_per_call<T>();
+  if constexpr (sizeof(T) == 4) matern_gen_deriv_eval<PC, NU>(v, dnu, live, tab, dtab, (float)nu, g.h, g.lc, (float)g.psi);
+  else matern_gen_deriv_batch64<PC, NU>(v, dnu, live, tab, dtab, nu, g.h64, g.lc64, g.xmin64, g.psi);
+}
+
 // the general-smoothness launches of the workgroup families (mgp_generic.hip, mgp_large.hip); a.smoothness is set
 template <typename T> int launch_fused_generic_gen(const FusedArgs&, hipStream_t);
 template <typename T> int launch_fused_large_gen(const FusedArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
 int max_nn_count_gen(int elem_size, int R);
+// ... and of the hyper-parameter backward on the slab factor (mgp_backward_gen_large.hip): grad_nu (b) may be NULL
+template <typename T> int launch_hyper_backward_gen_large(const BackwardArgs&, void* grad_nu, void* workspace, int64_t workspace_bytes, hipStream_t);
+int backward_gen_large_max_nn_count(int elem_size);
 
 }  // namespace mgp

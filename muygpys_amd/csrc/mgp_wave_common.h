@@ -807,6 +807,202 @@ __device__ __forceinline__ void matern_gen_batch64(double (&v)[CB], unsigned liv
 #pragma unroll
   for (int u = 0; u < CB; ++u) v[u] = acc[u];
 }
+
+// ---- derivatives of the general-smoothness Matern (the backward on the slab factor, mgp_backward_gen_large.hip) ------
+// The same trapezoidal rule with other node weights, every term in the log domain as above.  With x = sqrt(2 nu) r,
+// c = 2^(1-nu) / Gamma(nu), k = c x^nu K_nu(x):
+//     dk/dr      = -sqrt(2 nu) c x^nu K_{nu-1}(x)                         weights cosh((nu-1) t_n): no cancellation
+//     dk/dnu |_r = k (ln x - ln 2 - psi(nu)) + c x^nu dK_nu/dnu + (x / (2 nu)) dk/dx,      dk/dx = -c x^nu K_{nu-1}(x)
+//     dK_nu/dnu  = int_0^inf exp(-x cosh t) t sinh(nu t) dt              weights t_n sinh(nu t_n) >= 0, none at node 0
+// The derivative table holds, per node, (ln cosh((nu-1) t_n) [half weight at n = 0], ln(t_n sinh(nu t_n))) next to the
+// forward table's (-cosh t_n, ln cosh(nu t_n)); log2 in fp32.  The node count covers the slowest-decaying weight,
+// exp(max(nu, 1 - nu) t) -- below nu = 1/2 that is cosh((1 - nu) t) -- and leaves e^-4 for the factor t_n of the third
+// sum.  The clamps on x are the forward's; a pair at zero distance returns 0 for both (k(0) = 1 for every nu, and its
+// length-scale term carries a factor x).  NU = false pays for one exponential per node, NU = true for three.  Checked
+// against scipy in tests/test_matern_gen_deriv_cpu.py (the same arithmetic in numpy at the working precision).
+#define MGP_GEN_NO_TERM -1.0e4f  // the logarithm of a node weight that is zero
+__device__ __forceinline__ void gen_build_deriv_table(float* dtab, float nu, float h, int lane) {
+  for (int n = lane; n < MGP_GEN_NODES; n += 64) {
+    const float t = n * h, a = nu * t, b = fabsf(nu - 1.0f) * t;
+    dtab[2 * n] = (b + log1pf(expf(-2.0f * b)) - 0.693147180559945f) * 1.44269504088896f - (n == 0 ? 1.0f : 0.0f);
+    dtab[2 * n + 1] = n == 0 ? MGP_GEN_NO_TERM : (logf(t) + a + logf(-expm1f(-2.0f * a)) - 0.693147180559945f) * 1.44269504088896f;
+  }
+}
+
+// in: r[s] = metric argument of the lane's NS pairs; out: r[s] = dk/dr there and, NU, dnu[s] = dk/dnu.  `live`, tab,
+// h, lc as matern_gen_eval; dtab: gen_build_deriv_table; psi = digamma(nu)
+template <int NS, bool NU>
+__device__ __forceinline__ void matern_gen_deriv_eval(float (&r)[NS], float (&dnu)[NS], unsigned live, const float* tab,
+                                                      const float* dtab, float nu, float h, float lc, float psi) {
+  constexpr int NP2 = (NS + 1) / 2;
+  f2 x2[NP2], L2[NP2], lx2[NP2], s1[NP2], s0[NP2], sd[NP2];
+  const float s2nu = __builtin_amdgcn_sqrtf(2.0f * nu);
+  const float mu = __builtin_fmaxf(nu, 1.0f - nu);
+  float nmaxf = 1.0f;
+  unsigned zero = 0;
+#pragma unroll
+  for (int s = 0; s < NP2 * 2; ++s) {
+    float x = 1.0f;
+    if (s < NS && ((live >> s) & 1u)) {
+      if (r[s] == 0.0f) zero |= 1u << s;
+      x = r[s] != r[s] ? r[s] : __builtin_fminf(__builtin_fmaxf(r[s] * s2nu, 1e-6f), 3.0e4f);
+    }
+    const float lx = __builtin_amdgcn_logf(x);  // log2
+    // nodes until x cosh t - mu t > ~26: T = ln(2 (26 + mu max(1, ln(52 / x))) / x)
+    const float inner = 26.0f + mu * __builtin_fmaxf(1.0f, (5.7004397f - lx) * 0.693147181f);
+    const float T = (__builtin_amdgcn_logf(2.0f * inner) - lx) * 0.693147181f;
+    nmaxf = __builtin_fmaxf(nmaxf, T);
+    const float Ls = __builtin_fmaf(nu, lx, lc);
+    if (s & 1) {
+      x2[s / 2].y = x;
+      L2[s / 2].y = Ls;
+      lx2[s / 2].y = lx;
+    } else {
+      x2[s / 2].x = x;
+      L2[s / 2].x = Ls;
+      lx2[s / 2].x = lx;
+    }
+  }
+  int N = (int)(nmaxf / h) + 3;
+  N = N < MGP_GEN_NODES ? N : MGP_GEN_NODES;
+#pragma unroll
+  for (int p = 0; p < NP2; ++p) s1[p] = s0[p] = sd[p] = f2{0.0f, 0.0f};
+  for (int n = 0; n < MGP_GEN_NODES; ++n) {
+    if (__builtin_amdgcn_ballot_w64(n < N) == 0) break;  // (uniform: the longest tail of the wave)
+    const f2 cl = *reinterpret_cast<const f2*>(tab + 2 * n);   // uniform LDS reads: (-c_n, l_n)
+    const f2 dl = *reinterpret_cast<const f2*>(dtab + 2 * n);  // (l_n of nu - 1, l_n of t sinh(nu t))
+    const f2 negc = {cl.x, cl.x}, l1 = {dl.x, dl.x};
+#pragma unroll
+    for (int p = 0; p < NP2; ++p) {
+      const f2 base = x2[p] * negc + L2[p];
+      const f2 a1 = base + l1;
+      f2 e;
+      e.x = __builtin_amdgcn_exp2f(a1.x);
+      e.y = __builtin_amdgcn_exp2f(a1.y);
+      s1[p] = s1[p] + e;
+      if constexpr (NU) {
+        const f2 a0 = base + f2{cl.y, cl.y}, ad = base + f2{dl.y, dl.y};
+        e.x = __builtin_amdgcn_exp2f(a0.x);
+        e.y = __builtin_amdgcn_exp2f(a0.y);
+        s0[p] = s0[p] + e;
+        e.x = __builtin_amdgcn_exp2f(ad.x);
+        e.y = __builtin_amdgcn_exp2f(ad.y);
+        sd[p] = sd[p] + e;
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const bool z = (zero >> s) & 1u;
+    const float k1 = s & 1 ? s1[s / 2].y : s1[s / 2].x;
+    r[s] = z ? 0.0f : -s2nu * k1;
+    if constexpr (NU) {
+      const float k0 = s & 1 ? s0[s / 2].y : s0[s / 2].x, kd = s & 1 ? sd[s / 2].y : sd[s / 2].x;
+      const float x = s & 1 ? x2[s / 2].y : x2[s / 2].x, lx = s & 1 ? lx2[s / 2].y : lx2[s / 2].x;
+      const float v = k0 * (lx * 0.693147181f - 0.693147180559945f - psi) + kd - (x / (2.0f * nu)) * k1;
+      dnu[s] = z ? 0.0f : v;
+    }
+  }
+}
+
+// ... and in fp64: natural logarithms, the software exp of matern_gen_batch64, its step and its clamps; nodes until
+// x cosh t - mu t > 41
+__device__ __forceinline__ void gen_build_deriv_table64(double* dtab, double nu, double h, int lane) {
+  for (int n = lane; n < MGP_GEN_NODES64; n += 64) {
+    const double t = n * h, a = nu * t, b = fabs(nu - 1.0) * t;
+    dtab[2 * n] = b + log1p(exp(-2.0 * b)) - 0.693147180559945309417 - (n == 0 ? 0.693147180559945309417 : 0.0);
+    dtab[2 * n + 1] = n == 0 ? (double)MGP_GEN_NO_TERM : ::log(t) + a + ::log(-expm1(-2.0 * a)) - 0.693147180559945309417;
+  }
+}
+// e[u] = exp(-t[u]), CB chains interleaved (the stages of exp_neg())
+template <int CB>
+__device__ __forceinline__ void gen_exp_neg_batch64(const double (&t)[CB], double (&e)[CB]) {
+  constexpr auto C = [](unsigned long long bits) { return __builtin_bit_cast(double, bits); };
+  double m[CB], r[CB], q[CB];
+#pragma unroll
+  for (int u = 0; u < CB; ++u) m[u] = __builtin_rint(t[u] * -1.4426950408889634074);
+#pragma unroll
+  for (int u = 0; u < CB; ++u) r[u] = __builtin_fma(m[u], -6.93147180369123816490e-01, -t[u]);
+#pragma unroll
+  for (int u = 0; u < CB; ++u) r[u] = __builtin_fma(m[u], -1.90821492927058770002e-10, r[u]);
+#pragma unroll
+  for (int u = 0; u < CB; ++u) q[u] = fma_sc(r[u], C(0x3e5ae64567f544e4ull), C(0x3e928af3fca7ab0cull));
+  constexpr unsigned long long coef[8] = {0x3ec71dee623fde64ull, 0x3efa01997c89e6b0ull, 0x3f2a01a014761f6eull, 0x3f56c16c1852b7b0ull,
+                                          0x3f81111111122322ull, 0x3fa55555555502a1ull, 0x3fc5555555555511ull, 0x3fe000000000000bull};
+#pragma unroll
+  for (int c = 0; c < 8; ++c)
+#pragma unroll
+    for (int u = 0; u < CB; ++u) q[u] = fma_sc(q[u], r[u], C(coef[c]));
+#pragma unroll
+  for (int u = 0; u < CB; ++u) q[u] = __builtin_fma(q[u], r[u], 1.0);
+#pragma unroll
+  for (int u = 0; u < CB; ++u) q[u] = __builtin_fma(q[u], r[u], 1.0);
+#pragma unroll
+  for (int u = 0; u < CB; ++u) e[u] = __builtin_amdgcn_ldexp(q[u], cvt_i32_sat(m[u]));
+}
+// in: v[u] = metric argument of CB pairs; out: v[u] = dk/dr and, NU, dnu[u] = dk/dnu.  `live`, tab, h, lc, xmin as
+// matern_gen_batch64; dtab: gen_build_deriv_table64; psi = digamma(nu)
+template <int CB, bool NU>
+__device__ __forceinline__ void matern_gen_deriv_batch64(double (&v)[CB], double (&dnu)[CB], unsigned live, const double* tab,
+                                                         const double* dtab, double nu, double h, double lc, double xmin,
+                                                         double psi) {
+  double x[CB], L[CB], lxs[CB], s1[CB], s0[CB], sd[CB];
+  const double s2nu = ::sqrt(2.0 * nu);
+  const double mu = __builtin_fmax(nu, 1.0 - nu);
+  double tmax = 1.0;
+  unsigned zero = 0;
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    double xx = 1.0;
+    if ((live >> u) & 1u) {
+      if (v[u] == 0.0) zero |= 1u << u;
+      const double r = v[u] == 0.0 ? 2.220446049250313e-16 : v[u];
+      xx = r != r ? r : __builtin_fmin(__builtin_fmax(r * s2nu, xmin), 1.0e5);
+    }
+    const double lx = ::log(xx);
+    tmax = __builtin_fmax(tmax, ::log(2.0 * (41.0 + mu * __builtin_fmax(1.0, 4.40671924726425 - lx))) - lx);
+    x[u] = xx;
+    lxs[u] = lx;
+    L[u] = __builtin_fma(nu, lx, lc);
+    s1[u] = s0[u] = sd[u] = 0.0;
+  }
+  int N = (int)(tmax / h) + 3;
+  N = N < MGP_GEN_NODES64 ? N : MGP_GEN_NODES64;
+  for (int n = 0; n < MGP_GEN_NODES64; ++n) {
+    if (__builtin_amdgcn_ballot_w64(n < N) == 0) break;  // (uniform: the longest tail of the wave)
+    const double negc = tab[2 * n], l1 = dtab[2 * n];  // uniform LDS reads
+    double base[CB], t[CB], e[CB];
+#pragma unroll
+    for (int u = 0; u < CB; ++u) base[u] = __builtin_fma(x[u], negc, L[u]);
+#pragma unroll
+    for (int u = 0; u < CB; ++u) t[u] = -(base[u] + l1);
+    gen_exp_neg_batch64<CB>(t, e);
+#pragma unroll
+    for (int u = 0; u < CB; ++u) s1[u] += e[u];
+    if constexpr (NU) {
+      const double l0 = tab[2 * n + 1], ld = dtab[2 * n + 1];
+#pragma unroll
+      for (int u = 0; u < CB; ++u) t[u] = -(base[u] + l0);
+      gen_exp_neg_batch64<CB>(t, e);
+#pragma unroll
+      for (int u = 0; u < CB; ++u) s0[u] += e[u];
+#pragma unroll
+      for (int u = 0; u < CB; ++u) t[u] = -(base[u] + ld);
+      gen_exp_neg_batch64<CB>(t, e);
+#pragma unroll
+      for (int u = 0; u < CB; ++u) sd[u] += e[u];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < CB; ++u) {
+    const bool z = (zero >> u) & 1u;
+    v[u] = z ? 0.0 : -s2nu * s1[u];
+    if constexpr (NU) {
+      const double w = s0[u] * (lxs[u] - 0.693147180559945309417 - psi) + sd[u] - (x[u] / (2.0 * nu)) * s1[u];
+      dnu[u] = z ? 0.0 : w;
+    }
+  }
+}
 // metric argument of CB squared distances in fp64: the lean square root of cov_batch64() under the l2 metric
 template <int CB, int MID>
 __device__ __forceinline__ void metric_batch64(double (&v)[CB], double post_scale) {

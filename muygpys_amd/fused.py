@@ -679,7 +679,7 @@ class LoocvPlan:
 
 
 
-def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want_noise: bool = True):
+def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want_noise: bool = True, want_nu: bool = False):
     """One backward launch for the hyper-parameters: the per-neighbourhood partials ``(g_l (b, ls_count), g_n (b, k) or
     None)`` of the cotangents ``gm`` / ``gv`` (either may be None) -- and ``gyk`` of ``y^T K^-1 y``: given, the launch is
     the LOOCV objective's (``mgp_loocv_backward_*``, one response), else ``mgp_posterior_backward_*`` with no feature or
@@ -687,9 +687,18 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
 
     A closed-form kernel whose two triangles no longer fit LDS (``nn_count`` beyond ``mgp_max_nn_count_backward``) goes
     to the backward on the slab factor (``mgp_hyper_backward_large_*``, csrc/mgp_backward_large.hip), up to
-    ``mgp_large_max_nn_count(elem_size, 1)`` = 1022 whatever the response count; ``ValueError`` beyond."""
+    ``mgp_large_max_nn_count(elem_size, 1)`` = 1022 whatever the response count; ``ValueError`` beyond.
+
+    The general-smoothness Matern has one rung at every ``nn_count``: its own backward on the slab factor
+    (``mgp_hyper_backward_gen_large_*``, csrc/mgp_backward_gen_large.hip) with ``spec.smoothness``, up to
+    ``mgp_backward_gen_large_max_nn_count``; ``ValueError`` beyond.  ``want_nu`` (that kernel alone): a third result,
+    the per-neighbourhood partials ``g_nu (b,)`` with respect to the smoothness."""
     P = _lib.ptr
     fn, ls = inp.fn, inp.ls
+    if spec.kernel == "matern_gen":
+        return _hyper_partials_gen(spec, inp, info, gm, gv, gyk, want_noise, want_nu)
+    if want_nu:
+        raise ValueError(f"kernel {spec.kernel!r} has a fixed smoothness: no gradient with respect to it")
     g_l = torch.zeros((inp.b, ls.numel()), device=fn.device, dtype=fn.dtype)
     g_n = torch.zeros((inp.b, inp.k), device=fn.device, dtype=fn.dtype) if want_noise else None
     gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
@@ -714,23 +723,71 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     return g_l, g_n
 
 
-def _hyper_gradient(g_l, g_n, info, what: str, reduce_fn):
+def _hyper_partials_gen(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_noise: bool, want_nu: bool):
+    """:func:`_hyper_partials` of the general-smoothness Matern: ``(g_l, g_n or None[, g_nu])``."""
+    P = _lib.ptr
+    fn, ls = inp.fn, inp.ls
+    nu = spec.smoothness
+    if nu is None or not float(nu) > 0.0:
+        raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {nu}")
+    limit = int(_lib.load().mgp_backward_gen_large_max_nn_count(fn.element_size()))
+    if inp.k > limit:
+        raise ValueError(f"analytic gradients of the general-smoothness Matern: nn_count = {inp.k} is beyond "
+                         f"mgp_backward_gen_large_max_nn_count = {limit}")
+    g_l = torch.zeros((inp.b, ls.numel()), device=fn.device, dtype=fn.dtype)
+    g_n = torch.zeros((inp.b, inp.k), device=fn.device, dtype=fn.dtype) if want_noise else None
+    g_nu = torch.zeros((inp.b,), device=fn.device, dtype=fn.dtype) if want_nu else None
+    gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
+
+    def slab():
+        ws = _lib.backward_large_workspace(fn.dtype, inp.k, inp.b, fn.device)
+        return _lib.fn("hyper_backward_gen_large", fn.dtype)(
+            P(fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, _lib.NOISE_SCALAR, float(spec.noise), None,
+            float(nu), spec.metric_id(), P(ls), ls.numel(), P(gm), P(gv), P(gyk), P(g_l), P(g_n), P(g_nu), P(info),
+            P(ws), ws.numel(), _lib.stream_ptr())
+
+    rc, _ = _lib.run_ladder((slab,))
+    _lib.check(rc, "mgp_hyper_backward_gen_large")
+    return (g_l, g_n, g_nu) if want_nu else (g_l, g_n)
+
+
+def _hyper_gradient(g_l, g_n, info, what: str, reduce_fn, g_nu=None):
     """The tail of an analytic gradient: the SPD check of the backward launches, deterministic fp64 column sums of
-    their partials, the sum over the ranks -- ``(grad_length_scale (numpy, ls_count), grad_noise (float))``."""
+    their partials, the sum over the ranks -- ``(grad_length_scale (numpy, ls_count), grad_noise (float))``, and
+    ``grad_smoothness (float)`` behind them when ``g_nu`` is given."""
     import numpy as np
 
     _lib.raise_if_not_spd(info, what)
-    grad = torch.cat([_lib.column_sums(g_l), _lib.column_sums(g_n.reshape(-1, 1))])  # fp64, deterministic
+    cols = [_lib.column_sums(g_l), _lib.column_sums(g_n.reshape(-1, 1))]  # fp64, deterministic
+    if g_nu is not None:
+        cols.append(_lib.column_sums(g_nu.reshape(-1, 1)))
+    grad = torch.cat(cols)
     if reduce_fn is not None:
         reduce_fn(grad)
     g = grad.cpu().numpy()
+    if g_nu is not None:
+        return np.asarray(g[:-2], dtype=np.float64), float(g[-2]), float(g[-1])
     return np.asarray(g[:-1], dtype=np.float64), float(g[-1])
+
+
+def _loocv_forward(spec: KernelSpec, train_features, train_targets, bi, ni, packed, huber_delta: float):
+    """``(partials, mean, var, ykinvy)`` of one LOOCV evaluation: :func:`loocv_partials`, or -- the general-smoothness
+    Matern, which ``mgp_loocv_*`` serves on the wave kernels alone -- the fused posterior with ``y^T K^-1 y`` at any
+    ``nn_count`` followed by the reduction tree over its outputs (:func:`loocv_tree_sums`)."""
+    if spec.kernel != "matern_gen":
+        return loocv_partials(spec, train_features, train_targets, bi, ni, packed=packed, return_ykinvy=True,
+                              huber_delta=huber_delta)
+    mean, var, yk = posterior_mean_var(spec, train_features, train_features, bi, ni, train_targets, want_ykinvy=True,
+                                       packed=packed)
+    mean, var, yk = mean.reshape(-1), var.reshape(-1), yk.reshape(-1)
+    return loocv_tree_sums(mean, var, yk, train_targets, bi, huber_delta), mean, var, yk
 
 
 def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_targets: torch.Tensor,
                          batch_indices: torch.Tensor, nn_indices: torch.Tensor, loss: str = "lool",
                          packed: Union[str, bool] = "auto", reduce_fn=None, scale=("analytic", 1),
-                         boundary_scale: Optional[float] = None, sigma_noise: Optional[float] = None):
+                         boundary_scale: Optional[float] = None, sigma_noise: Optional[float] = None,
+                         grad_smoothness: bool = False):
     """A LOOCV loss and its ANALYTIC gradient with respect to the length scale(s) and a homoscedastic noise: one
     forward evaluation (``mgp_loocv_*``) and one backward launch (``mgp_loocv_backward_*``) instead of the ``p + 1``
     forward evaluations per iteration scipy's finite differences cost the reference's L-BFGS-B driver
@@ -764,8 +821,14 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     Any ``nn_count`` the forward serves: beyond ``mgp_max_nn_count_backward`` the backward launches run on the slab
     factor in global memory (``mgp_hyper_backward_large_*``), up to ``nn_count = 1022``; ``ValueError`` beyond.
 
+    The general-smoothness Matern (``spec.kernel == "matern_gen"``): the forward is the fused posterior with
+    ``y^T K^-1 y`` and the reduction tree over its outputs, the backward ``mgp_hyper_backward_gen_large_*`` at every
+    ``nn_count`` up to 1022.  ``grad_smoothness`` (that kernel alone): the gradient with respect to nu as well -- the
+    cotangent of ``y^T K^-1 y`` (the analytic sigma^2 with its fixed-point passes, the ``sigma_noise`` split with its
+    second backward launch) reaches it the way it reaches the length scales.
+
     Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS (the objective the
-    drivers maximise is its negative)."""
+    drivers maximise is its negative); with ``grad_smoothness`` ``(value, grad_ls, grad_noise, grad_nu (float))``."""
     import copy
     import math
 
@@ -773,14 +836,14 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
         raise NotImplementedError(f"analytic gradients are written out for lool, mse, pseudo_huber and looph, not {loss!r}")
     if isinstance(spec.noise, torch.Tensor) and spec.noise.ndim >= 1:
         raise NotImplementedError("analytic gradients: homoscedastic noise")
-    if spec.kernel == "matern_gen":
-        raise NotImplementedError("analytic gradients: closed-form kernels (fixed smoothness)")
+    if grad_smoothness and spec.kernel != "matern_gen":
+        raise ValueError(f"grad_smoothness: kernel {spec.kernel!r} has a fixed smoothness")
     inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_targets, responses="single")
     dtype, tg, ni, bi, k = inp.fn.dtype, inp.tg, inp.ni, inp.bi, inp.k
     needs_scale = loss in ("lool", "looph")
     delta = float(boundary_scale) if boundary_scale is not None else (3.0 if loss == "looph" else 1.5)
-    partials, mean, var, yk = loocv_partials(spec, train_features, train_targets, bi, ni, packed=packed, return_ykinvy=True,
-                                             huber_delta=delta if loss == "pseudo_huber" else 1.5)
+    huber = delta if loss == "pseudo_huber" else 1.5
+    partials, mean, var, yk = _loocv_forward(spec, train_features, train_targets, bi, ni, packed, huber)
     # (sigma_noise given = the noise is a VARIABLE of the caller's function while sigma^2 holds its own, constant one:
     # the cotangent of y^T K^-1 y must not reach the noise gradient even where the two values coincide)
     split_bwd = needs_scale and scale[0] == "analytic" and sigma_noise is not None
@@ -789,7 +852,7 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     if split:  # sigma^2 at the stored noise: y^T K^-1 y of a second evaluation
         spec_s = copy.copy(spec)
         spec_s.noise = float(sigma_noise)
-        partials_s = loocv_partials(spec_s, train_features, train_targets, bi, ni, packed=packed)[0]
+        partials_s = _loocv_forward(spec_s, train_features, train_targets, bi, ni, packed, 1.5)[0]
         partials = torch.cat([partials[:5], partials_s[5:6]])
     if reduce_fn is not None:
         reduce_fn(partials)
@@ -832,17 +895,21 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     gv = zeros if gv is None else gv
     gyk_value = dL_ds * ds / (n * k) if needs_scale else 0.0
     info = torch.zeros(1, device=inp.fn.device, dtype=torch.int32)
+    nu = {"want_nu": True} if grad_smoothness else {}
     if split_bwd:
-        g_l, g_n = _hyper_partials(spec, inp, info, gm, gv, zeros)
-        g_l = g_l + _hyper_partials(spec_s, inp, info, zeros, zeros, torch.full_like(var, gyk_value), want_noise=False)[0]
+        g_l, g_n, *g_nu = _hyper_partials(spec, inp, info, gm, gv, zeros, **nu)
+        second = _hyper_partials(spec_s, inp, info, zeros, zeros, torch.full_like(var, gyk_value), want_noise=False, **nu)
+        g_l = g_l + second[0]
+        g_nu = [g_nu[0] + second[2]] if grad_smoothness else g_nu
     else:
-        g_l, g_n = _hyper_partials(spec, inp, info, gm, gv, torch.full_like(var, gyk_value) if gyk_value != 0.0 else zeros)
-    return (value, *_hyper_gradient(g_l, g_n, info, "LOOCV gradient", reduce_fn))
+        g_l, g_n, *g_nu = _hyper_partials(spec, inp, info, gm, gv,
+                                          torch.full_like(var, gyk_value) if gyk_value != 0.0 else zeros, **nu)
+    return (value, *_hyper_gradient(g_l, g_n, info, "LOOCV gradient", reduce_fn, *g_nu))
 
 
 def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_labels: torch.Tensor,
                          batch_indices: torch.Tensor, nn_indices: torch.Tensor, loss: str = "cross_entropy",
-                         packed: Union[str, bool] = "auto", reduce_fn=None):
+                         packed: Union[str, bool] = "auto", reduce_fn=None, grad_smoothness: bool = False):
     """A classification LOOCV loss on ``R >= 2`` one-hot response columns and its ANALYTIC gradient with respect to
     the length scale(s) and a homoscedastic noise: the fused posterior (``posterior_mean_var``), one
     ``mgp_class_sums_*`` launch that returns the loss sums and the cotangent of the (b, R) mean, and one
@@ -856,15 +923,17 @@ def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_l
     the mse count is the global one) and to the gradient.
 
     Any ``nn_count`` the forward serves (``nn_count + 1 + R <= 1024``): beyond ``mgp_max_nn_count_backward`` the
-    backward launch runs on the slab factor in global memory (``mgp_hyper_backward_large_*``).
+    backward launch runs on the slab factor in global memory (``mgp_hyper_backward_large_*``).  The general-smoothness
+    Matern: ``mgp_hyper_backward_gen_large_*`` at every ``nn_count`` up to 1022, and with ``grad_smoothness`` the gradient
+    with respect to nu as a fourth result.
 
     Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS."""
     if loss not in ("cross_entropy", "mse"):
         raise NotImplementedError(f"classification gradients are written out for cross_entropy and mse, not {loss!r}")
     if isinstance(spec.noise, torch.Tensor) and spec.noise.ndim >= 1:
         raise NotImplementedError("analytic gradients: homoscedastic noise")
-    if spec.kernel == "matern_gen":
-        raise NotImplementedError("analytic gradients: closed-form kernels (fixed smoothness)")
+    if grad_smoothness and spec.kernel != "matern_gen":
+        raise ValueError(f"grad_smoothness: kernel {spec.kernel!r} has a fixed smoothness")
     inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_labels, responses="labels")
     fn, tg, bi, b, R = inp.fn, inp.tg, inp.bi, inp.b, inp.R
     info = torch.zeros(1, device=fn.device, dtype=torch.int32)
@@ -881,8 +950,8 @@ def class_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_l
             reduce_fn(sums)
     ce, r2sum, count = (float(v) for v in sums[:3].tolist())
     value = ce if loss == "cross_entropy" else r2sum / count
-    g_l, g_n = _hyper_partials(spec, inp, info, gm, None)
-    return (value, *_hyper_gradient(g_l, g_n, info, "classification gradient", reduce_fn))
+    g_l, g_n, *g_nu = _hyper_partials(spec, inp, info, gm, None, **({"want_nu": True} if grad_smoothness else {}))
+    return (value, *_hyper_gradient(g_l, g_n, info, "classification gradient", reduce_fn, *g_nu))
 
 
 def loocv_tree_sums(mean: torch.Tensor, var: torch.Tensor, ykinvy: torch.Tensor, train_targets: torch.Tensor,
