@@ -22,6 +22,8 @@ def _dev_inputs(g, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_tensor_family(golden, dtype):
+    """The golden fixtures' shapes through the Python layer; every launch route, shape edge and derived error bound of
+    these kernels: tests/test_gpu_tensor_ops_edges.py."""
     from muygpys_amd._src.gp import tensors as T
     from muygpys_amd._src.gp.tensors import hip as Th
 
