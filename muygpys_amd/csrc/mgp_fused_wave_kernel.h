@@ -48,11 +48,29 @@
 #include "mgp_wave_common.h"
 
 // Phase tests: WaveGeom::mask is a kernel argument, always 0xF in the shipped library (only builds
-// with -DMGP_DEBUG_HOOKS export a setter, for the timing ablations of tools/kbench.py).  The test
-// stays a run-time one on purpose: with the phases fused into one straight-line region the
+// with -DMGP_DEBUG_HOOKS export a setter, for the timing ablations of tools/kbench.py).  Most tests
+// stay run-time ones on purpose: with the phases fused into one straight-line region the
 // compiler hoists per-lane addresses of all phases to the top of the task loop and the static
 // shapes spill (168 VGPRs + 164 B scratch instead of 134 and none; 2.78 instead of 2.22 ms).
-#define MGP_PHASE(g, bit) ((g).mask & (bit))
+// MGP_PHASE_STATIC: the bits whose test is `true` at compile time in builds without the hooks.  At the headline
+// instantiation (fp32, k = 30, d = 40, prepared tables; 168 VGPRs, none spilled, as it stands):
+//   all four (15)            63 VGPRs spilled, 188 B of scratch
+//   factor (8)               54 spilled
+//   distances (2)             2 spilled -- with or without the zeroing of the Gram accumulators
+//   gather + exchange (5)     none there, 16 instructions and two branches fewer per task -- but the exchange bit
+//                             spills 38 registers of the fp64 k = 50, d = 8 kernels and costs the fp64 32-slot ones
+//                             their third wave; the gather bit alone is worth 3 instructions
+// so: none (0).
+// The Gram loop's own test is dropped wherever its first block writes the accumulators (ACC_FIRST, phase 2).
+#ifdef MGP_DEBUG_HOOKS
+#define MGP_PHASE_HOOKS 1
+#else
+#define MGP_PHASE_HOOKS 0
+#endif
+#ifndef MGP_PHASE_STATIC
+#define MGP_PHASE_STATIC 0
+#endif
+#define MGP_PHASE(g, bit) ((((bit) & (MGP_PHASE_STATIC)) != 0) || ((g).mask & (bit)))
 
 #ifndef MGP_F64_SAME_PRIO
 #define MGP_F64_SAME_PRIO 0
@@ -127,6 +145,10 @@
 #define MGP_F64_DIST_HALF 0
 #endif
 // (folded fp32 kernels, Gram form) partner groups in flight ahead of the block that consumes one.  See phase 2.
+// (pipelined Gram loop) the first block of every accumulator writes it instead of adding to a zeroed one
+#ifndef MGP_GRAM_FIRST_WRITE
+#define MGP_GRAM_FIRST_WRITE 1
+#endif
 #ifndef MGP_GRAM_PREFETCH
 #define MGP_GRAM_PREFETCH 3
 #endif
@@ -278,6 +300,65 @@ constexpr int wave_tile_rows(const WaveDims& w, int NP, int KFIX, int xs) {
 constexpr int wave_gather_pieces(const WaveDims& w, int KFIX, int xs) {
   const int spr = xs / w.E;
   return (w.STAT && w.NH == 1) ? ((KFIX + 1) * spr + 63) / 64 : spr;
+}
+// ---- the gather in WHOLE-ROW pieces.  The image is the one above (row r at slot r * spr, spr 16-byte slots a row, the
+// last one padding); a piece is one direct-to-LDS instruction, lane l writing 16 bytes at the piece's base + 16 l.
+// Piece p starts at row RPP p, RPP = 64 / spr rows per piece, so lane l always lands in row-of-piece l / spr, slot
+// l % spr: what a lane fetches is fixed for the whole gather (one divide per gather instead of one per piece), and no
+// piece crosses a row.  Lanes RPP spr .. 63 and lanes whose row lies behind the last gathered one are switched off:
+// they would write into the next piece's rows, or -- the last piece -- behind the tile, where the row pointers live.
+// The rule as plain functions, shared by the kernel, its static_asserts and tests/test_wave_gather_pieces_cpu.py.
+struct WaveGatherLane {
+  int rr, c;    // row inside the piece, 16-byte slot fetched (padding slots repeat slot `last`)
+  bool active;  // lane < RPP * spr
+};
+constexpr WaveGatherLane wave_gather_lane(int lane, int spr, int last) {
+  const int rr = lane / spr, c = lane - rr * spr;
+  return WaveGatherLane{rr, c < last ? c : last, lane < (64 / spr) * spr};
+}
+// does the lane write in piece p?  (`rows` gathered rows; spelled so that it folds to `active` for every piece but the last)
+constexpr bool wave_gather_on(const WaveGatherLane& l, int p, int spr, int rows) {
+  const int rpp = 64 / spr, left = rows - rpp * p;
+  return left >= rpp ? l.active : (l.active && l.rr < left);
+}
+// rows the gather fills: all 64 slots of the wave, or -- one static neighbourhood per wave -- the rows the image-order
+// pieces fill completely (the feature rows and whatever of the rows behind them the last piece covers)
+constexpr int wave_gather_rows(const WaveDims& w, int NP, int KFIX, int xs) {
+  if (!(w.STAT && w.NH == 1)) return w.NH * NP;
+  const int spr = xs / w.E, full = wave_gather_pieces(w, KFIX, xs) * 64 / spr;
+  return full < wave_tile_rows(w, NP, KFIX, xs) ? full : wave_tile_rows(w, NP, KFIX, xs);
+}
+constexpr int wave_gather_row_pieces(int rows, int spr) { return (rows + 64 / spr - 1) / (64 / spr); }
+// Which instantiations gather in whole-row pieces: static feature counts whose piece count stays within a quarter of
+// the image-order one (long rows multiply it: fp32 d = 64, 17 slots, 22 pieces for 17; d = 8, 3 slots, 4 for 3).  The
+// run-time-shape kernels keep the image order.
+#ifndef MGP_GATHER_ROWS
+#define MGP_GATHER_ROWS 1
+#endif
+constexpr int WAVE_GATHER_ROWS_NUM = 5, WAVE_GATHER_ROWS_DEN = 4;  // whole-row pieces <= NUM / DEN x image-order pieces
+constexpr bool wave_gather_whole_rows(const WaveDims& w, int NP, int KFIX, int DFIX, int xs) {
+  if (!MGP_GATHER_ROWS || DFIX <= 0) return false;
+  const int spr = xs / w.E;
+  if (spr > 64) return false;
+  return WAVE_GATHER_ROWS_DEN * wave_gather_row_pieces(wave_gather_rows(w, NP, KFIX, xs), spr) <= WAVE_GATHER_ROWS_NUM * wave_gather_pieces(w, KFIX, xs);
+}
+// every slot of every gathered row written exactly once, nothing written at or behind the end of the rows
+constexpr bool wave_gather_cover_ok(int rows, int spr) {
+  if (spr < 1 || spr > 64 || rows < 1 || rows > 64) return false;
+  int hits[64 * 64] = {};
+  const int rpp = 64 / spr, np = wave_gather_row_pieces(rows, spr);
+  for (int p = 0; p < np; ++p)
+    for (int lane = 0; lane < 64; ++lane) {
+      const WaveGatherLane l = wave_gather_lane(lane, spr, spr - 1);
+      if (!wave_gather_on(l, p, spr, rows)) continue;
+      const int slot = p * rpp * spr + lane;  // 16-byte slot of the image the lane writes
+      if (slot >= rows * spr) return false;
+      if (slot != (p * rpp + l.rr) * spr + l.c) return false;  // ... and it is slot c of row RPP p + rr
+      ++hits[slot];
+    }
+  for (int s = 0; s < rows * spr; ++s)
+    if (hits[s] != 1) return false;
+  return true;
 }
 // (DLT) elements of the posted-column staging area behind the feature tile: two slots of 64 pairs and a bias of 32
 // pairs in front (a consumer addresses it relative to row pair j / 2 of the pivot column)
@@ -554,6 +635,12 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
   const int C16V = d / E;                                   //  -> SPR loads per task); C16V of them hold data
   constexpr int GB = 11;                                    // loads issued per batch (= SPR at d = 40, fp32)
   const unsigned spr_magic = (1u << 20) / (unsigned)SPR + 1u;  // sigma / SPR for sigma < 64 * 33
+  // (static feature counts) whole-row pieces where they do not multiply the loads: wave_gather_whole_rows
+  constexpr int SPRC = DFIX > 0 ? (DSTFIX + E) / E : 1;
+  constexpr bool WROW = PIPED && wave_gather_whole_rows(WD, NP, KFIX, DFIX, DSTFIX + E);
+  constexpr int GROWS = WROW ? wave_gather_rows(WD, NP, KFIX, DSTFIX + E) : 1;
+  static_assert(!WROW || wave_gather_cover_ok(GROWS, SPRC), "whole-row gather: every slot of every row once, nothing behind the rows");
+  static_assert(!WROW || GROWS <= wave_tile_rows(WD, NP, KFIX, DSTFIX + E), "whole-row gather: inside the tile");
   T pre_y = T(0), pre_eps = T(0);
   int64_t pre_idx = 0, pre_tg = 0;  // pre_tg: row of the response tensor (table row, or b * k + slot when gathered)
   auto pipe_issue = [&](int task_n, int64_t idx_n, int lane_) {
@@ -569,6 +656,44 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
       rowaddr[lane_] = (i == q ? feat_q : feat_nn) + idx_n * (int64_t)d;
     pre_idx = idx_n;
     __syncthreads();
+    if constexpr (WROW) {
+      if (MGP_PHASE(g, 1)) {
+        // whole-row pieces (wave_gather_lane above): the lane's row-of-piece and slot hold for every piece; per piece
+        // one read of the row pointer (immediate offset) and one 64-bit add.  Switched-off lanes read no pointer either.
+        constexpr int RPP = 64 / SPRC, NPR = wave_gather_row_pieces(GROWS, SPRC);
+        const WaveGatherLane gl = wave_gather_lane(lane_ & 63, SPRC, PACKED ? DFIX / E : DFIX / E - 1);
+        if (gl.active) {
+          typedef const T* rowptr_t;
+          typedef __attribute__((address_space(3))) const volatile rowptr_t lds_rowptr_t;
+          const lds_rowptr_t* ral = (const lds_rowptr_t*)(rowaddr + gl.rr);
+#if MGP_DMA_ASM
+          unsigned tile_lds = lds_byte_address(smem);  // the tile starts the dynamic LDS
+          asm volatile("" : "+s"(tile_lds));           // (opaque: one base register, scalar adds per piece)
+#endif
+          // (loads per batch: all of them up to 13 -- the headline shape -- else the fewest equal batches of at most 13:
+          // two registers of source address per load in flight)
+          constexpr int GBR = (NPR + (NPR + 12) / 13 - 1) / ((NPR + 12) / 13);
+#pragma unroll
+          for (int p0 = 0; p0 < NPR; p0 += GBR) {
+            const T* src[GBR];
+#pragma unroll
+            for (int u = 0; u < GBR; ++u)
+              if (p0 + u < NPR && wave_gather_on(gl, p0 + u, SPRC, GROWS))  // (volatile: one ds_read_b64 each -- merged in
+                src[u] = ral[RPP * (p0 + u)] + gl.c * E;  // pairs they are ds_read2_b64, twice the LDS cycles)
+#pragma unroll
+            for (int u = 0; u < GBR; ++u)
+              if (p0 + u < NPR && wave_gather_on(gl, p0 + u, SPRC, GROWS)) {
+                const int p = p0 + u;
+#if MGP_DMA_ASM
+                glds16_asm_at(src[u], tile_lds + p * RPP * SPRC * 16);
+#else
+                glds16_lds(src[u], smem, p * RPP * SPRC * 16);
+#endif
+              }
+          }
+        }
+      }
+    } else
     if (MGP_PHASE(g, 1)) {
       // 16-byte slot sigma = 64 n + lane of the tile: row = sigma / SPR, column = sigma % SPR
       // (unsigned 32-bit arithmetic throughout; padding slots re-read the last data slot, the
@@ -741,8 +866,15 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
     // (zeroed here, not under `d0 == 0` inside the feature loop: with a run-time feature count a conditional first
     // store makes the accumulators a value carried around the persistent loop -- NS registers (pairs) live, untouched,
     // through the whole elimination; found in the rhs-column kernel, round 4)
+    // (the pipelined Gram loop of the static folded kernels writes every accumulator with its first block -- no zeroing.
+    // A skipped loop would leave them unwritten, so the loop's own phase test goes with the zeroing; builds with the
+    // debug hooks, which can switch phases off, keep both)
+    constexpr bool GPF = GRAM && FOLD && sizeof(T) == 4 && DFIX > 0 && !(MGP_OWN_REG && DFIX > 0) && !DPRE && MGP_GRAM_PREFETCH > 0;  // pipelined Gram loop
+    constexpr bool ACC_FIRST = GPF && MGP_GRAM_FIRST_WRITE && !MGP_PHASE_HOOKS;
+    if constexpr (!ACC_FIRST) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) acc[s] = ACC(0);
+      for (int s = 0; s < NS; ++s) acc[s] = ACC(0);
+    }
 #if MGP_CHOL_PRIO && MGP_PRIO_LATE_DROP
     __builtin_amdgcn_s_setprio(0);  // the distance phase: long independent streams, lowest priority
 #endif
@@ -874,7 +1006,6 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
         };
         constexpr int NCF = DFIX > 0 ? DSTFIX / E : 1;  // 16-byte groups per row (static shapes)
         constexpr bool OWNREG = MGP_OWN_REG && DFIX > 0;
-        constexpr bool GPF = FOLD && sizeof(T) == 4 && DFIX > 0 && !OWNREG && !DPRE && MGP_GRAM_PREFETCH > 0;  // pipelined Gram loop
         V x[DFIX > 0 ? NCF : 1];
         if (MGP_PHASE(g, 2)) {
           const bool has = i < k || i == q;
@@ -958,7 +1089,7 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
         __syncthreads();
         MGP_WAVE_T(1)
         // ---- phase 2 (Gram form): acc = a'.b' per pair ------------------------------------------
-        if (MGP_PHASE(g, 2)) {
+        if (ACC_FIRST || MGP_PHASE(g, 2)) {
           if constexpr (GPF) {
             // (folded kernels) the blocks of the loop below as a software pipeline over the 16-byte groups: group gi
             // of the BA own rows against group gi of partners 1 .. BP, the stream of partner groups requested GPD
@@ -987,7 +1118,8 @@ void fused_wave_kernel(FusedArgs a, WaveGeom g) {
                 for (int j = 0; j < BA; ++j) own[(gi + 1) & 1][j] = *reinterpret_cast<const V*>(own_row(j) + (gi + 1) * E);
               }
               __builtin_amdgcn_sched_barrier(0);
-              gram_block<BA, BP>(&acc[s], own[gi & 1], par[t % (GPD + 1)]);
+              if (ACC_FIRST && gi == 0) gram_block_first<BA, BP>(&acc[s], own[0], par[t % (GPD + 1)]);
+              else gram_block<BA, BP>(&acc[s], own[gi & 1], par[t % (GPD + 1)]);
               __builtin_amdgcn_sched_barrier(0);
             }
           } else {

@@ -196,6 +196,63 @@ __device__ __forceinline__ void gram_block(f2* acc, const v16<float>::type (&w)[
     for (int j = 0; j < BA; ++j) acc[j * BP] = w[j].zw * o.zw + acc[j * BP];
   }
 }
+// The block that touches its accumulators FIRST: acc[j * BP] = w_j.xy * o.xy, then + w_j.zw * o.zw -- the accumulators
+// are outputs only, so nobody has to zero them.  fma(a, b, +0) and a * b differ in the sign of a zero product alone,
+// which |a'|^2 + |b'|^2 - 2 acc cannot see.
+template <int BA, int BP>
+__device__ __forceinline__ void gram_block_first(f2* acc, const v16<float>::type (&w)[BA], const v16<float>::type& o) {
+  if constexpr (BA == 3) {
+    asm volatile(
+        "v_pk_mul_f32 %0, %3, %9\n\t"
+        "v_pk_mul_f32 %1, %5, %9\n\t"
+        "v_pk_mul_f32 %2, %7, %9\n\t"
+        "v_pk_fma_f32 %0, %4, %10, %0\n\t"
+        "v_pk_fma_f32 %1, %6, %10, %1\n\t"
+        "v_pk_fma_f32 %2, %8, %10, %2"
+        : "=&v"(acc[0]), "=&v"(acc[BP]), "=&v"(acc[2 * BP])
+        : "v"(w[0].xy), "v"(w[0].zw), "v"(w[1].xy), "v"(w[1].zw), "v"(w[2].xy), "v"(w[2].zw), "v"(o.xy), "v"(o.zw));
+  } else if constexpr (BA == 4) {
+    asm volatile(
+        "v_pk_mul_f32 %0, %4, %12\n\t"
+        "v_pk_mul_f32 %1, %6, %12\n\t"
+        "v_pk_mul_f32 %2, %8, %12\n\t"
+        "v_pk_mul_f32 %3, %10, %12\n\t"
+        "v_pk_fma_f32 %0, %5, %13, %0\n\t"
+        "v_pk_fma_f32 %1, %7, %13, %1\n\t"
+        "v_pk_fma_f32 %2, %9, %13, %2\n\t"
+        "v_pk_fma_f32 %3, %11, %13, %3"
+        : "=&v"(acc[0]), "=&v"(acc[BP]), "=&v"(acc[2 * BP]), "=&v"(acc[3 * BP])
+        : "v"(w[0].xy), "v"(w[0].zw), "v"(w[1].xy), "v"(w[1].zw), "v"(w[2].xy), "v"(w[2].zw), "v"(w[3].xy), "v"(w[3].zw),
+          "v"(o.xy), "v"(o.zw));
+  } else if constexpr (BA == 5) {
+    asm volatile(
+        "v_pk_mul_f32 %0, %5, %15\n\t"
+        "v_pk_mul_f32 %1, %7, %15\n\t"
+        "v_pk_mul_f32 %2, %9, %15\n\t"
+        "v_pk_mul_f32 %3, %11, %15\n\t"
+        "v_pk_mul_f32 %4, %13, %15\n\t"
+        "v_pk_fma_f32 %0, %6, %16, %0\n\t"
+        "v_pk_fma_f32 %1, %8, %16, %1\n\t"
+        "v_pk_fma_f32 %2, %10, %16, %2\n\t"
+        "v_pk_fma_f32 %3, %12, %16, %3\n\t"
+        "v_pk_fma_f32 %4, %14, %16, %4"
+        : "=&v"(acc[0]), "=&v"(acc[BP]), "=&v"(acc[2 * BP]), "=&v"(acc[3 * BP]), "=&v"(acc[4 * BP])
+        : "v"(w[0].xy), "v"(w[0].zw), "v"(w[1].xy), "v"(w[1].zw), "v"(w[2].xy), "v"(w[2].zw), "v"(w[3].xy), "v"(w[3].zw),
+          "v"(w[4].xy), "v"(w[4].zw), "v"(o.xy), "v"(o.zw));
+  } else {
+#pragma unroll
+    for (int j = 0; j < BA; ++j) acc[j * BP] = w[j].xy * o.xy;
+#pragma unroll
+    for (int j = 0; j < BA; ++j) acc[j * BP] = w[j].zw * o.zw + acc[j * BP];
+  }
+}
+template <int BA, int BP>
+__device__ __forceinline__ void gram_block_first(double* acc, const v16<double>::type (&w)[BA], const v16<double>::type& o) {
+#pragma unroll
+  for (int j = 0; j < BA; ++j) acc[j * BP] = w[j].x * o.x;
+#pragma unroll
+  for (int j = 0; j < BA; ++j) acc[j * BP] = __builtin_fma(w[j].y, o.y, acc[j * BP]);
+}
 // fp64: the same block as plain FMAs (no packed fp64; two accumulators' worth of independent chains per row)
 template <int BA, int BP>
 __device__ __forceinline__ void gram_block(double* acc, const v16<double>::type (&w)[BA], const v16<double>::type& o) {
@@ -1057,6 +1114,17 @@ template <typename SharedArray>
 __device__ __forceinline__ void glds16_asm(const void* gsrc, SharedArray& shared, int byte_offset) {
   typedef __attribute__((address_space(3))) char lds_char;
   const unsigned lds = (unsigned)(size_t)(lds_char*)(&shared[0]) + (unsigned)byte_offset;
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds) : "memory");
+}
+// (the LDS byte address given as such: a caller that issues many pieces keeps ONE base in a scalar register and adds the
+// piece offsets with scalar instructions -- left to the compiler, the piece addresses are loop invariants that it
+// hoists into scalar registers, spills to VGPR lanes and fetches back with a v_readlane per piece)
+template <typename SharedArray>
+__device__ __forceinline__ unsigned lds_byte_address(SharedArray& shared) {
+  typedef __attribute__((address_space(3))) char lds_char;
+  return (unsigned)(size_t)(lds_char*)(&shared[0]);
+}
+__device__ __forceinline__ void glds16_asm_at(const void* gsrc, unsigned lds) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds) : "memory");
 }
 __device__ __forceinline__ void lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
