@@ -157,7 +157,9 @@ int mgp_posterior_gathered_f64(const double* feat_q, const double* feat_nn, int 
 int mgp_posterior_kernel_name(int elem_size, int d, int k, int R, int packed, int path, char* buf, int len);
 
 /* Name of the kernel instantiation the calling thread's most recent mgp_posterior_* / mgp_loocv_* call actually
- * launched ("" before the first).  Unlike mgp_posterior_kernel_name this reflects everything the dispatch looked at:
+ * launched ("" before the first), the backward entries included: mgp_posterior_backward_* / mgp_loocv_backward_* note
+ * the forward kernel's backward instantiation, "mgp::backward_wave_kernel<T,NP,DG,KFIX,HYPER>" or
+ * "mgp::backward_kernel<T> [threads=N,dc=M]", whichever served.  Unlike mgp_posterior_kernel_name this reflects everything the dispatch looked at:
  * batch thresholds and disk cache of the run-time compiler, table alignment, Gram-form eligibility of the
  * covariance function.  Tests use it to prove that the kernel a benchmark line times is one the oracle has checked. */
 int mgp_last_kernel_name(char* buf, int len);
@@ -382,7 +384,8 @@ int mgp_last_loocv_geometry(int* grid, int* nh);
 int mgp_loocv_tree_mode_get(void);
 int mgp_loocv_tree_mode_set(int mode);
 /* launch geometry of the calling thread's most recent fused launch of an LDS-resident family (wave, rhs, matrix-core
- * layout, wide, generic, shear; the large kernels note none): workgroups (the
+ * layout, wide, generic, shear, and the three backward families up to mgp_max_nn_count_backward: the forward kernel's
+ * backward instantiations, backward_wave_kernel, backward_kernel; the large kernels note none): workgroups (the
  * persistent grid) and dynamic LDS bytes per workgroup -- what profiles/ quote next to the compiler's register
  * record (lib/kernel_resources.json); diagnostic */
 int mgp_last_launch_geometry(int64_t* workgroups, int* lds_bytes);

@@ -290,7 +290,9 @@ int launch_backward(const BackwardArgs& in, hipStream_t stream) {
   if (!fc.fits) return MGP_EUNSUPPORTED;
   g.f.dc = fc.dc;
   const int threads = g.f.k + 2 <= 64 ? 64 : (g.f.k + 2 <= 128 ? 128 : 256);
-  return launch_capacity(&backward_kernel<T>, threads, fc.lds, g.f.b, Capacity{16}, stream, nullptr, g, g_bwd_stage).status;
+  const LaunchLabel label(g.f.b, g.f.k, g.f.d, g.f.R, "mgp::backward_kernel<%s> [threads=%d,dc=%d]", sizeof(T) == 4 ? "float" : "double",
+                          threads, fc.dc);
+  return launch_capacity(&backward_kernel<T>, threads, fc.lds, g.f.b, Capacity{16}, stream, &label, g, g_bwd_stage).status;
 }
 
 template int launch_backward<float>(const BackwardArgs&, hipStream_t);

@@ -488,7 +488,9 @@ static int launch_bwd_np_impl(const BackwardArgs& g, hipStream_t stream) {
   const int vec_ok = (g.f.d % E == 0) && (align % 16 == 0);
   const size_t lds = ((size_t)NH * NP * xs + (size_t)NH * NP * KS + 4 * 64) * sizeof(T) + 64 * sizeof(int64_t);
   static Residency res;
-  return launch_resident(&backward_wave_kernel<T, NP, DG, KFIX, HYPER>, res, 64, lds, (g.f.b + NH - 1) / NH, nullptr, stream, nullptr, g,
+  const LaunchLabel label(g.f.b, g.f.k, g.f.d, g.f.R, "mgp::backward_wave_kernel<%s,%d,%d,%d,%s>", sizeof(T) == 4 ? "float" : "double", NP, DG,
+                          KFIX, HYPER ? "true" : "false");
+  return launch_resident(&backward_wave_kernel<T, NP, DG, KFIX, HYPER>, res, 64, lds, (g.f.b + NH - 1) / NH, nullptr, stream, &label, g,
                          vec_ok).status;
 }
 // (no feature cotangent asked for: the instantiation without the sweep)
