@@ -384,8 +384,9 @@ int mgp_last_loocv_geometry(int* grid, int* nh);
 int mgp_loocv_tree_mode_get(void);
 int mgp_loocv_tree_mode_set(int mode);
 /* launch geometry of the calling thread's most recent fused launch of an LDS-resident family (wave, rhs, matrix-core
- * layout, wide, generic, shear, and the three backward families up to mgp_max_nn_count_backward: the forward kernel's
- * backward instantiations, backward_wave_kernel, backward_kernel; the large kernels note none): workgroups (the
+ * layout, wide, generic, shear, the three backward families up to mgp_max_nn_count_backward: the forward kernel's
+ * backward instantiations, backward_wave_kernel, backward_kernel, and the general-smoothness backward_gen_kernel up to
+ * mgp_max_nn_count_backward_gen; the large kernels note none): workgroups (the
  * persistent grid) and dynamic LDS bytes per workgroup -- what profiles/ quote next to the compiler's register
  * record (lib/kernel_resources.json); diagnostic */
 int mgp_last_launch_geometry(int64_t* workgroups, int* lds_bytes);
@@ -691,6 +692,45 @@ int mgp_loocv_backward_f64(const double* features, int d, const int64_t* batch_i
                            double* grad_ls, double* grad_noise, int* info, void* stream);
 /* Largest nn_count the backward kernel accepts (two LDS-resident k x k triangles). */
 int mgp_max_nn_count_backward(int elem_size);
+/* The same vector-Jacobian product for the general-smoothness Matern (K3 _matern_gen_fn, _src/gp/kernels/numpy.py:34-43;
+ * `smoothness` = nu in place of a kernel id): what the reference obtains from torch autograd over
+ * torch/muygps_layer.py:129-164 with _matern_gen_fn as the kernel function.  One workgroup per neighbourhood with the
+ * system in LDS (csrc/mgp_backward_gen.hip), every cotangent of mgp_posterior_backward_* and one more: grad_nu (b), the
+ * per-neighbourhood partial with respect to nu.  Two feature tables, any R >= 1, any d >= 1, both metrics, scalar or
+ * per-feature length scale, the three noise modes, 0 < nu <= 30, k up to mgp_max_nn_count_backward_gen(elem_size) (both
+ * node tables sit in LDS behind the closed-form kernel's carve; MGP_EINVAL for an elem_size that is not 4 or 8).
+ *   grad_ykinvy given (R must be 1): the LOOCV form of mgp_loocv_backward_*, grad_mean is then (b); grad_mean / grad_var
+ *       may be NULL (= 0).  grad_ykinvy NULL: the posterior form with grad_mean (b, R) and / or grad_var (b).
+ *   grad_feat_q, grad_feat_nn, grad_targets: ACCUMULATED into with atomic adds, as mgp_posterior_backward_*.
+ *   grad_ls (b, ls_count), grad_noise (b, k), grad_nu (b): written; every sum inside a neighbourhood runs in a fixed
+ *       order (no floating-point atomic), so a neighbourhood's three partials are the same bits whatever its place in
+ *       the batch, the batch and the grid.  With grad_nu NULL the kernel evaluates one exponential per quadrature node
+ *       and pair, with it three.
+ *   Any of the six outputs may be NULL, not all.  A pair at zero distance contributes nothing to any feature,
+ *   length-scale or smoothness cotangent, also below nu = 1/2 where dk/dr diverges.  A non-SPD neighbourhood counts in
+ *   *info and leaves every output of that neighbourhood untouched.
+ *   Order of the checks, all before any HIP call: sizes b < 0, k < 1, d < 1, R < 1 and a smoothness that is not > 0
+ *   (NaN included) (MGP_EINVAL); the empty batch (MGP_OK, nothing else looked at); required pointers, grad_ykinvy with
+ *   R != 1, all three cotangents NULL, all six outputs NULL, ids, a noise mode without noise_dev, ls_count not in {1, d}
+ *   (MGP_EINVAL); then smoothness > 30 or k > mgp_max_nn_count_backward_gen: MGP_EUNSUPPORTED.  The closed-form entries
+ *   go on refusing MGP_KERNEL_MATERN_GEN. */
+int mgp_max_nn_count_backward_gen(int elem_size);
+int mgp_posterior_backward_gen_f32(const float* feat_q, const float* feat_nn, int d,
+                                   const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                   const float* targets, int R,
+                                   int noise_mode, double noise_scalar, const float* noise_dev,
+                                   double smoothness, int metric_id, const float* length_scale, int ls_count,
+                                   const float* grad_mean, const float* grad_var, const float* grad_ykinvy,
+                                   float* grad_feat_q, float* grad_feat_nn, float* grad_targets,
+                                   float* grad_ls, float* grad_noise, float* grad_nu, int* info, void* stream);
+int mgp_posterior_backward_gen_f64(const double* feat_q, const double* feat_nn, int d,
+                                   const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                   const double* targets, int R,
+                                   int noise_mode, double noise_scalar, const double* noise_dev,
+                                   double smoothness, int metric_id, const double* length_scale, int ls_count,
+                                   const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
+                                   double* grad_feat_q, double* grad_feat_nn, double* grad_targets,
+                                   double* grad_ls, double* grad_noise, double* grad_nu, int* info, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Materialising per-function kernels (API parity with the backend modules).

@@ -65,6 +65,9 @@ PER_FILE_FLAGS = {
     "mgp_backward_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and its general-smoothness form, a file of its own: tests/test_hyper_backward_gen_status_cpu.py reads it)
     "mgp_backward_gen_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the general-smoothness backward in LDS: the single-wave factorisation unrolls like mgp_backward.hip's;
+    # tests/test_backward_gen_status_cpu.py reads the record)
+    "mgp_backward_gen.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
     # (... and the whole vector-Jacobian product there: tests/test_large_full_backward_status_cpu.py reads the record)
     "mgp_backward_large_full.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }

@@ -140,10 +140,11 @@ __device__ __forceinline__ void backward_large_solve_tails(SlabRows<T> row, int 
 }
 
 // ---- 5. Anisotropy, one feature chunk whose rows are staged in X: grad_ls[c] = -2 / l_c^3 sum_pairs q_ij (x_ic - x_jc)^2
-// with q in the triangle Dst, eight features per pass.  gls_row / ls: at the chunk's first feature ----
-template <typename T>
-__device__ __forceinline__ void backward_large_ls_chunk(const T* Dst, const T* X, int XP, T* red, const T* ls, T* gls_row,
-                                                        int w, int wp, int npairs, int tid, int NT) {
+// with q_ij = qof(p, i, j) wherever the kernel keeps it, eight features per pass.  gls_row / ls: at the chunk's first
+// feature ----
+template <typename T, typename QOf>
+__device__ __forceinline__ void pair_ls_chunk(QOf qof, const T* X, int XP, T* red, const T* ls, T* gls_row, int w, int wp,
+                                              int npairs, int tid, int NT) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
   for (int c0 = 0; c0 < wp; c0 += kBwdGroup) {
@@ -153,7 +154,7 @@ __device__ __forceinline__ void backward_large_ls_chunk(const T* Dst, const T* X
     for (int p = tid; p < npairs; p += NT) {
       int a_, c_;
       tri_decode(p, a_, c_);
-      const T q = Dst[p];
+      const T q = qof(p, a_, c_);
       const T* xa = X + a_ * XP + c0;
       const T* xc = X + c_ * XP + c0;
 #pragma unroll
@@ -179,6 +180,12 @@ __device__ __forceinline__ void backward_large_ls_chunk(const T* Dst, const T* X
     }
     __syncthreads();
   }
+}
+// ... with q in the triangle Dst of a backward slab
+template <typename T>
+__device__ __forceinline__ void backward_large_ls_chunk(const T* Dst, const T* X, int XP, T* red, const T* ls, T* gls_row,
+                                                        int w, int wp, int npairs, int tid, int NT) {
+  pair_ls_chunk<T>([&](int p, int, int) { return Dst[p]; }, X, XP, red, ls, gls_row, w, wp, npairs, tid, NT);
 }
 
 }  // namespace mgp

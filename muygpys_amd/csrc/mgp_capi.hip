@@ -202,6 +202,27 @@ int posterior_backward(const T* fq, const T* fn, int d, const int64_t* bi, const
   return launch_backward<T>(g, static_cast<hipStream_t>(stream));
 }
 
+// the whole vector-Jacobian product of the general-smoothness Matern in LDS (mgp_backward_gen.hip): the checks of
+// hyper_backward_gen_large in its order, without a workspace; gyk selects the LOOCV form, grad_nu is a sixth output
+template <typename T>
+int posterior_backward_gen(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                           const T* tg, int R, int noise_mode, double eps, const T* nd, double smoothness, int metric_id,
+                           const T* ls, int ls_count, const T* gmean, const T* gvar, const T* gyk, T* gfq, T* gfn, T* gtg,
+                           T* gls, T* gnz, T* gnu, int* info, void* stream) {
+  if (!(smoothness > 0.0)) return MGP_EINVAL;
+  BackwardArgs g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES | KERNEL_IS_GEN, fq, fn, d, bi, ni, b, k, tg, R, noise_mode, eps, nd,
+                                  MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (gyk && R != 1) return MGP_EINVAL;  // (the LOOCV losses are defined for one response)
+  if ((!gmean && !gvar && !gyk) || (!gfq && !gfn && !gtg && !gls && !gnz && !gnu)) return MGP_EINVAL;
+  if (smoothness > 30.0) return MGP_EUNSUPPORTED;
+  g.f.smoothness = smoothness;
+  g.grad_mean = gmean, g.grad_var = gvar, g.grad_yk = gyk;
+  g.grad_feat_q = gfq, g.grad_feat_nn = gfn, g.grad_targets = gtg, g.grad_ls = gls, g.grad_noise = gnz;
+  return launch_backward_gen<T>(g, gnu, static_cast<hipStream_t>(stream));  // (refuses k beyond max_nn_count_backward_gen)
+}
+
 template <typename T>
 int solve(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, double kout, T* mean, T* var, T* yk,
           T* coeffs, int* info, void* stream) {
@@ -760,6 +781,21 @@ MGP_DEFINE_COEF_ANY(f64, double)
 MGP_DEFINE_BWD(f32, float)
 MGP_DEFINE_BWD(f64, double)
 int mgp_max_nn_count_backward(int elem_size) { return max_nn_count_backward(elem_size); }
+int mgp_max_nn_count_backward_gen(int elem_size) {
+  if (elem_size != 4 && elem_size != 8) return MGP_EINVAL;
+  return max_nn_count_backward_gen(elem_size);
+}
+#define MGP_DEFINE_BWD_GEN(SUF, T)                                                                                  \
+  int mgp_posterior_backward_gen_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,        \
+                                       int64_t b, int k, const T* tg, int R, int nm, double eps, const T* nd,        \
+                                       double smoothness, int mid, const T* ls, int lsc, const T* gmean,             \
+                                       const T* gvar, const T* gyk, T* gfq, T* gfn, T* gtg, T* gls, T* gnz, T* gnu,  \
+                                       int* info, void* st) {                                                        \
+    return posterior_backward_gen<T>(fq, fn, d, bi, ni, b, k, tg, R, nm, eps, nd, smoothness, mid, ls, lsc, gmean,   \
+                                     gvar, gyk, gfq, gfn, gtg, gls, gnz, gnu, info, st);                             \
+  }
+MGP_DEFINE_BWD_GEN(f32, float)
+MGP_DEFINE_BWD_GEN(f64, double)
 
 int64_t mgp_backward_large_workspace_bytes(int elem_size, int k, int64_t b) {
   if ((elem_size != 4 && elem_size != 8) || k < 1 || b < 0 || (int64_t)k + 2 > kLargeMaxRows) return 0;

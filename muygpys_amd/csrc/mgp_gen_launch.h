@@ -141,5 +141,9 @@ int max_nn_count_gen(int elem_size, int R);
 // ... and of the hyper-parameter backward on the slab factor (mgp_backward_gen_large.hip): grad_nu (b) may be NULL
 template <typename T> int launch_hyper_backward_gen_large(const BackwardArgs&, void* grad_nu, void* workspace, int64_t workspace_bytes, hipStream_t);
 int backward_gen_large_max_nn_count(int elem_size);
+// ... and of the whole vector-Jacobian product in LDS (mgp_backward_gen.hip): two tables, every cotangent of
+// BackwardArgs, grad_nu (b) may be NULL; MGP_EUNSUPPORTED beyond max_nn_count_backward_gen
+template <typename T> int launch_backward_gen(const BackwardArgs&, void* grad_nu, hipStream_t);
+int max_nn_count_backward_gen(int elem_size);
 
 }  // namespace mgp

@@ -9,6 +9,7 @@ and what ``bench.py`` times.
 
 from __future__ import annotations
 
+import contextlib
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
@@ -689,9 +690,10 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     to the backward on the slab factor (``mgp_hyper_backward_large_*``, csrc/mgp_backward_large.hip), up to
     ``mgp_large_max_nn_count(elem_size, 1)`` = 1022 whatever the response count; ``ValueError`` beyond.
 
-    The general-smoothness Matern has one rung at every ``nn_count``: its own backward on the slab factor
+    The general-smoothness Matern has its own backward on the slab factor at every ``nn_count``
     (``mgp_hyper_backward_gen_large_*``, csrc/mgp_backward_gen_large.hip) with ``spec.smoothness``, up to
-    ``mgp_backward_gen_large_max_nn_count``; ``ValueError`` beyond.  ``want_nu`` (that kernel alone): a third result,
+    ``mgp_backward_gen_large_max_nn_count``; ``ValueError`` beyond -- and, on request (:func:`gen_backward`), the LDS
+    workgroup backward ``mgp_posterior_backward_gen_*`` in front of it where that one is faster.  ``want_nu`` (that kernel alone): a third result,
     the per-neighbourhood partials ``g_nu (b,)`` with respect to the smoothness."""
     P = _lib.ptr
     fn, ls = inp.fn, inp.ls
@@ -723,8 +725,51 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     return g_l, g_n
 
 
+# which rung serves the hyper-parameter partials of the general-smoothness Matern first: "slab" (the backward on the slab
+# factor alone, csrc/mgp_backward_gen_large.hip) or "lds" (the LDS workgroup backward, csrc/mgp_backward_gen.hip, with
+# the slab behind it for an nn_count beyond mgp_max_nn_count_backward_gen).  MUYGPYS_HIP_GEN_BACKWARD, unset = slab.
+GEN_BACKWARD_MODES = ("slab", "lds")
+# ... and the largest nn_count at which the "lds" rung is tried, by element size: where it was measured to beat the slab
+# backward (profiles/gen_backward_lds_bench.json, d = 40, 200 000 neighbourhoods, nu = 1.3: fp32 4.0x at nn_count 30 and
+# 2.1x at 63, 0.77x at 100; fp64 2.5x at 30, 0.72x at 63 -- one 128-thread workgroup per CU there).  Nothing was
+# measured between those shapes: the rung ends at the last one it won.
+GEN_BACKWARD_LDS_MAX_NN_COUNT = {4: 63, 8: 30}
+
+
+def _gen_backward_from_env() -> str:
+    mode = os.environ.get("MUYGPYS_HIP_GEN_BACKWARD", "") or "slab"
+    if mode not in GEN_BACKWARD_MODES:
+        raise ValueError(f"MUYGPYS_HIP_GEN_BACKWARD={mode!r} is none of {GEN_BACKWARD_MODES}")
+    return mode
+
+
+_GEN_BACKWARD = _gen_backward_from_env()
+
+
+@contextlib.contextmanager
+def gen_backward(mode: str):
+    """``with fused.gen_backward("lds"):`` -- the first rung of the general-smoothness Matern's analytic gradients inside
+    the block (:func:`loocv_value_and_grad`, :func:`class_value_and_grad` and the optimisers on top of them); the
+    previous mode is restored on the way out."""
+    global _GEN_BACKWARD
+    if mode not in GEN_BACKWARD_MODES:
+        raise ValueError(f"gen_backward mode {mode!r} is none of {GEN_BACKWARD_MODES}")
+    previous, _GEN_BACKWARD = _GEN_BACKWARD, mode
+    try:
+        yield
+    finally:
+        _GEN_BACKWARD = previous
+
+
+def gen_backward_default() -> str:
+    """The mode in force right now (the environment's choice, or an enclosing block's)."""
+    return _GEN_BACKWARD
+
+
 def _hyper_partials_gen(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_noise: bool, want_nu: bool):
-    """:func:`_hyper_partials` of the general-smoothness Matern: ``(g_l, g_n or None[, g_nu])``."""
+    """:func:`_hyper_partials` of the general-smoothness Matern: ``(g_l, g_n or None[, g_nu])``.  The ladder is the
+    slab backward alone, or -- :func:`gen_backward` ``"lds"``, up to ``GEN_BACKWARD_LDS_MAX_NN_COUNT`` --
+    ``mgp_posterior_backward_gen_*`` with the slab behind it."""
     P = _lib.ptr
     fn, ls = inp.fn, inp.ls
     nu = spec.smoothness
@@ -738,16 +783,24 @@ def _hyper_partials_gen(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_
     g_n = torch.zeros((inp.b, inp.k), device=fn.device, dtype=fn.dtype) if want_noise else None
     g_nu = torch.zeros((inp.b,), device=fn.device, dtype=fn.dtype) if want_nu else None
     gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
+    shape = (inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R)
+    model = (_lib.NOISE_SCALAR, float(spec.noise), None, float(nu), spec.metric_id(), P(ls), ls.numel())
+    cotangents = (P(gm), P(gv), P(gyk))
+
+    def lds():  # (the training table on both sides, no feature or response cotangents)
+        return _lib.fn("posterior_backward_gen", fn.dtype)(
+            P(fn), P(fn), *shape, *model, *cotangents, None, None, None, P(g_l), P(g_n), P(g_nu), P(info), _lib.stream_ptr())
 
     def slab():
         ws = _lib.backward_large_workspace(fn.dtype, inp.k, inp.b, fn.device)
         return _lib.fn("hyper_backward_gen_large", fn.dtype)(
-            P(fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, _lib.NOISE_SCALAR, float(spec.noise), None,
-            float(nu), spec.metric_id(), P(ls), ls.numel(), P(gm), P(gv), P(gyk), P(g_l), P(g_n), P(g_nu), P(info),
-            P(ws), ws.numel(), _lib.stream_ptr())
+            P(fn), *shape, *model, *cotangents, P(g_l), P(g_n), P(g_nu), P(info), P(ws), ws.numel(), _lib.stream_ptr())
 
-    rc, _ = _lib.run_ladder((slab,))
-    _lib.check(rc, "mgp_hyper_backward_gen_large")
+    use_lds = _GEN_BACKWARD == "lds" and inp.k <= GEN_BACKWARD_LDS_MAX_NN_COUNT[fn.element_size()]
+    rungs = ((lds, "mgp_posterior_backward_gen"),) if use_lds else ()
+    rungs += ((slab, "mgp_hyper_backward_gen_large"),)
+    rc, at = _lib.run_ladder([r for r, _ in rungs])
+    _lib.check(rc, rungs[at][1])
     return (g_l, g_n, g_nu) if want_nu else (g_l, g_n)
 
 
