@@ -459,7 +459,8 @@ int mgp_fast_coefficients_f64(const double* feat, int d, const int64_t* nn_idx, 
  * closed-form kernels, both metrics, scalar or per-feature length scale, the three noise modes.
  * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), the empty batch (MGP_OK, nothing else looked at),
  * pointers, ids, a noise mode without noise_dev, ls_count not in {1, d} and a needed workspace that is NULL, misaligned
- * or under one slab (MGP_EINVAL), then k + 1 + R > 1024 or MGP_KERNEL_MATERN_GEN: MGP_EUNSUPPORTED. */
+ * or under one slab (MGP_EINVAL), then k + 1 + R > 1024 or MGP_KERNEL_MATERN_GEN: MGP_EUNSUPPORTED (the general
+ * smoothness has entries of its own: mgp_fast_coefficients_gen_* below). */
 int64_t mgp_fast_coefficients_workspace_bytes(int elem_size, int k, int response_count, int64_t b);
 int mgp_fast_coefficients_any_f32(const float* feat, int d, const int64_t* nn_idx, int64_t b, int k,
                                   const float* targets, int R, int noise_mode, double noise_scalar,
@@ -469,6 +470,32 @@ int mgp_fast_coefficients_any_f32(const float* feat, int d, const int64_t* nn_id
 int mgp_fast_coefficients_any_f64(const double* feat, int d, const int64_t* nn_idx, int64_t b, int k,
                                   const double* targets, int R, int noise_mode, double noise_scalar,
                                   const double* noise_dev, int kernel_id, int metric_id, const double* length_scale,
+                                  int ls_count, double* coeffs, int* info, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
+/* The same precompute for the general-smoothness Matern (k(r) = 2^(1-nu)/Gamma(nu) x^nu K_nu(x), x = sqrt(2 nu) r,
+ * _src/gp/kernels/numpy.py:34-43; 0 < smoothness <= 30), evaluated inside the launch from a node table in LDS as in
+ * mgp_posterior_gen_*: the arguments of mgp_fast_coefficients_any_* with `smoothness` in place of kernel_id.
+ *   k <= mgp_max_nn_count_gen(elem_size, R): the general-smoothness coefficient instantiation of the LDS workgroup
+ *       kernel (the limit is the one of mgp_posterior_gen_generic_*: the system, an 8-feature chunk and the node
+ *       table); no workspace (mgp_fast_coefficients_gen_workspace_bytes returns 0, `workspace` is not looked at).  Up to
+ *       64 slots this is the 64-thread workgroup: no wave kernel computes general-smoothness coefficients.
+ *   beyond, up to k + 1 + R <= 1024: the same instantiation of the slab kernel, under the workspace contract above
+ *       (one slab = mgp_fast_coefficients_gen_workspace_bytes(elem_size, k, R, 1); any workspace of at least one slab
+ *       gives the same bits).
+ * What a neighbourhood returns does not depend on its place in the batch, the grid or the workspace.
+ * Order of the checks, all before any HIP call: smoothness <= 0 or NaN and the sizes (MGP_EINVAL), the empty batch
+ * (MGP_OK), pointers, ids, a noise mode without noise_dev, ls_count not in {1, d} and a needed workspace that is NULL,
+ * misaligned or under one slab (MGP_EINVAL), then k + 1 + R > 1024 or smoothness > 30: MGP_EUNSUPPORTED. */
+int64_t mgp_fast_coefficients_gen_workspace_bytes(int elem_size, int k, int response_count, int64_t b);
+int mgp_fast_coefficients_gen_f32(const float* feat, int d, const int64_t* nn_idx, int64_t b, int k,
+                                  const float* targets, int R, int noise_mode, double noise_scalar,
+                                  const float* noise_dev, double smoothness, int metric_id, const float* length_scale,
+                                  int ls_count, float* coeffs, int* info, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+int mgp_fast_coefficients_gen_f64(const double* feat, int d, const int64_t* nn_idx, int64_t b, int k,
+                                  const double* targets, int R, int noise_mode, double noise_scalar,
+                                  const double* noise_dev, double smoothness, int metric_id, const double* length_scale,
                                   int ls_count, double* coeffs, int* info, void* workspace, int64_t workspace_bytes,
                                   void* stream);
 
@@ -967,7 +994,8 @@ int mgp_posterior_backward_large_f64(const double* feat_q, const double* feat_nn
  * (_muygps_fast_posterior_mean_precompute, numpy.py:88-95); coeff_row (b) = the closest
  * training point of each test point; nn_idx (b, k) = that point's neighbourhood.
  * Every k >= 1: up to k + 1 <= 64 one test point per 32 or 64 lanes, beyond that one test point per wave in passes of
- * 64 neighbours; no workspace.  MGP_KERNEL_MATERN_GEN is not a kernel id of this entry (MGP_EINVAL).
+ * 64 neighbours; no workspace.  MGP_KERNEL_MATERN_GEN is not a kernel id of this entry (MGP_EINVAL): the general
+ * smoothness is served by mgp_fast_posterior_mean_gen_* below.
  * ------------------------------------------------------------------------- */
 int mgp_fast_posterior_mean_f32(const float* feat_q, const float* feat_nn, int d, const int64_t* batch_idx,
                                 const int64_t* nn_idx, int64_t b, int k, const float* coeffs,
@@ -977,6 +1005,23 @@ int mgp_fast_posterior_mean_f64(const double* feat_q, const double* feat_nn, int
                                 const int64_t* nn_idx, int64_t b, int k, const double* coeffs,
                                 const int64_t* coeff_row, int R, int kernel_id, int metric_id,
                                 const double* length_scale, int ls_count, double* mean, void* stream);
+
+/* The same prediction for the general-smoothness Matern (0 < smoothness <= 30; coefficients from
+ * mgp_fast_coefficients_gen_*): the arguments above with `smoothness` in place of kernel_id, general-smoothness
+ * instantiations of both kernels with the node table of the launch's smoothness in LDS.  A zero distance (a test
+ * point equal to a neighbour) gives covariance 1, a NaN distance stays NaN.  With two test points per wave (k + 1 <=
+ * 32) each sums to the node count of its own 32 lanes: what a test point returns does not depend on the batch
+ * around it.  smoothness <= 0 or NaN: MGP_EINVAL, with the sizes and in front of the empty-batch return; then
+ * pointers, ids and ls_count (MGP_EINVAL); then smoothness > 30 or k > 1023 (no coefficient entry writes a wider list):
+ * MGP_EUNSUPPORTED. */
+int mgp_fast_posterior_mean_gen_f32(const float* feat_q, const float* feat_nn, int d, const int64_t* batch_idx,
+                                    const int64_t* nn_idx, int64_t b, int k, const float* coeffs,
+                                    const int64_t* coeff_row, int R, double smoothness, int metric_id,
+                                    const float* length_scale, int ls_count, float* mean, void* stream);
+int mgp_fast_posterior_mean_gen_f64(const double* feat_q, const double* feat_nn, int d, const int64_t* batch_idx,
+                                    const int64_t* nn_idx, int64_t b, int k, const double* coeffs,
+                                    const int64_t* coeff_row, int R, double smoothness, int metric_id,
+                                    const double* length_scale, int ls_count, double* mean, void* stream);
 
 /* L1/L2 loss sums in fp64, _src/optimize/loss/numpy.py:22-117.  For n residuals
  * r = pred - target and variances v (may be NULL), with s = *scale_dev (device

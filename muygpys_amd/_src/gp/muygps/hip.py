@@ -158,13 +158,14 @@ def _precompute_fused(Kin, train_nn_targets_fast):
     through the fused coefficient launch (``muygpys_amd.fused._fused_coefficients``: nothing of size (b, k, k) is
     formed).  None when the handles are not such a pair (the recognisers of ``lazy.fused_triple``, without a
     crosswise side) or the library refuses the model: the caller then forces the handles and solves."""
-    from muygpys_amd.fused import _fused_coefficients, _normalize
+    from muygpys_amd.fused import _fused_coefficients, _normalize, gen_fast_default
     from muygpys_amd.lazy_eval import _spec
 
     if not (isinstance(Kin, lazy.LazyCov) and isinstance(train_nn_targets_fast, lazy.LazyTargets)):
         return None
     a, t = Kin.diffs, train_nn_targets_fast
-    if Kin.kernel == "matern_gen":  # (no fused coefficient kernel evaluates the general nu: force and solve)
+    # (the general nu: force and solve, unless fused.gen_fast("fused") asks for mgp_fast_coefficients_gen_*)
+    if Kin.kernel == "matern_gen" and gen_fast_default() != "fused":
         return None
     if not (a.kind == "pairwise" and a.reduced and a.metric in ("l2", "F2") and not t.swapped
             and lazy._same_tensor(a.nn_indices, t.nn_indices) and t.targets.ndim in (1, 2)

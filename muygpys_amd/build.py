@@ -70,6 +70,9 @@ PER_FILE_FLAGS = {
     "mgp_backward_gen.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
     # (... and the whole vector-Jacobian product there: tests/test_large_full_backward_status_cpu.py reads the record)
     "mgp_backward_large_full.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the prediction kernels of the fast posterior mean, closed-form and general-smoothness:
+    # tests/test_fast_gen_cpu.py compares the closed-form records with the ones from before the general ones existed)
+    "mgp_fast_mean.hip": ["-Rpass-analysis=kernel-resource-usage"],
 }
 
 

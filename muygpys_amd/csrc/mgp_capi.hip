@@ -283,6 +283,51 @@ int fast_coefficients_any(const T* fn, int d, const int64_t* ni, int64_t b, int 
   return large ? launch_fused_large<T>(a, ws, ws_bytes, s) : launch_fused_generic<T>(a, s);
 }
 
+// ... of the general-smoothness Matern (mgp_fast_coefficients_gen_*): the GEN x COEFFS instantiations of the same two
+// families, the LDS limit with the node table in place (mgp_max_nn_count_gen); the checks of fast_coefficients_any in
+// its order, the smoothness sign with the sizes (in front of the empty-batch return), its limit with the shapes beyond
+// the kernels
+static bool coefficients_gen_need_workspace(int elem_size, int k, int R) {
+  return (int64_t)k + 1 + R > kLargeMaxRows || k > max_nn_count_gen(elem_size, R);
+}
+
+template <typename T>
+int fast_coefficients_gen(const T* fn, int d, const int64_t* ni, int64_t b, int k, const T* tg, int R, int noise_mode,
+                          double eps, const T* nd, double smoothness, int metric_id, const T* ls, int ls_count, T* coeffs,
+                          int* info, void* ws, int64_t ws_bytes, void* stream) {
+  if (!(smoothness > 0.0)) return MGP_EINVAL;
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | KERNEL_IS_GEN, fn, fn, d, nullptr, ni, b, k, tg, R, noise_mode, eps, nd,
+                                  MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (!coeffs) return MGP_EINVAL;
+  const bool large = coefficients_gen_need_workspace(sizeof(T), k, R);
+  if (large && !valid_workspace(ws, ws_bytes, sizeof(T), k, R)) return MGP_EINVAL;
+  if ((int64_t)k + 1 + R > kLargeMaxRows || smoothness > 30.0) return MGP_EUNSUPPORTED;
+  a.coeffs = coeffs;
+  a.smoothness = smoothness;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return large ? launch_fused_large_gen<T>(a, ws, ws_bytes, s) : launch_fused_generic_gen<T>(a, s);
+}
+
+// ... and the prediction from such coefficients (mgp_fast_posterior_mean_gen_*): the checks of fast_posterior_mean, the
+// smoothness as above; a list of more than 1023 neighbours is refused (no coefficient entry writes one: k + 1 + R <=
+// 1024, and up to there the covariances of a test point and the fp64 node table fit the default 64 KiB of dynamic LDS)
+template <typename T>
+int fast_posterior_mean_gen(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                            const T* coeffs, const int64_t* crow, int R, double smoothness, int metric_id, const T* ls,
+                            int ls_count, T* mean, void* stream) {
+  if (!(smoothness > 0.0)) return MGP_EINVAL;
+  FusedArgs a;
+  const int ready = fused_args<T>(a, KERNEL_IS_GEN, fq, fn, d, bi, ni, b, k, nullptr, R, MGP_NOISE_SCALAR, 0.0, nullptr,
+                                  MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, mean, nullptr, nullptr, nullptr);
+  if (ready != ARGS_READY) return ready;
+  if (!coeffs || !crow || !mean) return MGP_EINVAL;
+  if ((int64_t)k + 1 > kLargeMaxRows || smoothness > 30.0) return MGP_EUNSUPPORTED;
+  return launch_fast_mean_gen<T>(fq, fn, d, bi, ni, b, k, coeffs, crow, R, smoothness, metric_id, ls, ls_count, mean,
+                                 static_cast<hipStream_t>(stream));
+}
+
 template <typename T>
 int solve_large(const T* Kin, const T* Kc, const T* Y, int64_t b, int k, int R, double kout, T* mean, T* var, T* yk,
                 T* coeffs, int* info, void* ws, int64_t ws_bytes, void* stream) {
@@ -762,6 +807,26 @@ int64_t mgp_fast_coefficients_workspace_bytes(int elem_size, int k, int R, int64
   }
 MGP_DEFINE_COEF_ANY(f32, float)
 MGP_DEFINE_COEF_ANY(f64, double)
+
+int64_t mgp_fast_coefficients_gen_workspace_bytes(int elem_size, int k, int R, int64_t b) {
+  if ((elem_size != 4 && elem_size != 8) || k < 1 || R < 1 || b < 0 || (int64_t)k + 1 + R > kLargeMaxRows) return 0;
+  return coefficients_gen_need_workspace(elem_size, k, R) ? large_workspace_bytes(elem_size, k, R, b) : 0;
+}
+#define MGP_DEFINE_COEF_GEN(SUF, T)                                                                                 \
+  int mgp_fast_coefficients_gen_##SUF(const T* fn, int d, const int64_t* ni, int64_t b, int k, const T* tg, int R,   \
+                                      int nm, double eps, const T* nd, double smoothness, int mid, const T* ls,      \
+                                      int lsc, T* coeffs, int* info, void* workspace, int64_t workspace_bytes,       \
+                                      void* st) {                                                                    \
+    return fast_coefficients_gen<T>(fn, d, ni, b, k, tg, R, nm, eps, nd, smoothness, mid, ls, lsc, coeffs, info,     \
+                                    workspace, workspace_bytes, st);                                                 \
+  }                                                                                                                  \
+  int mgp_fast_posterior_mean_gen_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,       \
+                                        int64_t b, int k, const T* coeffs, const int64_t* crow, int R,               \
+                                        double smoothness, int mid, const T* ls, int lsc, T* mean, void* st) {       \
+    return fast_posterior_mean_gen<T>(fq, fn, d, bi, ni, b, k, coeffs, crow, R, smoothness, mid, ls, lsc, mean, st); \
+  }
+MGP_DEFINE_COEF_GEN(f32, float)
+MGP_DEFINE_COEF_GEN(f64, double)
 
 #define MGP_DEFINE_BWD(SUF, T)                                                                                      \
   int mgp_posterior_backward_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, \

@@ -145,5 +145,11 @@ int backward_gen_large_max_nn_count(int elem_size);
 // BackwardArgs, grad_nu (b) may be NULL; MGP_EUNSUPPORTED beyond max_nn_count_backward_gen
 template <typename T> int launch_backward_gen(const BackwardArgs&, void* grad_nu, hipStream_t);
 int max_nn_count_backward_gen(int elem_size);
+// ... and of the prediction from precomputed coefficients (mgp_fast_mean.hip): launch_fast_mean's arguments with the
+// smoothness in place of the kernel id
+template <typename T>
+int launch_fast_mean_gen(const void* feat_q, const void* feat_nn, int d, const int64_t* batch_idx, const int64_t* nn_idx, int64_t b,
+                         int k, const void* coeffs, const int64_t* coeff_row, int R, double smoothness, int metric_id,
+                         const void* length_scale, int ls_count, void* mean, hipStream_t stream);
 
 }  // namespace mgp

@@ -94,6 +94,9 @@ template <typename T>
 __global__ void fused_generic_coeffs_kernel(FusedArgs a) { fused_generic_body<T, false, true>(a, GenLaunch{}); }
 template <typename T>
 __global__ void fused_generic_gen_kernel(FusedArgs a, GenLaunch g) { fused_generic_body<T, true>(a, g); }
+// ... and its coefficient output (mgp_fast_coefficients_gen_*): GEN x COEFFS, an instantiation of its own as well
+template <typename T>
+__global__ void fused_generic_gen_coeffs_kernel(FusedArgs a, GenLaunch g) { fused_generic_body<T, true, true>(a, g); }
 
 // LDS carve: [S: rows*SP T][piv: k T][flag]
 template <typename T>
@@ -178,9 +181,12 @@ static int launch_fused_generic_impl(const FusedArgs& in, hipStream_t stream) {
     g = gen_launch_constants(a.smoothness, sizeof(T) == 8);
     g.tab = (int)(fc.lds - table);
   }
-  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic%s_kernel<%s>", GEN ? "_gen" : a.coeffs ? "_coeffs" : "", sizeof(T) == 4 ? "float" : "double");
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic%s%s_kernel<%s>", GEN ? "_gen" : "", a.coeffs ? "_coeffs" : "", sizeof(T) == 4 ? "float" : "double");
   const int threads = lds_factor_threads(a.k + 1 + a.R);
-  if constexpr (GEN) return a.coeffs ? MGP_EUNSUPPORTED : launch_capacity(&fused_generic_gen_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a, g).status;
+  if constexpr (GEN) {
+    if (a.coeffs) return launch_capacity(&fused_generic_gen_coeffs_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a, g).status;
+    return launch_capacity(&fused_generic_gen_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a, g).status;
+  }
   else if (a.coeffs) return launch_capacity(&fused_generic_coeffs_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a).status;
   else return launch_capacity(&fused_generic_kernel<T>, threads, fc.lds, a.b, Capacity{16}, stream, &label, a).status;
 }

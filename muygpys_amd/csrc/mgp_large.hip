@@ -32,7 +32,8 @@ namespace mgp {
 // measured 0.3 - 0.4 % behind this code at k = 300, d = 8, outside its own run-to-run spread, though the loops that take
 // the time were the same instructions.  A model parameter that touches the assembly is written here as well.
 // (LDS carve: as fused_large_body below, + the node table at byte g.tab, behind everything else)
-template <typename T>
+// COEFFS: as in fused_large_body (mgp_fast_coefficients_gen_*), an instantiation of its own.
+template <typename T, bool COEFFS = false>
 __device__ __forceinline__ void fused_large_gen_body(const FusedArgs& a, T* workspace, int slab_elems, const GenLaunch& g) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
@@ -67,7 +68,8 @@ __device__ __forceinline__ void fused_large_gen_body(const FusedArgs& a, T* work
     const int rows = k + 1 + R;
     const int npairs = (k + 1) * k / 2;
     const SlabRows<T> row{workspace + (int64_t)blockIdx.x * slab_elems, k};
-    fill_index_list(idx, a, nb, k, tid, NT);
+    if constexpr (COEFFS) fill_index_list_no_query(idx, a, nb, k, tid, NT);
+    else fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
     // squared distances, one chunk of dc features at a time, the partial sums in the slab (pair_distances, written out)
     for (int d0 = 0; d0 < d; d0 += dc) {
@@ -125,6 +127,10 @@ __device__ __forceinline__ void fused_large_gen_body(const FusedArgs& a, T* work
     T* yk = static_cast<T*>(a.ykinvy);
     emit_outputs<T>(row, k, R, T(1), bad, true, mean ? mean + nb * R : nullptr, var ? var + nb : nullptr,
                     yk ? yk + nb * R : nullptr, tid);
+    if constexpr (COEFFS) {
+      if (a.coeffs)  // (the diagonal holds the inverse pivots)
+        back_substitute_columns<T>(row, k, R, [&](int j) { return row(j)[j]; }, bad, static_cast<T*>(a.coeffs) + nb * (int64_t)k * R, tid, NT);
+    }
     if (bad && tid == 0 && a.info) atomicAdd(a.info, 1);
   }
 }
@@ -194,6 +200,10 @@ __global__ void __launch_bounds__(512) fused_large_coeffs_kernel(FusedArgs a, T*
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_gen_kernel(FusedArgs a, T* workspace, int slab_elems, GenLaunch g) {
   fused_large_gen_body<T>(a, workspace, slab_elems, g);
+}
+template <typename T>
+__global__ void __launch_bounds__(512) fused_large_gen_coeffs_kernel(FusedArgs a, T* workspace, int slab_elems, GenLaunch g) {
+  fused_large_gen_body<T, true>(a, workspace, slab_elems, g);
 }
 
 template <typename T>
@@ -282,12 +292,13 @@ static int launch_fused_large_impl(const FusedArgs& in, void* workspace, int64_t
     g = gen_launch_constants(a.smoothness, sizeof(T) == 8);
     g.tab = (int)(fc.lds - table);
   }
-  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large%s_kernel<%s>", GEN ? "_gen" : a.coeffs ? "_coeffs" : "", sizeof(T) == 4 ? "float" : "double");
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large%s%s_kernel<%s>", GEN ? "_gen" : "", a.coeffs ? "_coeffs" : "", sizeof(T) == 4 ? "float" : "double");
   const int threads = slab_block_threads((int)rows), slab_elems = (int)(slab / (int64_t)sizeof(T));
   const Capacity cap{kMaxPerCu, workspace_bytes / slab};
-  if constexpr (GEN)
-    return a.coeffs ? MGP_EUNSUPPORTED : launch_capacity(&fused_large_gen_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems, g).status;
-  else if (a.coeffs)
+  if constexpr (GEN) {
+    if (a.coeffs) return launch_capacity(&fused_large_gen_coeffs_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems, g).status;
+    return launch_capacity(&fused_large_gen_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems, g).status;
+  } else if (a.coeffs)
     return launch_capacity(&fused_large_coeffs_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems).status;
   else
     return launch_capacity(&fused_large_kernel<T>, threads, fc.lds, a.b, cap, stream, &label, a, static_cast<T*>(workspace), slab_elems).status;

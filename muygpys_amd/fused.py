@@ -766,6 +766,51 @@ def gen_backward_default() -> str:
     return _GEN_BACKWARD
 
 
+# how the fast-posterior-mean workflow serves the general-smoothness Matern: "materialised" (coefficients through
+# mgp_pairwise_dists_* + mgp_matern_gen_* + mgp_solve_* in row chunks, predictions through a materialised Kcross and an
+# einsum) or "fused" (one mgp_fast_coefficients_gen_* launch for the table, one mgp_fast_posterior_mean_gen_* launch per
+# query batch; the materialised route behind them where the library refuses: nu > 30, more than 1024 rows).
+# MUYGPYS_HIP_GEN_FAST, unset = materialised.
+GEN_FAST_MODES = ("materialised", "fused")
+
+
+def _gen_fast_from_env() -> str:
+    mode = os.environ.get("MUYGPYS_HIP_GEN_FAST", "") or "materialised"
+    if mode not in GEN_FAST_MODES:
+        raise ValueError(f"MUYGPYS_HIP_GEN_FAST={mode!r} is none of {GEN_FAST_MODES}")
+    return mode
+
+
+_GEN_FAST = _gen_fast_from_env()
+
+
+@contextlib.contextmanager
+def gen_fast(mode: str):
+    """``with fused.gen_fast("fused"):`` -- the general-smoothness Matern on the fused coefficient and prediction kernels
+    inside the block (:func:`fast_coefficients`, :func:`fast_posterior_mean`, ``lazy_eval.fast_mean`` and the example
+    workflow on top of them); the previous mode is restored on the way out."""
+    global _GEN_FAST
+    if mode not in GEN_FAST_MODES:
+        raise ValueError(f"gen_fast mode {mode!r} is none of {GEN_FAST_MODES}")
+    previous, _GEN_FAST = _GEN_FAST, mode
+    try:
+        yield
+    finally:
+        _GEN_FAST = previous
+
+
+def gen_fast_default() -> str:
+    """The mode in force right now (the environment's choice, or an enclosing block's)."""
+    return _GEN_FAST
+
+
+def _gen_smoothness(spec: KernelSpec) -> float:
+    """nu of a general-smoothness model; the forward's ``ValueError`` for a missing or non-positive one."""
+    if spec.smoothness is None or not float(spec.smoothness) > 0.0:
+        raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
+    return float(spec.smoothness)
+
+
 def _hyper_partials_gen(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_noise: bool, want_nu: bool):
     """:func:`_hyper_partials` of the general-smoothness Matern: ``(g_l, g_n or None[, g_nu])``.  The ladder is the
     slab backward alone, or -- :func:`gen_backward` ``"lds"``, up to ``GEN_BACKWARD_LDS_MAX_NN_COUNT`` --
@@ -1055,13 +1100,19 @@ def fast_posterior_mean(
     R = co.shape[2]
     crow = closest_neighbor.to(torch.int64).contiguous()
     mean = out if out is not None else torch.empty((b, R), device=fn.device, dtype=dtype)
-    rc = _lib.fn("fast_posterior_mean", dtype)(
+    # the general-smoothness Matern under gen_fast("fused"): its own entry, the smoothness in place of the kernel id
+    # (any other mode: the closed-form entry, which refuses the id as it always has)
+    gen = spec.kernel == "matern_gen" and _GEN_FAST == "fused"
+    entry = "fast_posterior_mean_gen" if gen else "fast_posterior_mean"
+    rc = _lib.fn(entry, dtype)(
         _lib.ptr(fq), _lib.ptr(fn), d, _lib.ptr(bi), _lib.ptr(ni), b, k, _lib.ptr(co), _lib.ptr(crow), R,
-        spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(mean), _lib.stream_ptr(),
+        _gen_smoothness(spec) if gen else spec.kernel_id(), spec.metric_id(), _lib.ptr(ls), ls.numel(), _lib.ptr(mean),
+        _lib.stream_ptr(),
     )
     if rc == _lib.EUNSUPPORTED:
-        raise FusedUnsupported(f"mgp_fast_posterior_mean refused kernel {spec.kernel!r} at nn_count = {k}, {R} response column(s)")
-    _lib.check(rc, "mgp_fast_posterior_mean")
+        model = f"{spec.kernel!r} (smoothness {spec.smoothness})" if gen else repr(spec.kernel)
+        raise FusedUnsupported(f"mgp_{entry} refused kernel {model} at nn_count = {k}, {R} response column(s)")
+    _lib.check(rc, f"mgp_{entry}")
     return mean.reshape(b) if squeeze else mean
 
 
@@ -1069,15 +1120,31 @@ def _fused_coefficients(spec: KernelSpec, inp: _Inputs) -> Optional[torch.Tensor
     """``(K_b + eps)^-1 Y_b`` (b, k, R) of the neighbourhoods ``inp.ni`` of one table in ONE launch: the wave kernel
     (``mgp_fast_coefficients_*``: one response, k <= 62) where it serves the shape, else ``mgp_fast_coefficients_any_*``
     (the system in LDS, or on a slab of a workspace beyond ``mgp_max_nn_count``).  None, without a call, for what no fused
-    coefficient kernel serves -- the general-smoothness Matern (not a kernel id of the wave entry at all) and systems of
-    more than 1024 rows (``nn_count + 1 + R``) -- and when the library refuses (``MGP_EUNSUPPORTED``): the caller
-    materialises."""
+    coefficient kernel serves -- the general-smoothness Matern (not a kernel id of the wave entry at all) outside
+    :func:`gen_fast` ``"fused"`` and systems of more than 1024 rows (``nn_count + 1 + R``) -- and when the library refuses
+    (``MGP_EUNSUPPORTED``): the caller materialises.  Under ``gen_fast("fused")`` the general smoothness takes one
+    ``mgp_fast_coefficients_gen_*`` launch."""
     P = _lib.ptr
     fn, b, k, R, dtype = inp.fn, inp.b, inp.k, inp.R, inp.fn.dtype
-    if spec.kernel == "matern_gen" or k + 1 + R > 1024:
+    gen = spec.kernel == "matern_gen"
+    if (gen and _GEN_FAST != "fused") or k + 1 + R > 1024:
         return None
     out = torch.empty((b, k, R), device=fn.device, dtype=dtype)
     info = torch.zeros(1, device=fn.device, dtype=torch.int32)
+    if gen:
+        # gen_fast("fused"): ONE mgp_fast_coefficients_gen_* launch (the LDS workgroup kernel up to mgp_max_nn_count_gen,
+        # no workspace; the slab kernel beyond); None when the library refuses (nu > 30)
+        nu = _gen_smoothness(spec)
+        ws = _lib.workspace("mgp_fast_coefficients_gen_workspace_bytes", dtype, k, R, b, device=fn.device)
+        rc = _lib.fn("fast_coefficients_gen", dtype)(
+            P(fn), inp.d, P(inp.ni), b, k, P(inp.tg), R, inp.mode, inp.eps, P(inp.nz), nu, spec.metric_id(), P(inp.ls),
+            inp.ls.numel(), P(out), P(info), P(ws), 0 if ws is None else ws.numel(), _lib.stream_ptr(),
+        )
+        if rc == _lib.EUNSUPPORTED:
+            return None
+        _lib.check(rc, "mgp_fast_coefficients_gen")
+        _lib.raise_if_not_spd(info, "fast_coefficients")
+        return out
     model = (inp.mode, inp.eps, P(inp.nz), spec.kernel_id(), spec.metric_id(), P(inp.ls), inp.ls.numel())
 
     def wave():  # mgp_fast_coefficients_* (fused gather .. LDL^T .. back-substitution on the wave kernel)
@@ -1108,8 +1175,9 @@ def fast_coefficients(spec: KernelSpec, train_features: torch.Tensor, train_targ
     _src/gp/tensors/numpy.py:97-108, _src/gp/muygps/numpy.py:88-95), computed once per model: one
     fused launch for any ``nn_count`` and response count with ``nn_count + 1 + R <= 1024`` (``mgp_fast_coefficients_*``
     for one response and k <= 62, ``mgp_fast_coefficients_any_*`` otherwise) or, with ``fused=False`` / for what no
-    fused kernel serves (the general-smoothness Matern, through ``mgp_matern_gen_*``; more than 1024 rows), row chunks
-    through the per-function kernels.  Returns ``(n, k)`` or ``(n, k, R)`` together with the updated index table
+    fused kernel serves (the general-smoothness Matern, through ``mgp_matern_gen_*`` -- unless :func:`gen_fast` ``"fused"``
+    is in force: then ``mgp_fast_coefficients_gen_*``, one launch; more than 1024 rows), row chunks through the
+    per-function kernels.  Returns ``(n, k)`` or ``(n, k, R)`` together with the updated index table
     ``(n, k)``."""
     from muygpys_amd._src.gp.kernels import hip as K
     from muygpys_amd._src.gp.muygps import hip as M

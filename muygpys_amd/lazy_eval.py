@@ -208,13 +208,16 @@ def fast_mean(Kcross: lazy.LazyCov, coeffs: torch.Tensor, rows: Optional[torch.T
     hands over, examples/from_indices.py:113-118).  ``rows`` (b,): ``coeffs`` is the whole table (n_train, k[, R]) and the
     kernel picks row ``rows[t]`` for test point t itself -- no gathered copy.  Returns (b,) or (b, R), squeezed like the
     reference; None when the handle is not a plain crosswise covariance the kernel evaluates (the general-smoothness
-    Matern included) or the shapes / dtypes do not fit: the caller then materialises the handle."""
-    from .fused import FusedUnsupported, KernelSpec, fast_posterior_mean
+    Matern outside ``fused.gen_fast("fused")``, and beyond nu = 30 inside it) or the shapes / dtypes do not fit: the
+    caller then materialises the handle."""
+    from .fused import FusedUnsupported, KernelSpec, fast_posterior_mean, gen_fast_default
 
     if not isinstance(Kcross, lazy.LazyCov):
         return None
     c = Kcross.diffs
-    if not (c.kind == "crosswise" and c.reduced and c.metric in ("l2", "F2") and Kcross.kernel != "matern_gen"):
+    # (the general-smoothness Matern: under fused.gen_fast("fused") alone, through mgp_fast_posterior_mean_gen_*)
+    gen = Kcross.kernel == "matern_gen"
+    if not (c.kind == "crosswise" and c.reduced and c.metric in ("l2", "F2") and (not gen or gen_fast_default() == "fused")):
         return None
     if not (isinstance(coeffs, torch.Tensor) and coeffs.is_cuda and coeffs.ndim in (2, 3)):
         return None
@@ -227,7 +230,8 @@ def fast_mean(Kcross: lazy.LazyCov, coeffs: torch.Tensor, rows: Optional[torch.T
         rows = torch.arange(b, device=coeffs.device)
     elif tuple(rows.shape) != (b,):
         return None
-    spec = KernelSpec(Kcross.kernel, c.metric, 1.0 if c.length_scale is None else c.length_scale, 0.0)
+    spec = KernelSpec(Kcross.kernel, c.metric, 1.0 if c.length_scale is None else c.length_scale, 0.0,
+                      Kcross.smoothness if gen else None)
     try:
         out = fast_posterior_mean(spec, c.data, c.nn_data, c.data_indices, c.nn_indices, coeffs, rows)
     except FusedUnsupported:
