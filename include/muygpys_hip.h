@@ -658,6 +658,38 @@ int mgp_knn_cells_scan(const float* table, int64_t n, int d, const int64_t* cell
                        const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
                        void* stream);
 
+/* Exact search over a rectilinear grid for tables of 1 to 3 features (csrc/mgp_knn_grid.hip): every query walks the
+ * cells around its own, shell by shell, until the distance to the faces of the walked block proves its list final.
+ * Fills the role of the reference's algorithm="kd_tree" / "ball_tree" (scikit-learn behind NN_Wrapper,
+ * src/MuyGPyS/neighbors.py:89-107): exact, sub-quadratic at low d.  The exact scans above stay the default.
+ *   table (n, 4) fp32: the features zero-padded to four, rows stored CELL BY CELL and 16-byte aligned, n < 2^31
+ *   g0, g1, g2 >= 1: the grid's dimensions (1 on an axis the table does not have), g0 g1 g2 <= 2^24; the linear cell
+ *       id is c0 + g0 (c1 + g1 c2), so the cells c0 - r .. c0 + r of one grid row are one contiguous run of rows
+ *   cell_start (g0 g1 g2 + 1) int64, non-decreasing: cell j = rows [cell_start[j], cell_start[j + 1]); empty cells are
+ *       legal.  Values outside [0, n] are clamped: no value makes the kernel read outside the table
+ *   edges (g0 - 1 + g1 - 1 + g2 - 1) fp32: the interior edges of axis 0, then 1, then 2, each non-decreasing; a row
+ *       belongs to cell c_a = #{j : E_a[j] <= x_a} of axis a (the outer cells are unbounded, equal edges are empty
+ *       cells).  May be NULL when every g is 1
+ *   queries (m, 4) fp32, rows 16-byte aligned
+ *   qcell (m, 3) int32: each query's cell per axis by the same rule; clamped to the grid in the kernel
+ *   self_pos (m) or NULL: the stored position a query must not return
+ *   best_d / best_i (m, k), 1 <= k <= 64, OUT: the k smallest difference-form fp32 squared distances over the WHOLE
+ *       table and their stored positions, UNORDERED; rows tied at the k-th distance are taken in order of position, so
+ *       the result is a function of the table alone.  Where the table holds fewer than k admissible rows the missing
+ *       entries are best_i = -1, best_d = +inf
+ *   shells (m) int32 OUT: the radius, in cells, of the last shell the query walked: 0 where its own cell sufficed
+ * The walk stops after shell r when no cell is left outside the block c_a - r .. c_a + r, or when
+ * tau < B^2 (1 - 2^-20): tau the k-th best distance (+inf while fewer than k rows are held), B the smallest distance
+ * from the query to a face of the block behind which cells remain.  The trip count is at most max(g0, g1, g2) whatever
+ * the data hold; a non-finite coordinate makes the comparison false and the walk ends at the grid's edge.
+ * Order of the checks, all before any HIP call: sizes (n, m < 0, k < 1, a g < 1: MGP_EINVAL), nothing to do (m == 0:
+ * MGP_OK, pointers not looked at), NULL pointers (MGP_EINVAL; self_pos and the stream are optional, edges where every
+ * g is 1), then MGP_EUNSUPPORTED for k > 64, n >= 2^31, g0 g1 g2 > 2^24, table or queries off 16-byte alignment and
+ * a launch grid of 2^31 workgroups or more (four queries each).  Nothing synchronises. */
+int mgp_knn_grid_scan(const float* table, int64_t n, const int64_t* cell_start, int g0, int g1, int g2,
+                      const float* edges, const float* queries, int64_t m, const int32_t* qcell,
+                      const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* shells, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Backward pass of the fused hot path (vector-Jacobian product).  Replaces what
  * torch autograd derives for the reference's torch backend when a deep-kernel

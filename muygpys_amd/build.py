@@ -56,6 +56,8 @@ PER_FILE_FLAGS = {
     "mgp_classify.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the cell scan of the approximate search: the query row and two steps of table rows sit in registers)
     "mgp_knn_cells.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the grid walk of the exact search at 1 to 3 features: tests/test_knn_grid_resources.py reads its record)
+    "mgp_knn_grid.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the blocked factorisation beyond LDS: a 32 x 32 diagonal block and a panel row sit in registers)
     "mgp_large.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and the LDS workgroup kernels, whose general-smoothness instantiations carry the Bessel evaluator:

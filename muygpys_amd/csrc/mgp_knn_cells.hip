@@ -16,35 +16,18 @@
 //           position bits, only when such a tie exists).  The result is therefore the k smallest by (distance,
 //           position) of the candidate set, whatever the order of the cells or the neighbours in the workgroup.
 //           After the first few hundred rows merges are rare: a row beats tau with probability ~ k / rows seen.
+//           (admit and merge live in mgp_knn_list.h: the grid walk of mgp_knn_grid.hip keeps its list the same way.)
 //
 // Reference: the approximate branch of the reference's neighbour search (hnswlib behind NN_Wrapper,
 // src/MuyGPyS/neighbors.py:109-127,213-262); the inverted-cell index fills the same role on a GPU.
 #include <cstdint>
 
 #include "mgp_args.h"
+#include "mgp_knn_list.h"
 
 namespace mgp {
 
 namespace {
-
-constexpr int kCellWaves = 4;     // queries per workgroup
-constexpr int kCellList = 64;     // list slots per wave (k <= 64)
-constexpr int kCellPending = 128; // pending slots per wave: merged when fewer than 64 are free
-constexpr int kCellSlots = kCellList + kCellPending;
-
-__device__ __forceinline__ unsigned cell_key(float x) {  // float_key of mgp_knn_select.hip
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float cell_unkey(unsigned key) {
-  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-__device__ __forceinline__ int popc64(unsigned long long m) { return __builtin_popcountll(m); }
-// the LDS traffic of one wave is in program order; this keeps the compiler from moving it
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 struct CellScanArgs {
   const float* table;
@@ -68,10 +51,7 @@ __global__ __launch_bounds__(kCellWaves * 64) void knn_cells_scan_kernel(const C
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t q = (int64_t)blockIdx.x * kCellWaves + wave;
   if (q >= a.m) return;
-  float* ld = s_dist[wave];
-  int* lp = s_pos[wave];
-  const unsigned long long lanes_below = (1ull << lane) - 1ull;
-  const int k = a.k;
+  WaveList list(s_dist[wave], s_pos[wave], lane, a.k);
 
   // the query row: its address is wave-uniform -> scalar registers up to d = 32; longer rows would spill those and are
   // broadcast from LDS instead (every lane reads the same 16 bytes: no bank conflict)
@@ -90,65 +70,6 @@ __global__ __launch_bounds__(kCellWaves * 64) void knn_cells_scan_kernel(const C
   }
   const int64_t self = a.self_pos ? a.self_pos[q] : (int64_t)-1;
   const int* pr = a.probes + q * (int64_t)a.nprobe;
-
-  int held = 0, npend = 0;  // entries of the list / of the pending buffer (wave-uniform)
-  float tau = __builtin_inff();
-
-  // the k smallest of list + pending by (distance, position) -> list
-  auto merge = [&]() {
-    const int total = held + npend;
-    const int kk = total < k ? total : k;
-    unsigned key[3];
-    float dv[3];
-    int pv[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int s = j * 64 + lane;
-      const bool on = j == 0 ? s < held : (s - kCellList) < npend;
-      dv[j] = ld[s];
-      pv[j] = lp[s];
-      key[j] = on ? cell_key(dv[j]) : 0xFFFFFFFFu;  // (an admitted distance is never NaN: no entry carries this key)
-    }
-    wave_lds_fence();
-    // T = the kk-th smallest key: the largest T with count(key < T) < kk
-    unsigned T = 0;
-#pragma unroll 1
-    for (int bit = 31; bit >= 0; --bit) {
-      const unsigned trial = T | (1u << bit);
-      const int cnt = popc64(__ballot(key[0] < trial)) + popc64(__ballot(key[1] < trial)) + popc64(__ballot(key[2] < trial));
-      if (cnt < kk) T = trial;
-    }
-    const int below = popc64(__ballot(key[0] < T)) + popc64(__ballot(key[1] < T)) + popc64(__ballot(key[2] < T));
-    const int equal = popc64(__ballot(key[0] == T)) + popc64(__ballot(key[1] == T)) + popc64(__ballot(key[2] == T));
-    const int need = kk - below;  // >= 1 of the `equal` entries at T
-    int P = 0x7FFFFFFF;           // the largest position taken among them
-    if (equal > need) {
-      P = 0;
-#pragma unroll 1
-      for (int bit = 30; bit >= 0; --bit) {
-        const int trial = P | (1 << bit);
-        const int cnt = popc64(__ballot(key[0] == T && pv[0] < trial)) + popc64(__ballot(key[1] == T && pv[1] < trial)) +
-                        popc64(__ballot(key[2] == T && pv[2] < trial));
-        if (cnt < need) P = trial;
-      }
-    }
-    int base = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const bool sel = key[j] < T || (key[j] == T && pv[j] <= P);
-      const unsigned long long mask = __ballot(sel);
-      const int at = base + popc64(mask & lanes_below);
-      if (sel && at < kk) {
-        ld[at] = dv[j];
-        lp[at] = pv[j];
-      }
-      base += popc64(mask);
-    }
-    wave_lds_fence();
-    held = kk;
-    npend = 0;
-    if (total >= k) tau = cell_unkey(T);
-  };
 
   // the steps of the scan: (first row, end of its cell), cell after cell
   int pi = 0;
@@ -202,18 +123,7 @@ __global__ __launch_bounds__(kCellWaves * 64) void knn_cells_scan_kernel(const C
       s3 = __builtin_fmaf(e3, e3, s3);
     }
     const float dd = (s0 + s1) + (s2 + s3);
-    const bool pass = cur_row < cur_end && cur_row != self && dd <= tau;
-    const unsigned long long mask = __ballot(pass);
-    if (mask) {
-      if (pass) {
-        const int at = kCellList + npend + popc64(mask & lanes_below);
-        ld[at] = dd;
-        lp[at] = (int)cur_row;
-      }
-      npend += popc64(mask);
-      wave_lds_fence();
-      if (npend > kCellPending - 64) merge();
-    }
+    list.admit(cur_row < cur_end && cur_row != self && dd <= list.tau, dd, cur_row);
     have = have_next;
     if (have_next) {
 #pragma unroll
@@ -222,14 +132,10 @@ __global__ __launch_bounds__(kCellWaves * 64) void knn_cells_scan_kernel(const C
       cur_end = nxt_end;
     }
   }
-  if (npend > 0) merge();
+  if (list.npend > 0) list.merge();
 
-  if (lane < k) {
-    const bool on = lane < held;
-    a.best_d[q * k + lane] = on ? ld[lane] : __builtin_inff();
-    a.best_i[q * k + lane] = on ? lp[lane] : -1;
-  }
-  if (lane == 0) a.short_flag[q] = held < k ? 1 : 0;
+  list.store(a.best_d, a.best_i, q);
+  if (lane == 0) a.short_flag[q] = list.held < a.k ? 1 : 0;
 }
 
 template <int D4>

@@ -28,7 +28,7 @@ squared-l2 distances)`` with the self-match dropped for batch queries (neighbors
   ``|q|^2 + |x|^2 - 2 q.x`` through ``torch.matmul`` (rocBLAS) followed by ``topk``.
 
 ``scan_route(d, k, dtype, train_count, use_scan)`` is the rule, a pure function; ``last_route`` ("scan" | "wide" |
-"long" | "dense" | "ivf") names what served the most recent search.
+"long" | "dense" | "ivf" | "grid") names what served the most recent search.
 
 Either way the k winners are then re-measured in difference form and sorted, so the returned
 distances carry no cancellation error and ties resolve by distance then index order of the sort.
@@ -40,6 +40,21 @@ cell by cell, and every query scans only its ``nprobe`` nearest cells (``mgp_knn
 cells and approximate over the table -- good on data with low-dimensional structure (clusters, manifolds), poor on
 data without (i.i.d. Gaussian at d = 40: recall 0.49 at 8 of 64 cells in a CPU simulation).  A query whose probed
 cells hold fewer than k rows is recomputed exactly on the dense path.
+
+``nn_method="exact", algorithm="grid"`` is the exact search for tables of 1 to 3 features (the role of the reference's
+``algorithm="kd_tree"`` / ``"ball_tree"``, which it hands to scikit-learn; every other value of ``algorithm`` is
+ignored, and the default route does not change).  The centred table is stored cell by cell over a rectilinear grid
+(``grid_dims``: near-cubic cells of ``cell_rows`` rows on average; ``edges="uniform"`` | ``"quantile"`` | a list of d
+edge tensors; cells are defined by comparisons against the stored edges, ``grid_cells``), and every query walks the
+cells around its own shell by shell until the distance to the faces of the walked block proves its list final
+(``mgp_knn_grid_scan``, ``csrc/mgp_knn_grid.hip``): a few hundred pair distances per query instead of n.  fp32 only,
+``1 <= d <= 3``, ``k <= 64``, ``n < 2^31``: anything else is a ``ValueError`` at construction, never another algorithm.
+``last_route`` is "grid" and ``last_shells`` holds, per query, the radius in cells of the last shell walked.  A query
+with a NaN feature is at no distance from anything (and so is every query of a table that holds a NaN: the mean it is
+centred on is NaN): its walk ends at the grid's edge with an empty list, it is flagged in ``last_short`` (device int32,
+1 per query left with fewer than k neighbours), and its entries name the row at stored position 0 (``_perm[0]``) at a
+NaN distance.  ``cell_rows`` defaults to 16, the best of the sweep of ``tools/knngridbench.py`` at 1 M rows
+(``profiles/knn_grid_bench.json``).
 """
 
 from __future__ import annotations
@@ -59,6 +74,9 @@ WIDE_MAX_K = 1024      # mgp_knn_wide_max_nn_count(): the longest list of the wi
 LONG_MAX_D = 256       # mgp_knn_long_max_features(): the widest row of the long-row scans (64 < d: csrc/mgp_knn_long.hip)
 CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
 CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
+GRID_MAX_D = 3         # most features of the grid walk (3^d cells around a query: csrc/mgp_knn_grid.hip)
+GRID_MAX_CELLS = 1 << 24  # most cells of a grid (mgp_knn_grid_scan's limit): beyond that the cells grow
+GRID_CELL_ROWS = 16    # mean rows per cell of a grid where the caller names none: the sweep's best at 1 M rows
 
 
 def stored_width(d: int) -> int:
@@ -114,16 +132,66 @@ def cell_layout(assignment: torch.Tensor, nlist: int):
     return perm, inv, cell_start
 
 
+def grid_dims(n: int, extents, cell_rows: float = GRID_CELL_ROWS) -> Tuple[int, int, int]:
+    """(g0, g1, g2) of the grid over a table of ``n`` rows whose axes span ``extents`` (one to three numbers): near-cubic
+    cells, g_a proportional to the axis extent, g0 g1 g2 ~ n / cell_rows and at most GRID_MAX_CELLS (beyond that the
+    cells grow).  g_a = 1 on an axis the table does not have, on an axis of zero (or non-finite) extent and on an axis
+    thinner than one cell.  A pure function."""
+    ext = [float(v) for v in extents]
+    if not 1 <= len(ext) <= GRID_MAX_D:
+        raise ValueError(f"a grid has 1 to {GRID_MAX_D} axes (1 <= d <= {GRID_MAX_D}), got {len(ext)}")
+    target = min(GRID_MAX_CELLS, max(1, int(round(n / float(cell_rows)))))
+    g = [1, 1, 1]
+    active = [a for a, v in enumerate(ext) if v > 0 and math.isfinite(v)]
+    side = 0.0
+    while active:
+        side = math.exp((sum(math.log(ext[a]) for a in active) - math.log(target)) / len(active))
+        thin = [a for a in active if ext[a] < side]  # (not one cell wide: one cell, and the others share the target)
+        if not thin:
+            break
+        active = [a for a in active if a not in thin]
+    for a in active:
+        g[a] = max(1, int(round(ext[a] / side)))
+    while g[0] * g[1] * g[2] > GRID_MAX_CELLS:  # (rounding up on every axis at the cap)
+        g[g.index(max(g))] -= 1
+    return g[0], g[1], g[2]
+
+
+def grid_cells(x: torch.Tensor, edges) -> torch.Tensor:
+    """(m, 3) int32: the cell of every row of ``x`` (m, >= d) per axis, c_a = #{j : E_a[j] <= x_a} against the interior
+    edges ``edges[a]`` (1-D, non-decreasing; an axis without edges is one cell).  Comparisons against the stored edge
+    values, never a division: a row at an edge value goes to the upper cell.  Any device."""
+    out = torch.zeros((x.shape[0], 3), dtype=torch.int32, device=x.device)
+    for a, e in enumerate(edges):
+        if e is not None and e.numel():
+            out[:, a] = torch.bucketize(x[:, a].contiguous(), e, right=True).to(torch.int32)
+    return out
+
+
+def grid_linear(cells: torch.Tensor, dims) -> torch.Tensor:
+    """The linear cell id (int64) of per-axis cells (m, 3): axis 0 runs fastest."""
+    c = cells.to(torch.int64)
+    return c[:, 0] + dims[0] * (c[:, 1] + dims[1] * c[:, 2])
+
+
 class NN_Wrapper:
     def __init__(self, train: torch.Tensor, nn_count: int, nn_method: str = "exact", chunk: int = 4096,
                  use_scan: bool = True, scan_kind: str = "auto", shuffle: bool = True, nlist=None, nprobe=None,
-                 kmeans_iters: int = 10, seed: int = 0, _cells=None, **kwargs):
+                 kmeans_iters: int = 10, seed: int = 0, _cells=None, algorithm=None, edges="uniform",
+                 cell_rows=GRID_CELL_ROWS, **kwargs):
         if nn_method.lower() not in ("exact", "ivf"):
             raise NotImplementedError(f"Nearest Neighbor algorithm {nn_method} is not implemented.")
+        self.algorithm = None  # "grid": the grid walk serves every search (any other value of the keyword is ignored)
+        grid = nn_method.lower() == "exact" and algorithm == "grid" and isinstance(train, torch.Tensor)
+        if grid:  # (its limits before anything else: they need no device)
+            self._check_grid(train, nn_count, edges, cell_rows)
         if not (isinstance(train, torch.Tensor) and train.is_cuda):
             raise TypeError("NN_Wrapper takes a torch tensor on the ROCm device")
         if nn_method.lower() == "ivf":
             self._init_cells(train, nn_count, nlist, nprobe, kmeans_iters, seed, chunk, _cells)
+            return
+        if grid:
+            self._init_grid(train, nn_count, edges, cell_rows, chunk)
             return
         # the table is kept centred on its mean (queries are shifted alike): distances are unchanged,
         # and every Gram-form quantity below (|q|^2 + |x|^2 - 2 q.x, the split-bf16 margin) is computed
@@ -187,6 +255,9 @@ class NN_Wrapper:
         if self.nn_method == "ivf":
             self.last_route = "ivf"
             return self._cells_nns(samples, nn_count, exclude)
+        if self.algorithm == "grid":
+            self.last_route = "grid"
+            return self._grid_nns(samples, nn_count, exclude)
         samples = self._pad_features(samples)
         out = self._scan_nns(samples, nn_count, exclude)  # (sets last_route where it serves the call)
         if out is None:
@@ -570,4 +641,123 @@ class NN_Wrapper:
             ri, rd = self._dense_nns(qs[redo], k, None if ex is None else ex[redo])
             si[redo], sd[redo] = self._perm[ri], rd
         idx[order], dist[order], self.last_short[order] = si, sd, short
+        return idx, dist
+
+    # ---- the grid walk (nn_method="exact", algorithm="grid") ---------------------------------------------------------
+
+    @staticmethod
+    def _check_grid(train, nn_count, edges, cell_rows):
+        """The grid scan's contract (include/muygpys_hip.h: mgp_knn_grid_scan) as ValueErrors that name the limit; no
+        other algorithm steps in.  Looks at shapes, dtypes and the caller's edges only: any device."""
+        table = train[:, None] if train.ndim == 1 else train
+        n, d = table.shape
+        k = int(nn_count)
+        if table.dtype != torch.float32:
+            raise ValueError(f"algorithm='grid' serves float32 tables only (fp32 only), got {table.dtype}")
+        if not 1 <= d <= GRID_MAX_D:
+            raise ValueError(f"algorithm='grid' serves 1 to {GRID_MAX_D} features (1 <= d <= {GRID_MAX_D}), got d = {d}")
+        if not 1 <= k <= 64:
+            raise ValueError(f"algorithm='grid' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+        if not 1 <= n < 2**31:
+            raise ValueError(f"algorithm='grid' serves 1 <= n < 2^31 table rows, got n = {n}")
+        if not float(cell_rows) > 0:
+            raise ValueError(f"algorithm='grid' takes cell_rows > 0 (mean rows per cell), got {cell_rows}")
+        if isinstance(edges, str):
+            if edges not in ("uniform", "quantile"):
+                raise ValueError(f"algorithm='grid' takes edges='uniform', 'quantile' or a list of d edge tensors, got {edges!r}")
+            return
+        if len(edges) != d:
+            raise ValueError(f"algorithm='grid' takes one edge tensor per feature, got {len(edges)} for d = {d}")
+        cells = 1
+        for a, e in enumerate(edges):
+            e = torch.as_tensor(e).reshape(-1)
+            if e.numel() and not (bool(torch.isfinite(e).all()) and bool((e[1:] >= e[:-1]).all())):
+                raise ValueError(f"algorithm='grid' takes finite, sorted (non-decreasing) edges; axis {a}'s are not")
+            cells *= e.numel() + 1
+        if cells > GRID_MAX_CELLS:
+            raise ValueError(f"algorithm='grid' serves at most 2^24 cells, got {cells}")
+
+    def _init_grid(self, train, nn_count, edges, cell_rows, chunk):
+        table = train[:, None] if train.ndim == 1 else train
+        n, d = table.shape
+        k = int(nn_count)
+        self.train_count, self.feature_count = n, d
+        self.nn_count, self.nn_method, self.algorithm, self.chunk = k, "exact", "grid", int(chunk)
+        self.use_scan, self.scan_kind, self.last_overflow, self.last_route = False, None, None, None
+        self.last_shells = None  # per query: the radius, in cells, of the last shell its walk took (device int32)
+        self.last_short = None   # per query: 1 where fewer than k rows had a distance that is a number (a NaN query)
+        self.cell_rows = float(cell_rows)
+        self._width = 4
+        self._mean = table.double().mean(0).to(table.dtype)
+        x = self._pad_features(table - self._mean)
+        if isinstance(edges, str):
+            lo, hi = x[:, :d].min(0).values.double(), x[:, :d].max(0).values.double()
+            dims = grid_dims(n, (hi - lo).cpu().tolist(), self.cell_rows)
+            per_axis = []
+            for a in range(d):
+                inner = torch.arange(1, dims[a], device=x.device)
+                if edges == "uniform":  # the bounding box in equal parts (fp64, then rounded once: non-decreasing)
+                    e = (lo[a] + inner.double() * ((hi[a] - lo[a]) / dims[a])).to(x.dtype)
+                else:                   # per-axis quantiles: equal counts along each axis
+                    e = x[:, a].sort().values[(inner * n) // dims[a]]
+                per_axis.append(e.contiguous())
+        else:
+            # the caller's edges, shifted like the table (monotone: a row below an edge stays at or below it)
+            per_axis = [(torch.as_tensor(e, device=x.device).reshape(-1).to(x.dtype) - self._mean[a]).contiguous()
+                        for a, e in enumerate(edges)]
+            dims = tuple(int(e.numel()) + 1 for e in per_axis) + (1,) * (3 - d)
+        self.grid_shape = dims
+        self._edges = per_axis + [None] * (3 - d)
+        self._edges_flat = torch.cat(per_axis).contiguous()
+        cells = grid_linear(grid_cells(x, self._edges), dims)
+        self._perm, self._inv, self.cell_start = cell_layout(cells, dims[0] * dims[1] * dims[2])
+        self.train = x[self._perm].contiguous()
+
+    def _grid_scan(self, q, qcell, k, self_pos=None):
+        """mgp_knn_grid_scan on centred, padded queries and their per-axis cells (m, 3) int32, in the order given:
+        (best_d, best_i (stored positions, unordered), shells)."""
+        m, dev = q.shape[0], q.device
+        best_d = torch.empty((m, k), device=dev, dtype=torch.float32)
+        best_i = torch.empty((m, k), device=dev, dtype=torch.int32)
+        shells = torch.empty((m,), device=dev, dtype=torch.int32)
+        g0, g1, g2 = self.grid_shape
+        _lib.check(_lib.load().mgp_knn_grid_scan(
+            _lib.ptr(self.train), self.train_count, _lib.ptr(self.cell_start), g0, g1, g2, _lib.ptr(self._edges_flat),
+            _lib.ptr(q), m, _lib.ptr(qcell), _lib.ptr(self_pos), k, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(shells),
+            _lib.stream_ptr()), "mgp_knn_grid_scan")
+        return best_d, best_i, shells
+
+    def _grid_nns(self, samples, nn_count, exclude=None):
+        """The queries' cells, the walk in order of linear cell id (consecutive workgroups meet the same cells in L2), the
+        finish kernel.  Returns the caller's row numbers."""
+        q = self._pad_features(samples)
+        m, k, dev = q.shape[0], int(nn_count), q.device
+        idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+        dist = torch.empty((m, k), dtype=q.dtype, device=dev)
+        if not 1 <= k <= 64:
+            raise ValueError(f"algorithm='grid' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+        have = self.train_count - (0 if exclude is None else 1)
+        if k > have:
+            raise ValueError(f"algorithm='grid': nn_count = {k} neighbours of a table that can give {have} "
+                             f"(n = {self.train_count}{', the query row excluded' if exclude is not None else ''})")
+        # (a refused search leaves the record of the last served one as it is)
+        self.last_shells = torch.zeros((m,), dtype=torch.int32, device=dev)
+        self.last_short = torch.zeros((m,), dtype=torch.int32, device=dev)
+        if m == 0:
+            return idx, dist
+        qcell = grid_cells(q, self._edges)
+        order = grid_linear(qcell, self.grid_shape).argsort()
+        qs, cs = q[order].contiguous(), qcell[order].contiguous()
+        ex = None if exclude is None else exclude.to(torch.int64)[order].contiguous()
+        _, best_i, shells = self._grid_scan(qs, cs, k, ex)
+        # -1: fewer than k rows at a distance that is a number (a NaN feature in the query, or in the table's mean).
+        # The finish kernel reads rows, so such an entry becomes stored row 0 -- and the query is flagged in last_short
+        short = (best_i < 0).any(1).to(torch.int32)
+        best_i.clamp_(min=0)
+        si = torch.empty((m, k), dtype=torch.int64, device=dev)
+        sd = torch.empty((m, k), dtype=q.dtype, device=dev)
+        _lib.check(_lib.load().mgp_knn_finish_f32(_lib.ptr(qs), _lib.ptr(self.train), self._width, _lib.ptr(best_i), m, k,
+                                                  _lib.ptr(self._perm), _lib.ptr(si), _lib.ptr(sd), _lib.stream_ptr()),
+                   "mgp_knn_finish_f32")
+        idx[order], dist[order], self.last_shells[order], self.last_short[order] = si, sd, shells, short
         return idx, dist
