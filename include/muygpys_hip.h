@@ -266,6 +266,55 @@ int mgp_posterior_gen_large_f64(const double* feat_q, const double* feat_nn, int
                                 void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * A length scale per neighbourhood (the nonstationary model: HierarchicalParameter,
+ * gp/hyperparameter/experimental/hierarchical.py:15-158, accepted by Isotropy / Anisotropy, whose (b,) scale
+ * divides Kin and Kcross of batch element i alike: gp/deformation/isotropy.py:60-89, anisotropy.py:70) on the two
+ * workgroup kernel families by name, T1-T4, D1/D2, N1/N2, S1-S3 in one launch as mgp_posterior_generic_* /
+ * mgp_posterior_large_* do them.  The parameter lists are those of mgp_posterior_gen_generic_* /
+ * mgp_posterior_gen_large_* with `kernel_id` in place of `smoothness` and `length_scale_batch` in place of
+ * `length_scale`: device, (b, ls_count) row-major, ls_count == 1 (Isotropy) or d (Anisotropy); row nb belongs to the
+ * neighbourhood at POSITION nb of the batch (not to training row batch_idx[nb]).  Closed-form kernels only; plain
+ * tables only; targets_batch != 0: `targets` is the gathered (b, k, R) tensor.
+ *   With every row of length_scale_batch equal to the scale(s) of a scalar launch, an entry returns the bits of
+ *   mgp_posterior_generic_* / mgp_posterior_large_* (the same loads and divisions, per neighbourhood).
+ *   A neighbourhood with a scale that is not finite and > 0 (NaN included) gets NaN in mean / var / ykinvy and counts
+ *   once in *info, exactly like a non-positive pivot; the other neighbourhoods of the launch are not affected.
+ *   mgp_posterior_ns_generic_*: the system in LDS; any k up to mgp_max_nn_count(elem_size, R).
+ *   mgp_posterior_ns_large_*: the system in a slab of `workspace`; every k >= 1 with k + 1 + R <= 1024.  Workspace
+ *       contract of mgp_posterior_large_*.
+ *   Order of the checks, all before any HIP call: sizes (MGP_EINVAL), the empty batch (MGP_OK, nothing else looked
+ *   at), pointers (length_scale_batch NULL: MGP_EINVAL), ids and -- the large entry -- the workspace (NULL,
+ *   misaligned, less than one slab: MGP_EINVAL), then MGP_KERNEL_MATERN_GEN, k + 1 + R > 1024 (large) or a system
+ *   that does not fit LDS (generic): MGP_EUNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+int mgp_posterior_ns_generic_f32(const float* feat_q, const float* feat_nn, int d,
+                                 const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                 const float* targets, int R, int targets_batch,
+                                 int noise_mode, double noise_scalar, const float* noise_dev,
+                                 int kernel_id, int metric_id, const float* length_scale_batch, int ls_count,
+                                 float* mean, float* var, float* ykinvy, int* info, void* stream);
+int mgp_posterior_ns_generic_f64(const double* feat_q, const double* feat_nn, int d,
+                                 const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                                 const double* targets, int R, int targets_batch,
+                                 int noise_mode, double noise_scalar, const double* noise_dev,
+                                 int kernel_id, int metric_id, const double* length_scale_batch, int ls_count,
+                                 double* mean, double* var, double* ykinvy, int* info, void* stream);
+int mgp_posterior_ns_large_f32(const float* feat_q, const float* feat_nn, int d,
+                               const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                               const float* targets, int R, int targets_batch,
+                               int noise_mode, double noise_scalar, const float* noise_dev,
+                               int kernel_id, int metric_id, const float* length_scale_batch, int ls_count,
+                               float* mean, float* var, float* ykinvy, int* info,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_posterior_ns_large_f64(const double* feat_q, const double* feat_nn, int d,
+                               const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                               const double* targets, int R, int targets_batch,
+                               int noise_mode, double noise_scalar, const double* noise_dev,
+                               int kernel_id, int metric_id, const double* length_scale_batch, int ls_count,
+                               double* mean, double* var, double* ykinvy, int* info,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Run-time specialisation.  mgp_posterior_* / mgp_loocv_* serve a shape (k, R, d) with a kernel whose
  * loops are compiled for exactly that shape: built into the library for the BASELINE shapes, compiled
  * on first use (hiprtc, ~1 s, cached on disk next to the library) for any other shape with

@@ -101,6 +101,14 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     if type(muygps.kernel).__name__ in ("ShearKernel", "ShearKernel2in3out"):
         raise ValueError("analytic_gradient=True: the shear kernels have no backward kernel; optimise them with "
                          "finite differences (analytic_gradient=False) or Bayes_optimize")
+    # (by the parameter's type, before any name is looked at: the knots of a hierarchical length scale are called
+    # length_scale0 ... like the per-feature scales of Anisotropy, and no backward kernel differentiates them)
+    from muygpys_amd.gp.hyperparameter.experimental import HierarchicalParam
+
+    if isinstance(getattr(getattr(muygps.kernel, "deformation", None), "length_scale", None), HierarchicalParam):
+        raise ValueError("analytic_gradient=True: a hierarchical length scale (a length scale per neighbourhood, "
+                         "length_scale_batch) has no backward kernel; optimise its knot values with finite differences "
+                         "(analytic_gradient=False) or Bayes_optimize")
     ctx = getattr(obj_fn, "loocv_context", None)
     if ctx is None:
         raise ValueError("analytic_gradient=True: the objective was not built by make_loo_crossval_fn")

@@ -35,11 +35,12 @@ template <typename T>
 struct IsoScale {
   T post_scale, inv_l;
 };
+// (`ls`: where the scale is read -- a.length_scale, or the row of a neighbourhood of an NS launch)
 template <typename T, bool BACKWARD>
-__device__ __forceinline__ IsoScale<T> iso_scale(const FusedArgs& a) {
+__device__ __forceinline__ IsoScale<T> iso_scale_at(const FusedArgs& a, const T* ls) {
   IsoScale<T> s{T(1), T(1)};
   if (a.ls_count > 1) return s;
-  const T l = static_cast<const T*>(a.length_scale)[0];
+  const T l = ls[0];
   const bool l2 = a.metric_id == MGP_METRIC_L2;
   if constexpr (BACKWARD) {
     s.inv_l = T(1) / l;
@@ -48,6 +49,50 @@ __device__ __forceinline__ IsoScale<T> iso_scale(const FusedArgs& a) {
     s.post_scale = l2 ? T(1) / l : T(1) / (l * l);
   }
   return s;
+}
+template <typename T, bool BACKWARD>
+__device__ __forceinline__ IsoScale<T> iso_scale(const FusedArgs& a) {
+  return iso_scale_at<T, BACKWARD>(a, static_cast<const T*>(a.length_scale));
+}
+
+// What a per-neighbourhood-scale (NS) instantiation of a workgroup kernel is handed next to FusedArgs: the (b, ls_count)
+// length scales, row nb for the neighbourhood at position nb of the batch (NOT batch_idx[nb]).  FusedArgs::length_scale
+// is not read by such an instantiation; every other instantiation receives no NsLaunch at all.
+struct NsLaunch {
+  const void* ls_batch;
+};
+
+// The scale(s) of neighbourhood nb of an NS launch: row nb of ls_batch, handed to iso_scale_at and pair_distances_at,
+// which read it exactly as they read a launch-wide one (same loads, same divisions: a constant ls_batch gives the bits
+// of the scalar launch).  *bad: whether some scale of the row is not finite and > 0 (NaN included) -- every thread walks
+// the whole row (ls_count uniform loads, next to the (k+1) k / 2 pairs of the neighbourhood), so the answer is uniform
+// across the workgroup without a barrier or LDS.
+template <typename T>
+__device__ __forceinline__ const T* ns_select_scales(const FusedArgs& a, const NsLaunch& n, int64_t nb, bool* bad) {
+  const T* ls = static_cast<const T*>(n.ls_batch) + nb * a.ls_count;
+  bool any = false;
+  for (int c = 0; c < a.ls_count; ++c) {
+    const T l = ls[c];
+    any |= !(l > T(0) && l < num<T>::inf());
+  }
+  *bad = any;
+  return ls;
+}
+
+// ... and what such a neighbourhood returns: NaN in every output it has and one count in info, like a non-positive pivot
+template <typename T>
+__device__ __forceinline__ void ns_refuse_neighbourhood(const FusedArgs& a, int64_t nb, int R, int tid, int NT) {
+  T* mean = static_cast<T*>(a.mean);
+  T* var = static_cast<T*>(a.var);
+  T* yk = static_cast<T*>(a.ykinvy);
+  for (int r = tid; r < R; r += NT) {
+    if (mean) mean[nb * R + r] = num<T>::nan();
+    if (yk) yk[nb * R + r] = num<T>::nan();
+  }
+  if (tid == 0) {
+    if (var) var[nb] = num<T>::nan();
+    if (a.info) atomicAdd(a.info, 1);
+  }
 }
 
 // idx[0 .. k-1]: the neighbours' rows of feat_nn; idx[k]: the query's row of feat_q (batch_idx == NULL: row nb).
@@ -68,16 +113,16 @@ __device__ __forceinline__ void fill_index_list_no_query(int64_t* idx, const Fus
 //   sink(p, row, col, acc, d0, last)     p: pair index; d0: the chunk's first feature; last: no chunk follows
 // by the thread that owns the pair (p = tid, tid + NT, ...: the same thread in every chunk).  Summing over the chunks
 // and turning the last sum into a covariance is the sink's: that is where the kernels differ.  Barriers: the caller's
-// in front (idx written, X and il free), one behind every chunk.
+// in front (idx written, X and il free), one behind every chunk.  `ls`: where the length scale(s) are read, as in
+// iso_scale_at.
 template <typename T, typename Sink>
-__device__ __forceinline__ void pair_distances(const FusedArgs& a, int k, const int64_t* idx, T* X, int XP, T* il, int tid,
-                                               int NT, Sink sink) {
+__device__ __forceinline__ void pair_distances_at(const FusedArgs& a, const T* ls, int k, const int64_t* idx, T* X, int XP, T* il,
+                                                  int tid, int NT, Sink sink) {
   using V = typename lds_vec<T>::type;
   constexpr int E = 16 / (int)sizeof(T);
   const int d = a.d, dc = a.dc;
   const T* feat_q = static_cast<const T*>(a.feat_q);
   const T* feat_nn = static_cast<const T*>(a.feat_nn);
-  const T* ls = static_cast<const T*>(a.length_scale);
   const bool aniso = a.ls_count > 1;
   const bool vec_ok = d % E == 0 && dc % E == 0 && ((uintptr_t)feat_q | (uintptr_t)feat_nn) % 16 == 0;
   const int npairs = (k + 1) * k / 2;
@@ -113,6 +158,11 @@ __device__ __forceinline__ void pair_distances(const FusedArgs& a, int k, const 
     }
     __syncthreads();
   }
+}
+template <typename T, typename Sink>
+__device__ __forceinline__ void pair_distances(const FusedArgs& a, int k, const int64_t* idx, T* X, int XP, T* il, int tid,
+                                               int NT, Sink sink) {
+  pair_distances_at<T>(a, static_cast<const T*>(a.length_scale), k, idx, X, XP, il, tid, NT, sink);
 }
 
 // the noise variance of neighbour r of neighbourhood nb: one scalar, a table by training row, or a (b, k) tensor

@@ -460,6 +460,35 @@ static int posterior_gen_large(const T* fq, const T* fn, int d, const int64_t* b
   return launch_fused_large_gen<T>(a, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses rows > 1024)
 }
 
+// A length scale per neighbourhood (mgp_posterior_ns_*): the NS instantiations of the two workgroup families by name.
+// The checks of posterior_gen (PATH_GENERIC) / posterior_gen_large in their order, `lsb` (b, ls_count) in the place of
+// the launch's length scale(s); the general smoothness is a known id both refuse.
+template <typename T>
+static int posterior_ns(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
+                        int R, int targets_batch, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id,
+                        const T* lsb, int ls_count, T* mean, T* var, T* yk, int* info, void* stream) {
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_MAY_BE_GEN, fq, fn, d, bi, ni, b, k, tg, R,
+                                  noise_mode, eps, nd, kernel_id, metric_id, lsb, ls_count, mean, var, yk, info, nullptr, 0,
+                                  nullptr, 0, targets_batch != 0);
+  if (ready != ARGS_READY) return ready;
+  if (kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
+  return launch_fused_generic_ns<T>(a, lsb, static_cast<hipStream_t>(stream));  // (refuses a system beyond LDS)
+}
+template <typename T>
+static int posterior_ns_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                              const T* tg, int R, int targets_batch, int noise_mode, double eps, const T* nd, int kernel_id,
+                              int metric_id, const T* lsb, int ls_count, T* mean, T* var, T* yk, int* info, void* ws,
+                              int64_t ws_bytes, void* stream) {
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_MAY_BE_GEN, fq, fn, d, bi, ni, b, k, tg, R,
+                                  noise_mode, eps, nd, kernel_id, metric_id, lsb, ls_count, mean, var, yk, info, nullptr, 0,
+                                  nullptr, 0, targets_batch != 0);
+  if (ready != ARGS_READY) return ready;
+  if (!valid_workspace(ws, ws_bytes, sizeof(T), k, R)) return MGP_EINVAL;
+  return launch_fused_large_ns<T>(a, lsb, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses rows > 1024 and the general nu)
+}
+
 template <typename T>
 static int shear_tensor(const T* diffs, int64_t G, int n, int m, int variant, double ls, T* out, void* stream) {
   if (G < 0 || n < 0 || m < 0 || !(ls > 0.0)) return MGP_EINVAL;
@@ -711,6 +740,24 @@ int64_t mgp_large_workspace_bytes(int elem_size, int k, int R, int64_t b) {
   }
 MGP_DEFINE_LARGE(f32, float)
 MGP_DEFINE_LARGE(f64, double)
+
+#define MGP_DEFINE_NS(SUF, T)                                                                                       \
+  int mgp_posterior_ns_generic_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,          \
+                                     int64_t b, int k, const T* tg, int R, int targets_batch, int nm, double eps,    \
+                                     const T* nd, int kid, int mid, const T* lsb, int lsc, T* mean, T* var, T* yk,   \
+                                     int* info, void* st) {                                                          \
+    return posterior_ns<T>(fq, fn, d, bi, ni, b, k, tg, R, targets_batch, nm, eps, nd, kid, mid, lsb, lsc, mean,     \
+                           var, yk, info, st);                                                                       \
+  }                                                                                                                  \
+  int mgp_posterior_ns_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,            \
+                                   int64_t b, int k, const T* tg, int R, int targets_batch, int nm, double eps,      \
+                                   const T* nd, int kid, int mid, const T* lsb, int lsc, T* mean, T* var, T* yk,     \
+                                   int* info, void* workspace, int64_t workspace_bytes, void* st) {                  \
+    return posterior_ns_large<T>(fq, fn, d, bi, ni, b, k, tg, R, targets_batch, nm, eps, nd, kid, mid, lsb, lsc,     \
+                                 mean, var, yk, info, workspace, workspace_bytes, st);                               \
+  }
+MGP_DEFINE_NS(f32, float)
+MGP_DEFINE_NS(f64, double)
 
 int mgp_topk_rows_f32(const float* x, int64_t rows, int cols, int64_t row_stride, int k, float* out_values, int32_t* out_cols,
                       void* st) {

@@ -138,6 +138,11 @@ __device__ __forceinline__ void gen_deriv_strip(T (&v)[gen_pairs_per_call<T>()],
 template <typename T> int launch_fused_generic_gen(const FusedArgs&, hipStream_t);
 template <typename T> int launch_fused_large_gen(const FusedArgs&, void* workspace, int64_t workspace_bytes, hipStream_t);
 int max_nn_count_gen(int elem_size, int R);
+// ... and the per-neighbourhood-scale launches of the same two families (NsLaunch, mgp_assemble.h): closed-form kernels,
+// ls_batch (b, a.ls_count) on the device; MGP_EUNSUPPORTED as the scalar launches of the same family
+template <typename T> int launch_fused_generic_ns(const FusedArgs&, const void* ls_batch, hipStream_t);
+template <typename T>
+int launch_fused_large_ns(const FusedArgs&, const void* ls_batch, void* workspace, int64_t workspace_bytes, hipStream_t);
 // ... and of the hyper-parameter backward on the slab factor (mgp_backward_gen_large.hip): grad_nu (b) may be NULL
 template <typename T> int launch_hyper_backward_gen_large(const BackwardArgs&, void* grad_nu, void* workspace, int64_t workspace_bytes, hipStream_t);
 int backward_gen_large_max_nn_count(int elem_size);

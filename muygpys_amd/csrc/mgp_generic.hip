@@ -21,8 +21,12 @@ namespace mgp {
 // COEFFS (a.coeffs set, no query, no mean / var / yKinvy: the fast-mean precompute): the back-substitution behind the
 // factorisation, K^-1 y_r into a.coeffs (b, k, R).  An instantiation of its own, so that the kernels of every other
 // entry are compiled from what they always were.
-template <typename T, bool GEN, bool COEFFS = false>
-__device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const GenLaunch& g) {
+// NS (per-neighbourhood length scales, `n`: mgp_assemble.h): the scale(s) of neighbourhood nb come from row nb of
+// n.ls_batch, handed to the shared front end in the place of a.length_scale (iso_scale_at, pair_distances_at);
+// closed-form kernels only.  An instantiation of its own again; `ls` is a.length_scale everywhere else.
+template <typename T, bool GEN, bool COEFFS = false, bool NS = false>
+__device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const GenLaunch& g, const NsLaunch& n = NsLaunch{}) {
+  static_assert(!NS || (!GEN && !COEFFS), "per-neighbourhood scales: the closed-form posterior alone");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int k = a.k, R = a.R, dc = a.dc;
   const int rows = k + 1 + R;
@@ -37,7 +41,9 @@ __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const Gen
   const StridedRows<T> row{S, SP};
 
   const int tid = threadIdx.x, NT = blockDim.x;
-  const T post_scale = iso_scale<T, false>(a).post_scale;
+  T post_scale = T(1);
+  if constexpr (!NS) post_scale = iso_scale<T, false>(a).post_scale;
+  const T* ls = static_cast<const T*>(a.length_scale);  // (NS: row nb of n.ls_batch, per neighbourhood)
   if constexpr (GEN) gen_build_node_table<T>(reinterpret_cast<T*>(smem + g.tab), a.smoothness, g, tid);
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
@@ -45,10 +51,21 @@ __device__ __forceinline__ void fused_generic_body(const FusedArgs& a, const Gen
     if constexpr (COEFFS) fill_index_list_no_query(idx, a, nb, k, tid, NT);
     else fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
+    if constexpr (NS) {
+      // a scale that is not finite and > 0: NaN outputs and one count in info, like a non-positive pivot; uniform
+      // across the workgroup, and the other neighbourhoods of the launch see nothing of it
+      bool bad_scale;
+      ls = ns_select_scales<T>(a, n, nb, &bad_scale);
+      if (bad_scale) {
+        ns_refuse_neighbourhood<T>(a, nb, R, tid, NT);
+        continue;
+      }
+      post_scale = iso_scale_at<T, false>(a, ls).post_scale;
+    }
 
     // ---- assemble: squared distances summed over the feature chunks in S, covariances in place in a second pass, the
     // nugget on the diagonal, the responses into the tail rows ----
-    pair_distances<T>(a, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool) {
+    pair_distances_at<T>(a, ls, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool) {
       T* dst = row(r) + c;
       *dst = d0 == 0 ? acc : *dst + acc;
     });
@@ -97,6 +114,9 @@ __global__ void fused_generic_gen_kernel(FusedArgs a, GenLaunch g) { fused_gener
 // ... and its coefficient output (mgp_fast_coefficients_gen_*): GEN x COEFFS, an instantiation of its own as well
 template <typename T>
 __global__ void fused_generic_gen_coeffs_kernel(FusedArgs a, GenLaunch g) { fused_generic_body<T, true, true>(a, g); }
+// ... and the closed-form kernels with a length scale per neighbourhood (mgp_posterior_ns_generic_*)
+template <typename T>
+__global__ void fused_generic_ns_kernel(FusedArgs a, NsLaunch n) { fused_generic_body<T, false, false, true>(a, GenLaunch{}, n); }
 
 // LDS carve: [S: rows*SP T][piv: k T][flag]
 template <typename T>
@@ -195,6 +215,20 @@ int launch_fused_generic(const FusedArgs& a, hipStream_t stream) { return launch
 template <typename T>
 int launch_fused_generic_gen(const FusedArgs& a, hipStream_t stream) { return launch_fused_generic_impl<T, true>(a, stream); }
 
+// per-neighbourhood length scales: the LDS carve, the feature chunk, the threads and the grid of the scalar launch
+template <typename T>
+int launch_fused_generic_ns(const FusedArgs& in, const void* ls_batch, hipStream_t stream) {
+  FusedArgs a = in;
+  if (a.kernel_id == MGP_KERNEL_MATERN_GEN || a.coeffs) return MGP_EUNSUPPORTED;
+  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, a.R, dc); });
+  if (!fc.fits) return MGP_EUNSUPPORTED;
+  a.dc = fc.dc;
+  a.length_scale = nullptr;  // (not read: the scales are the second argument's)
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_generic_ns_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return launch_capacity(&fused_generic_ns_kernel<T>, lds_factor_threads(a.k + 1 + a.R), fc.lds, a.b, Capacity{16}, stream, &label, a,
+                         NsLaunch{ls_batch}).status;
+}
+
 template <typename T>
 int launch_solve_generic(const SolveArgs& a, hipStream_t stream) {
   const size_t lds = solve_lds_bytes<T>(a.k, a.R);
@@ -206,6 +240,8 @@ template int launch_fused_generic<float>(const FusedArgs&, hipStream_t);
 template int launch_fused_generic<double>(const FusedArgs&, hipStream_t);
 template int launch_fused_generic_gen<float>(const FusedArgs&, hipStream_t);
 template int launch_fused_generic_gen<double>(const FusedArgs&, hipStream_t);
+template int launch_fused_generic_ns<float>(const FusedArgs&, const void*, hipStream_t);
+template int launch_fused_generic_ns<double>(const FusedArgs&, const void*, hipStream_t);
 template int launch_solve_generic<float>(const SolveArgs&, hipStream_t);
 template int launch_solve_generic<double>(const SolveArgs&, hipStream_t);
 

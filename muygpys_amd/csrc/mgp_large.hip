@@ -138,8 +138,10 @@ __device__ __forceinline__ void fused_large_gen_body(const FusedArgs& a, T* work
 // dynamic LDS carve (every array 16-byte aligned): [Lb: LNB*LP T][idx: (k+2 & ~1) int64][X: (k+1)*XP T][il: dc T]
 // COEFFS (a.coeffs set, no query, no mean / var / yKinvy: the fast-mean precompute): the back-substitution behind the
 // factorisation, K^-1 y_r into a.coeffs (b, k, R) -- an instantiation of its own, as in mgp_generic.hip.
-template <typename T, bool COEFFS = false>
-__device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspace, int slab_elems) {
+// NS (per-neighbourhood length scales, `n`: mgp_assemble.h): as in mgp_generic.hip, an instantiation of its own.
+template <typename T, bool COEFFS = false, bool NS = false>
+__device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspace, int slab_elems, const NsLaunch& n = NsLaunch{}) {
+  static_assert(!NS || !COEFFS, "per-neighbourhood scales: the posterior alone");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int k_ = a.k, R_ = a.R, dc = a.dc;
   const int XP = tile_row_stride<T>(dc);
@@ -149,7 +151,9 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
   T* il = X + (k_ + 1) * XP;
 
   const int tid = threadIdx.x, NT = blockDim.x;
-  const T post_scale = iso_scale<T, false>(a).post_scale;
+  T post_scale = T(1);
+  if constexpr (!NS) post_scale = iso_scale<T, false>(a).post_scale;
+  const T* ls = static_cast<const T*>(a.length_scale);  // (NS: row nb of n.ls_batch, per neighbourhood)
 
   for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
     __syncthreads();  // previous neighbourhood fully consumed
@@ -160,10 +164,20 @@ __device__ __forceinline__ void fused_large_body(const FusedArgs& a, T* workspac
     if constexpr (COEFFS) fill_index_list_no_query(idx, a, nb, k, tid, NT);
     else fill_index_list(idx, a, nb, k, tid, NT);
     __syncthreads();
+    if constexpr (NS) {
+      // a scale that is not finite and > 0: NaN outputs and one count in info, like a non-positive pivot
+      bool bad_scale;
+      ls = ns_select_scales<T>(a, n, nb, &bad_scale);
+      if (bad_scale) {
+        ns_refuse_neighbourhood<T>(a, nb, R, tid, NT);
+        continue;
+      }
+      post_scale = iso_scale_at<T, false>(a, ls).post_scale;
+    }
 
     // ---- assemble: the chunks' rows are staged in LDS, the partial sums of the squared distances live in the slab,
     // and the last chunk turns a distance into the covariance ----
-    pair_distances<T>(a, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool last) {
+    pair_distances_at<T>(a, ls, k, idx, X, XP, il, tid, NT, [&](int, int r, int c, T acc, int d0, bool last) {
       T* dst = row(r) + c;
       if (d0 > 0) acc += *dst;
       *dst = last ? kernel_eval<T>(a.kernel_id, metric_arg<T>(acc, a.metric_id, post_scale)) : acc;
@@ -196,6 +210,10 @@ __global__ void __launch_bounds__(512) fused_large_kernel(FusedArgs a, T* worksp
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_coeffs_kernel(FusedArgs a, T* workspace, int slab_elems) {
   fused_large_body<T, true>(a, workspace, slab_elems);
+}
+template <typename T>
+__global__ void __launch_bounds__(512) fused_large_ns_kernel(FusedArgs a, T* workspace, int slab_elems, NsLaunch n) {
+  fused_large_body<T, false, true>(a, workspace, slab_elems, n);
 }
 template <typename T>
 __global__ void __launch_bounds__(512) fused_large_gen_kernel(FusedArgs a, T* workspace, int slab_elems, GenLaunch g) {
@@ -312,6 +330,22 @@ int launch_fused_large_gen(const FusedArgs& a, void* workspace, int64_t workspac
   return launch_fused_large_impl<T, true>(a, workspace, workspace_bytes, stream);
 }
 
+// per-neighbourhood length scales: the slab, the LDS carve, the threads and the grid of the scalar launch
+template <typename T>
+int launch_fused_large_ns(const FusedArgs& in, const void* ls_batch, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  FusedArgs a = in;
+  const int64_t rows = (int64_t)a.k + 1 + a.R;
+  if (rows > kLargeMaxRows || a.kernel_id == MGP_KERNEL_MATERN_GEN || a.coeffs) return MGP_EUNSUPPORTED;
+  const int64_t slab = large_slab_bytes(sizeof(T), a.k, a.R);
+  const FeatureChunk fc = feature_chunk(a.d, [&](int dc) { return fused_lds_bytes<T>(a.k, dc); });
+  if (!fc.fits) return MGP_EUNSUPPORTED;
+  a.dc = fc.dc;
+  a.length_scale = nullptr;  // (not read: the scales are the last argument's)
+  const LaunchLabel label(a.b, a.k, a.d, a.R, "mgp::fused_large_ns_kernel<%s>", sizeof(T) == 4 ? "float" : "double");
+  return launch_capacity(&fused_large_ns_kernel<T>, slab_block_threads((int)rows), fc.lds, a.b, Capacity{kMaxPerCu, workspace_bytes / slab},
+                         stream, &label, a, static_cast<T*>(workspace), (int)(slab / (int64_t)sizeof(T)), NsLaunch{ls_batch}).status;
+}
+
 template <typename T>
 int launch_solve_large(const SolveArgs& a, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   const int64_t rows = (int64_t)a.k + 1 + a.R;
@@ -326,6 +360,8 @@ template int launch_fused_large<float>(const FusedArgs&, void*, int64_t, hipStre
 template int launch_fused_large<double>(const FusedArgs&, void*, int64_t, hipStream_t);
 template int launch_fused_large_gen<float>(const FusedArgs&, void*, int64_t, hipStream_t);
 template int launch_fused_large_gen<double>(const FusedArgs&, void*, int64_t, hipStream_t);
+template int launch_fused_large_ns<float>(const FusedArgs&, const void*, void*, int64_t, hipStream_t);
+template int launch_fused_large_ns<double>(const FusedArgs&, const void*, void*, int64_t, hipStream_t);
 template int launch_solve_large<float>(const SolveArgs&, void*, int64_t, hipStream_t);
 template int launch_solve_large<double>(const SolveArgs&, void*, int64_t, hipStream_t);
 

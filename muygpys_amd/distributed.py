@@ -287,6 +287,9 @@ def hip_local_partials(spec, features, targets, batch_indices, nn_indices, packe
     is evaluated afterwards.  ``own_outputs=False`` returns ``mean = var = None`` and the plan's own ``partials``
     buffer (to be consumed before the next evaluation) -- what an optimiser's objective, which only needs the scalar,
     asks for."""
+    from muygpys_amd.fused import refuse_length_scale_batch
+
+    refuse_length_scale_batch(spec)  # (a prepared evaluation carries one scale per launch)
     general = spec.kernel == "matern_gen"
     if general:  # (the general-smoothness model is not on the prepared-evaluation path)
         from muygpys_amd.fused import loocv_partials

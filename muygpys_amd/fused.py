@@ -36,6 +36,11 @@ class KernelSpec:
     noise: scalar -> HomoscedasticNoise; 1-D tensor (n_train,) -> heteroscedastic table
         gathered with nn_indices (tensors/numpy.py:11-15); 2-D tensor (b, k) ->
         already gathered HeteroscedasticNoise tensor (noise/numpy.py:56-67)
+    length_scale_batch: a length scale per neighbourhood, ``(b,)`` / ``(b, 1)`` (Isotropy) or ``(b, d)`` (Anisotropy):
+        the nonstationary model (HierarchicalParameter, gp/hyperparameter/experimental/hierarchical.py; the ``(b,)``
+        scale divides Kin and Kcross of batch element i alike, isotropy.py:60-89).  Row i belongs to the neighbourhood at
+        position i of the batch.  When set, ``length_scale`` is ignored; :func:`posterior_mean_var` alone serves such a
+        spec (closed-form kernels), every other consumer raises ``ValueError``.
     """
 
     kernel: str = "matern15"
@@ -43,6 +48,7 @@ class KernelSpec:
     length_scale: Union[Number, Sequence[Number], torch.Tensor] = 1.0
     noise: Union[Number, torch.Tensor] = 0.0
     smoothness: Optional[float] = None
+    length_scale_batch: Optional[torch.Tensor] = None
 
     def kernel_id(self) -> int:
         try:
@@ -89,6 +95,33 @@ def _length_scale_tensor(ls, d: int, like: torch.Tensor, detach: bool = True) ->
             f"Difference tensor of shape (..., {d}) must have final dimension size of {t.numel()}"
         )
     return t
+
+
+def refuse_length_scale_batch(spec: "KernelSpec") -> None:
+    """What every consumer of a :class:`KernelSpec` but :func:`posterior_mean_var` does with a spec that carries a
+    length scale per neighbourhood: ``ValueError`` -- none may silently use ``length_scale`` instead."""
+    if getattr(spec, "length_scale_batch", None) is not None:
+        raise ValueError("KernelSpec.length_scale_batch (a length scale per neighbourhood) is served by "
+                         "fused.posterior_mean_var alone: no LOOCV launch, gradient, fast-prediction, prepared-table "
+                         "or general-smoothness path reads it")
+
+
+# what a non-zero ``info`` of an NS launch is reported as (``_lib.raise_if_not_spd``): a bad pivot or a bad scale
+NS_NOT_SPD = ("posterior with a length scale per neighbourhood (the other possible cause: a length scale that is not "
+              "positive and finite)")
+
+
+def _length_scale_batch_tensor(lsb, b: int, d: int, like: torch.Tensor) -> torch.Tensor:
+    """``KernelSpec.length_scale_batch`` as the library reads it: ``(b, 1)`` or ``(b, d)``, contiguous, on the tables'
+    device and dtype."""
+    if not isinstance(lsb, torch.Tensor):
+        raise ValueError("length_scale_batch must be a torch.Tensor of shape (b,), (b, 1) or (b, d)")
+    _lib.require_cuda(lsb)
+    t = lsb.detach().to(device=like.device, dtype=like.dtype)
+    t = t[:, None] if t.ndim == 1 else t
+    if t.ndim != 2 or t.shape[0] != b or t.shape[1] not in (1, d):
+        raise ValueError(f"length_scale_batch must have shape ({b},), ({b}, 1) or ({b}, {d}), got {tuple(lsb.shape)}")
+    return t.contiguous()
 
 
 class PackedTable:
@@ -237,14 +270,19 @@ class _Inputs(NamedTuple):
 
 
 def _normalize(spec: KernelSpec, test_features, train_features, batch_indices, nn_indices, targets=None, *,
-               gathered: bool = False, responses: str = "any", want_noise: bool = True, detach: bool = True) -> _Inputs:
+               gathered: bool = False, responses: str = "any", want_noise: bool = True, detach: bool = True,
+               per_neighbourhood: bool = False) -> _Inputs:
     """The one place where the public arguments of a fused function become what the library reads: 2-D contiguous
     tables, int64 indices, the shape and dtype checks, the length scale(s) and the noise triple.  A new model parameter
     is validated and converted here, once.
 
     ``responses``: "any", "single" (the LOOCV losses) or "labels" (two or more columns: classification).
     ``want_noise=False`` / ``detach=False``: the differentiable path decodes its noise tensor inside the autograd
-    function and keeps a length-scale tensor attached to the graph."""
+    function and keeps a length-scale tensor attached to the graph.
+    ``per_neighbourhood``: the caller serves ``spec.length_scale_batch`` (``ls`` is then the ``(b, 1)`` / ``(b, d)``
+    tensor on the tables' device and dtype); every other caller refuses a spec that carries one."""
+    if not per_neighbourhood:
+        refuse_length_scale_batch(spec)
     _lib.require_cuda(test_features, train_features, batch_indices, nn_indices, targets)
     dtype = train_features.dtype
     if test_features.dtype != dtype or (targets is not None and targets.dtype != dtype):
@@ -278,7 +316,10 @@ def _normalize(spec: KernelSpec, test_features, train_features, batch_indices, n
             raise NotImplementedError("the classification losses are defined for two or more response columns")
         if tg.shape[0] != fn.shape[0]:
             raise ValueError("train_features and train_targets differ in row count")
-    ls = _length_scale_tensor(spec.length_scale, d, fn, detach)
+    if spec.length_scale_batch is not None:
+        ls = _length_scale_batch_tensor(spec.length_scale_batch, b, d, fn)
+    else:
+        ls = _length_scale_tensor(spec.length_scale, d, fn, detach)
     mode, eps, nz = _noise_args(spec.noise, b, k, fn) if want_noise else (None, None, None)
     return _Inputs(fq, fn, bi, ni, tg, b, k, d, R, squeeze, ls, mode, eps, nz)
 
@@ -391,7 +432,13 @@ def posterior_mean_var(
     ``gathered``: ``train_targets`` is the already gathered ``(b, k[, R])`` tensor ``targets[nn_indices]``
     (what the reference's ``make_*_tensors`` return) instead of the ``(n[, R])`` table.
     """
-    inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, gathered=gathered)
+    ns = spec.length_scale_batch is not None
+    if ns and spec.kernel == "matern_gen":
+        raise ValueError("length_scale_batch: the general-smoothness Matern has no per-neighbourhood-scale kernel")
+    if ns and path not in ("auto", "generic", "large"):
+        raise ValueError(f"length_scale_batch: path is 'auto', 'generic' or 'large', not {path!r}")
+    inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, gathered=gathered,
+                     per_neighbourhood=ns)
     _debug_check_indices(inp)
     fn, b, R, dtype = inp.fn, inp.b, inp.R, inp.fn.dtype
     mean = out_mean if out_mean is not None else torch.empty((b, R), device=fn.device, dtype=dtype)
@@ -404,15 +451,16 @@ def posterior_mean_var(
         raise ValueError("the general-smoothness Matern goes through the dispatcher (path='auto')")
     if gen and (spec.smoothness is None or not float(spec.smoothness) > 0.0):
         raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
-    if gathered and path not in ("auto", "large") and not (gen and path == "generic"):
+    if gathered and path not in ("auto", "large") and not ((gen or ns) and path == "generic"):
         raise ValueError("gathered responses go through the dispatcher (path='auto') or path='large'")
     # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
     rows = fn.shape[0] + (0 if test_features is train_features else inp.fq.shape[0])
     # the general smoothness beyond the 64 slots of the wave kernels: the workgroup families, plain tables only
     beyond_wave = gen and inp.k + 1 + R > 64
-    use_packed = (path == "auto" and not beyond_wave
+    use_packed = (path == "auto" and not beyond_wave and not ns
                   and _use_packed(packed, inp, train_features, train_targets, rows, gathered))
-    outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info), _lib.stream_ptr())
+    ns_info = torch.zeros(1, device=fn.device, dtype=torch.int32) if ns and info is None else None
+    outs = (_lib.ptr(mean), _lib.ptr(var), _lib.ptr(yk), _lib.ptr(info if ns_info is None else ns_info), _lib.stream_ptr())
 
     def plain():  # the dispatcher on the plain tables, or a closed-form LDS family by name
         call, args = _posterior_call(spec, inp, gathered, path, None, None, outs)
@@ -427,8 +475,15 @@ def posterior_mean_var(
     def family(base="posterior_large", slab=True):  # a workgroup family by name, plain tables: on a slab beyond LDS, or in LDS
         return _posterior_plain(base, inp, _model_args(spec, inp.ls), outs, gathered, slab)
 
+    def ns_family(base, slab):  # a length scale per neighbourhood: (b, ls_count) scales, ls_count per row
+        model = (spec.kernel_id(), spec.metric_id(), _lib.ptr(inp.ls), inp.ls.shape[1])
+        return _posterior_plain(base, inp, model, outs, gathered, slab)
+
     # the ladders: a rung is tried when the one before it answered MGP_EUNSUPPORTED
-    if gen:
+    if ns:  # plain tables, the two workgroup families (own info: a bad scale counts there like a bad pivot)
+        lds, slab = (lambda: ns_family("posterior_ns_generic", False)), (lambda: ns_family("posterior_ns_large", True))
+        rungs = {"auto": (lds, slab), "generic": (lds,), "large": (slab,)}[path]
+    elif gen:
         def gen_slab():  # (more than 1024 rows: refused without a call)
             try:
                 return family("posterior_gen_large")
@@ -452,7 +507,11 @@ def posterior_mean_var(
     rc, _ = _lib.run_ladder(rungs)
     if gen and rc == _lib.EUNSUPPORTED:
         raise FusedUnsupported(f"general-smoothness Matern: no fused kernel for {dtype}, k={inp.k}, R={R}, d={inp.d}")
-    _lib.check(rc, "mgp_posterior_gen" if gen else "mgp_posterior")
+    _lib.check(rc, "mgp_posterior_ns" if ns else "mgp_posterior_gen" if gen else "mgp_posterior")
+    if ns_info is not None and b > 0:
+        # the counter this call owns (a caller that passes ``info=`` looks at its own, as on the scalar path): a
+        # non-positive or non-finite scale counts there like a non-positive pivot
+        _lib.raise_if_not_spd(ns_info, NS_NOT_SPD)
     mean_out = mean.reshape(b) if inp.squeeze else mean.reshape(b, R)
     if want_ykinvy:
         return mean_out, var, (yk.reshape(b) if inp.squeeze else yk)
@@ -1090,6 +1149,7 @@ def fast_posterior_mean(
     _src/gp/muygps/numpy.py:70-77).  Returns ``(b,)`` or ``(b, R)``.  Any ``nn_count``: up to 64 slots one test point per
     32 or 64 lanes, beyond that one test point per wave in passes of 64 neighbours (csrc/mgp_fast_mean.hip);
     :class:`FusedUnsupported` only follows a status the library really returns."""
+    refuse_length_scale_batch(spec)
     _lib.require_cuda(coeffs, closest_neighbor)
     inp = _normalize(spec, test_features, train_features, test_indices, closest_set, want_noise=False)
     fq, fn, bi, ni, b, k, d, ls, dtype = inp.fq, inp.fn, inp.bi, inp.ni, inp.b, inp.k, inp.d, inp.ls, inp.fn.dtype
@@ -1184,6 +1244,7 @@ def fast_coefficients(spec: KernelSpec, train_features: torch.Tensor, train_targ
     from muygpys_amd._src.gp.noise import hip as N
     from muygpys_amd._src.gp.tensors import hip as T
 
+    refuse_length_scale_batch(spec)
     _lib.require_cuda(train_features, train_targets, train_nn_indices)
     nn_fast = T._fast_nn_update(train_nn_indices.to(torch.int64))
     n, k = nn_fast.shape

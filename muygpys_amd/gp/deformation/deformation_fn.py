@@ -16,6 +16,7 @@ import numpy as np
 
 from muygpys_amd import lazy as _lazy
 from muygpys_amd.gp.hyperparameter import NamedParam, NamedVectorParam, ScalarParam, VectorParam
+from muygpys_amd.gp.hyperparameter.experimental import HierarchicalParam, NamedHierarchicalParam
 
 from .metric import MetricFn
 
@@ -42,19 +43,40 @@ class DeformationFn:
         return name
 
 
+def _per_batch(length_scale) -> bool:
+    """A (b,) length scale, one value per batch element (the value of a hierarchical parameter)."""
+    return getattr(length_scale, "ndim", 0) >= 1 and not isinstance(length_scale, (list, tuple))
+
+
+def _along_axis0(length_scale, like):
+    """The (b,) scale shaped to broadcast along axis 0 of ``like`` (isotropy.py:84-88), on its device and dtype."""
+    import torch
+
+    ls = torch.as_tensor(length_scale, device=like.device, dtype=like.dtype).reshape(-1)
+    if ls.shape[0] != like.shape[0]:
+        raise ValueError(f"a length scale per batch element: {ls.shape[0]} values for a batch of {like.shape[0]}")
+    return ls.reshape((-1,) + (1,) * (like.ndim - 1))
+
+
 class Isotropy(DeformationFn):
     def __init__(self, metric: MetricFn, length_scale: ScalarParam):
-        if not isinstance(length_scale, ScalarParam):
+        if isinstance(length_scale, ScalarParam):
+            self.length_scale = NamedParam("length_scale", length_scale)
+        elif isinstance(length_scale, HierarchicalParam):
+            self.length_scale = NamedHierarchicalParam("length_scale", length_scale)
+        else:
             raise ValueError(f"Expected ScalarParam type for length_scale, not {type(length_scale)}")
-        self.length_scale = NamedParam("length_scale", length_scale)
         self.metric = metric
 
     def __call__(self, dists, length_scale: Optional[float] = None, **kwargs):
-        """isotropy.py:60-89: scale distances by the (possibly trial) length scale."""
+        """isotropy.py:60-89: scale distances by the (possibly trial) length scale -- a scalar, or the (b,) values of a
+        hierarchical parameter, which scale batch element i by its own value (broadcast along axis 0)."""
         if length_scale is None:
             length_scale = self.length_scale(**kwargs)
         if isinstance(dists, _lazy.LazyDiffs):
-            return dists.with_length_scale(float(length_scale))
+            return dists.with_length_scale(length_scale if _per_batch(length_scale) else float(length_scale))
+        if _per_batch(length_scale):
+            length_scale = _along_axis0(length_scale, dists)
         return self.metric.apply_length_scale(dists, length_scale)
 
     def pairwise_tensor(self, data, nn_indices, lazy: bool = False, **kwargs):
@@ -80,6 +102,10 @@ class DifferenceIsotropy(Isotropy):
     def __call__(self, dists, length_scale: Optional[float] = None, **kwargs):
         if length_scale is None:
             length_scale = self.length_scale(**kwargs)
+        if _per_batch(length_scale):  # (metric(diffs / l) = metric(diffs) / l or / l^2 for the stock metrics)
+            if isinstance(dists, _lazy.LazyDiffs):
+                return dists.reduce(self._metric_name()).with_length_scale(length_scale)
+            return self.metric(dists / _along_axis0(length_scale, dists))
         if isinstance(dists, _lazy.LazyDiffs):
             return dists.with_length_scale(float(length_scale)).reduce(self._metric_name())
         return self.metric(dists / length_scale)

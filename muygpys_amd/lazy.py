@@ -109,6 +109,7 @@ class LazyDiffs(_Lazy):
       / per-feature scales    (length_scale vector)           Anisotropy.__call__, anisotropy.py:70
       metric: _l2 / _F2       (metric set,   reduced True)    numpy.py:89-94
       / l  or  / l^2          (length_scale scalar)           Isotropy.__call__, metric.py:241,264
+      / l_i  or  / l_i^2      (length_scale_batch, (b,))      a hierarchical length scale, isotropy.py:84-89
     ``reduced``: the handle stands for DISTANCES (b, k[, k]); otherwise for differences (..., d).
     """
 
@@ -121,6 +122,7 @@ class LazyDiffs(_Lazy):
     data_indices: Optional[torch.Tensor] = None
     length_scale: Any = None  # float, or (d,) sequence / tensor
     unit_axis: bool = False  # crosswise differences as (b, k, 1, d): ``diffs[..., None, :]`` of the shear functors
+    length_scale_batch: Optional[torch.Tensor] = None  # (b,) device tensor: one scale per batch element (distances only)
 
     @property
     def shape(self) -> Tuple[int, ...]:
@@ -144,7 +146,16 @@ class LazyDiffs(_Lazy):
         return self.nn_data.device
 
     def with_length_scale(self, length_scale) -> "LazyDiffs":
-        return replace(self, length_scale=length_scale)
+        """A scalar or (d,) length scale -- or, on a DISTANCE handle, a device tensor of b scales, one per batch element
+        (the value of a hierarchical parameter: batch element i is divided by its own scale, isotropy.py:84-89)."""
+        if self.reduced and isinstance(length_scale, torch.Tensor) and length_scale.ndim >= 1 and length_scale.numel() > 1:
+            b = self.nn_indices.shape[0]
+            if length_scale.numel() != b:
+                raise ValueError(f"a length scale per batch element: {length_scale.numel()} values for a batch of {b}")
+            if not length_scale.is_cuda:
+                raise TypeError("hip backend functions take torch tensors on a ROCm device ('cuda'): length scales")
+            return replace(self, length_scale=None, length_scale_batch=length_scale.reshape(-1))
+        return replace(self, length_scale=length_scale, length_scale_batch=None)
 
     def __getitem__(self, item):
         # ``crosswise[..., None, :]``: the unit axis ShearKernel.__call__ inserts (experimental/shear.py:125-128)
@@ -172,7 +183,7 @@ class LazyDiffs(_Lazy):
                 return self.with_length_scale(_as_float(other))
             if n == d and (not isinstance(other, torch.Tensor) or other.ndim == 1):
                 return self.with_length_scale(other)
-        elif self.reduced and self.length_scale is None and _is_scalar_like(other):
+        elif self.reduced and self.length_scale is None and self.length_scale_batch is None and _is_scalar_like(other):
             # distances / l (l2) or / l^2 (F2): metric.py:241,264
             v = _as_float(other)
             return self.with_length_scale(v if self.metric == "l2" else v**0.5)
@@ -210,6 +221,9 @@ class LazyDiffs(_Lazy):
             out = T._pairwise_distances(self.nn_data, self.nn_indices, self.metric)
         else:
             out = T._crosswise_distances(self.data, self.nn_data, self.data_indices, self.nn_indices, self.metric)
+        if self.length_scale_batch is not None:  # batch element i by its own scale: broadcast along axis 0
+            ell = self.length_scale_batch.to(device=out.device, dtype=out.dtype).reshape((-1,) + (1,) * (out.ndim - 1))
+            return out / ell if self.metric == "l2" else out / (ell * ell)
         if self.length_scale is not None:
             ell = _as_float(self.length_scale)
             out = out * (1.0 / ell if self.metric == "l2" else 1.0 / ell**2)
@@ -402,7 +416,16 @@ def fused_triple(Kin, Kcross, nn_targets) -> bool:
         and Kin.smoothness == Kcross.smoothness
         and _same_tensor(a.nn_indices, c.nn_indices) and _same_tensor(a.nn_data, c.nn_data)
         and a.metric == c.metric and a.metric in ("l2", "F2") and _same_ls(a.length_scale, c.length_scale)
+        and _same_ls_batch(a.length_scale_batch, c.length_scale_batch)
     )
+
+
+def _same_ls_batch(x, y) -> bool:
+    """Both handles without per-batch scales, or with the same ones (one tensor, as a hierarchical parameter hands out
+    for one batch and one set of knot values; equal values otherwise)."""
+    if x is None or y is None:
+        return x is None and y is None
+    return _same_tensor(x, y) or (x.shape == y.shape and bool(torch.equal(x, y.to(x.dtype))))
 
 
 def _same_ls(x, y) -> bool:

@@ -70,7 +70,18 @@ def _spec(Kin: lazy.LazyCov):
     return KernelSpec(
         kernel=Kin.kernel, metric=a.metric, length_scale=1.0 if a.length_scale is None else a.length_scale,
         noise=0.0 if Kin.noise is None else Kin.noise, smoothness=Kin.smoothness,
+        length_scale_batch=a.length_scale_batch,
     )
+
+
+def _ns_launch(spec, Kin: lazy.LazyCov, Kcross: lazy.LazyCov, tg, info, gathered: bool):
+    """The one fused launch of a triple whose handles carry a length scale per batch element (the NS ladder of
+    ``fused.posterior_mean_var``: ``mgp_posterior_ns_generic_*``, then ``mgp_posterior_ns_large_*``)."""
+    from .fused import posterior_mean_var
+
+    a, c = Kin.diffs, Kcross.diffs
+    return posterior_mean_var(spec, c.data, a.nn_data, c.data_indices, a.nn_indices, tg, want_ykinvy=True, info=info,
+                              gathered=gathered)
 
 
 def fused(Kin: lazy.LazyCov, Kcross: lazy.LazyCov, nn_targets, differentiable: Optional[bool] = None):
@@ -104,6 +115,9 @@ def fused(Kin: lazy.LazyCov, Kcross: lazy.LazyCov, nn_targets, differentiable: O
     spec = _spec(Kin)
     if differentiable and Kin.kernel == "matern_gen":
         return None  # (the backward kernels know the closed-form kernels only)
+    ns = spec.length_scale_batch is not None
+    if ns and Kin.kernel == "matern_gen":
+        return None  # (no fused kernel with per-neighbourhood scales for the general smoothness: materialise)
     if differentiable:
         from .autograd import posterior
 
@@ -113,13 +127,18 @@ def fused(Kin: lazy.LazyCov, Kcross: lazy.LazyCov, nn_targets, differentiable: O
         return value
     info = torch.zeros(1, dtype=torch.int32, device=a.device)
     try:
-        value = posterior_mean_var(
-            spec, c.data, a.nn_data, c.data_indices, a.nn_indices, tg, want_ykinvy=True, info=info, gathered=gathered,
-        ) + (info,)
+        if ns:
+            value = _ns_launch(spec, Kin, Kcross, tg, info, gathered) + (info,)
+        else:
+            value = posterior_mean_var(
+                spec, c.data, a.nn_data, c.data_indices, a.nn_indices, tg, want_ykinvy=True, info=info, gathered=gathered,
+            ) + (info,)
     except FusedUnsupported:
         Kin.cache["unsupported"] = True  # (shared by the decorated copies of this Kin: asked once)
         return None
-    _lib.raise_if_not_spd(info, "fused posterior")
+    from .fused import NS_NOT_SPD
+
+    _lib.raise_if_not_spd(info, "fused " + NS_NOT_SPD if ns else "fused posterior")
     # one evaluation at a time: the hyper-parameters changed -> older plain entries are dead
     Kin.cache["entries"] = [e for e in _entries(Kin) if e.differentiable]
     _entries(Kin).append(_Entry(nk, c, tg, False, value))
@@ -178,7 +197,7 @@ def analytic_scale(Kin: lazy.LazyCov, nn_targets):
         # dropped, y^T K^-1 y does not depend on the query at all
         stand_in = lazy.LazyCov(
             lazy.LazyDiffs("crosswise", a.metric, True, a.nn_data, a.nn_indices, a.nn_data,
-                           a.nn_indices[:, 0].contiguous(), a.length_scale),
+                           a.nn_indices[:, 0].contiguous(), a.length_scale, length_scale_batch=a.length_scale_batch),
             Kin.kernel, smoothness=Kin.smoothness,
         )
         out = fused(Kin, stand_in, nn_targets, differentiable=False)
@@ -231,7 +250,7 @@ def fast_mean(Kcross: lazy.LazyCov, coeffs: torch.Tensor, rows: Optional[torch.T
     elif tuple(rows.shape) != (b,):
         return None
     spec = KernelSpec(Kcross.kernel, c.metric, 1.0 if c.length_scale is None else c.length_scale, 0.0,
-                      Kcross.smoothness if gen else None)
+                      Kcross.smoothness if gen else None, length_scale_batch=c.length_scale_batch)
     try:
         out = fast_posterior_mean(spec, c.data, c.nn_data, c.data_indices, c.nn_indices, coeffs, rows)
     except FusedUnsupported:
