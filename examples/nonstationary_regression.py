@@ -3,10 +3,13 @@
 experimental/nonstationary_tutorial.ipynb) on the hip backend: a 1-D curve that oscillates fast on the left and slowly
 on the right, a handful of knots whose values are the length scale there, k-NN, L-BFGS-B over the knot values, prediction.
 
-    python examples/nonstationary_regression.py          # needs a ROCm device
+    python examples/nonstationary_regression.py                       # needs a ROCm device
+    python examples/nonstationary_regression.py --analytic-gradient   # the knots by the NS backward kernels
 
 The length scale of every neighbourhood is the posterior mean of a small higher-level GP over the knots, evaluated at
 the batch element's features; the whole posterior is ONE fused launch with a length scale per neighbourhood.
+``--analytic-gradient``: L-BFGS-B takes the gradient with respect to the knot values from one NS forward, one NS
+backward launch and the pullback through the knot GP, instead of knot_count + 1 forward evaluations per iteration.
 """
 
 import os
@@ -35,7 +38,8 @@ def curve(x, rng, noise):
     return np.sin(2 * np.pi * (1.0 + 7.0 * (1.0 - x) ** 2) * x) + np.sqrt(noise) * rng.standard_normal(x.shape)
 
 
-def run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, batch_count=300, verbose=True):
+def run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, batch_count=300, verbose=True,
+        analytic_gradient=False):
     rng = np.random.default_rng(seed)
     x = np.linspace(0.0, 1.0, n)
     y = curve(x, rng, noise)
@@ -65,7 +69,8 @@ def run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, bat
     batch_nn, _ = nbrs.get_batch_nns(batch_idx)
     cross, pair, y_b, y_nn = muygps.make_train_tensors(batch_idx, batch_nn, Xtr, ytr)
     batch_features = batch_features_tensor(Xtr, batch_idx)
-    muygps = L_BFGS_B_optimize(muygps, y_b, y_nn, cross, pair, batch_features=batch_features, loss_fn=lool_fn)
+    muygps = L_BFGS_B_optimize(muygps, y_b, y_nn, cross, pair, batch_features=batch_features, loss_fn=lool_fn,
+                               analytic_gradient="knots" if analytic_gradient else False)
     opt_fn = muygps.scale.get_opt_fn(muygps)
     muygps.scale._set(opt_fn(muygps.kernel(pair, batch_features=batch_features), y_nn))
     muygps._make()
@@ -89,4 +94,4 @@ def run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, bat
 
 
 if __name__ == "__main__":
-    run()
+    run(analytic_gradient="--analytic-gradient" in sys.argv[1:])

@@ -992,6 +992,45 @@ int mgp_hyper_backward_large_f64(const double* features, int d, const int64_t* b
                                  const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
                                  double* grad_ls, double* grad_noise, int* info,
                                  void* workspace, int64_t workspace_bytes, void* stream);
+/* The same with a length scale per neighbourhood (the nonstationary model of mgp_posterior_ns_*): `length_scale_batch` is
+ * the device (b, ls_count) tensor, row nb for the neighbourhood at POSITION nb, and grad_ls (b, ls_count) keeps its rows
+ * apart -- row nb is d loss / d (the scales of neighbourhood nb), the quantity the chain to a hierarchical parameter's
+ * knots starts from.  grad_ykinvy may be NULL (the posterior form, any R); no feature or response cotangents.
+ *   mgp_hyper_backward_ns_*: the wave-sized kernel (Isotropy, k + 2 <= 64, the shapes of mgp_posterior_backward_*'s wave
+ *       rung), the LDS workgroup kernel behind it ((b, d) scales, up to mgp_max_nn_count_backward); MGP_EUNSUPPORTED
+ *       beyond LDS.
+ *   mgp_hyper_backward_ns_large_*: the slab factor, k + 2 <= 1024, workspace contract of mgp_hyper_backward_large_*.
+ *   With every row equal, the LDS kernel and the slab kernel return the bits of the scalar launch of their family.
+ *   A neighbourhood whose row holds a scale that is not finite and > 0 (NaN included) gets NaN in its grad_ls and
+ *   grad_noise rows and counts once in *info; nothing else of it is written, no other neighbourhood is touched.
+ *   Checks in the order of mgp_hyper_backward_large_* (length_scale_batch NULL: MGP_EINVAL); then
+ *   MGP_KERNEL_MATERN_GEN or a system the family cannot hold: MGP_EUNSUPPORTED. */
+int mgp_hyper_backward_ns_f32(const float* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                              int64_t b, int k, const float* targets, int R,
+                              int noise_mode, double noise_scalar, const float* noise_dev,
+                              int kernel_id, int metric_id, const float* length_scale_batch, int ls_count,
+                              const float* grad_mean, const float* grad_var, const float* grad_ykinvy,
+                              float* grad_ls, float* grad_noise, int* info, void* stream);
+int mgp_hyper_backward_ns_f64(const double* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                              int64_t b, int k, const double* targets, int R,
+                              int noise_mode, double noise_scalar, const double* noise_dev,
+                              int kernel_id, int metric_id, const double* length_scale_batch, int ls_count,
+                              const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
+                              double* grad_ls, double* grad_noise, int* info, void* stream);
+int mgp_hyper_backward_ns_large_f32(const float* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                    int64_t b, int k, const float* targets, int R,
+                                    int noise_mode, double noise_scalar, const float* noise_dev,
+                                    int kernel_id, int metric_id, const float* length_scale_batch, int ls_count,
+                                    const float* grad_mean, const float* grad_var, const float* grad_ykinvy,
+                                    float* grad_ls, float* grad_noise, int* info,
+                                    void* workspace, int64_t workspace_bytes, void* stream);
+int mgp_hyper_backward_ns_large_f64(const double* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                    int64_t b, int k, const double* targets, int R,
+                                    int noise_mode, double noise_scalar, const double* noise_dev,
+                                    int kernel_id, int metric_id, const double* length_scale_batch, int ls_count,
+                                    const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
+                                    double* grad_ls, double* grad_noise, int* info,
+                                    void* workspace, int64_t workspace_bytes, void* stream);
 /* The same for the general-smoothness Matern (K3, _src/gp/kernels/numpy.py:34-43; `smoothness` = nu in place of a
  * kernel id, as mgp_posterior_gen_large_*), with the partial with respect to nu as a third output: what lets
  * L-BFGS-B optimise a free smoothness on one extra launch per iteration instead of p + 1 forward evaluations.  Serves

@@ -69,7 +69,7 @@ def _get_opt_lists(muygps, verbose: bool = False):
     return x0_names, np.asarray(x0, dtype=np.float64), np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
 
 
-def _analytic_value_and_grad(muygps, obj_fn, x0_names):
+def _analytic_value_and_grad(muygps, obj_fn, x0_names, knots: bool = False):
     """``x -> (loss, d loss / d x)`` for scipy's ``jac=True``: one fused LOOCV evaluation and one backward launch
     (``muygpys_amd.fused.loocv_value_and_grad``) instead of ``len(x) + 1`` evaluations per iteration.  The objective
     must be what ``make_loo_crossval_fn`` builds on lazy handles (``obj_fn.loocv_context``); the loss any of
@@ -92,7 +92,13 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
     The sigma^2 inside ``lool`` / ``looph`` is whatever the objective was built with, and the gradient follows it: the
     closed form of ``AnalyticScale`` (any ``iteration_count``: the fixed-point passes are scalar algebra on the first
     value and are differentiated as such) or the constant of ``FixedScale`` / a plain ``ScaleFn`` (no cotangent through
-    ``y^T K^-1 y``).  A ``scale_fn`` that is neither of the two closures ``ScaleFn.get_opt_fn`` returns is refused."""
+    ``y^T K^-1 y``).  A ``scale_fn`` that is neither of the two closures ``ScaleFn.get_opt_fn`` returns is refused.
+
+    ``knots`` (``analytic_gradient="knots"``): the model's length scale is a hierarchical parameter of ``Isotropy``; the
+    optimiser's names ``<name>0 ... <name>{K-1}`` take the pullback of the per-neighbourhood partials
+    (``fused.loocv_value_and_grad`` with ``length_scale_batch``, ``NamedHierarchicalParameter.pullback``), the
+    homoscedastic noise the summed noise gradient; ``batch_features=`` is required, as for the objective.  With
+    ``analytic_gradient=True`` such a model raises as it always has."""
     from muygpys_amd import distributed as D
     from muygpys_amd import lazy, lazy_eval
     from muygpys_amd.fused import class_value_and_grad, loocv_value_and_grad
@@ -102,14 +108,28 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
         raise ValueError("analytic_gradient=True: the shear kernels have no backward kernel; optimise them with "
                          "finite differences (analytic_gradient=False) or Bayes_optimize")
     # (by the parameter's type, before any name is looked at: the knots of a hierarchical length scale are called
-    # length_scale0 ... like the per-feature scales of Anisotropy, and no backward kernel differentiates them)
+    # length_scale0 ... like the per-feature scales of Anisotropy; their gradient is the pullback of the
+    # per-neighbourhood partials of the NS backward kernels through the knot GP)
     from muygpys_amd.gp.hyperparameter.experimental import HierarchicalParam
 
-    if isinstance(getattr(getattr(muygps.kernel, "deformation", None), "length_scale", None), HierarchicalParam):
+    hier = getattr(getattr(muygps.kernel, "deformation", None), "length_scale", None)
+    hier = hier if isinstance(hier, HierarchicalParam) else None
+    if hier is not None and not knots:
+        # (what analytic_gradient=True has always answered for such a model stays: the knot gradient is asked for by name)
         raise ValueError("analytic_gradient=True: a hierarchical length scale (a length scale per neighbourhood, "
-                         "length_scale_batch) has no backward kernel; optimise its knot values with finite differences "
-                         "(analytic_gradient=False) or Bayes_optimize")
+                         "length_scale_batch) is differentiated on request -- analytic_gradient='knots' pulls the "
+                         "per-neighbourhood partials of the NS backward kernels back to its knot values; otherwise "
+                         "optimise them with finite differences (analytic_gradient=False) or Bayes_optimize")
+    if knots and hier is None:
+        raise ValueError("analytic_gradient='knots': the model has no hierarchical length scale")
+    if isinstance(getattr(muygps.kernel, "smoothness", None), HierarchicalParam) or isinstance(muygps.noise, HierarchicalParam):
+        raise ValueError("analytic_gradient=True: a hierarchical parameter is differentiated as the length scale of "
+                         "Isotropy alone, not as a smoothness or a noise")
     ctx = getattr(obj_fn, "loocv_context", None)
+    batch_features = None if ctx is None else ctx.get("batch_features")
+    if hier is not None and batch_features is None:
+        raise ValueError("analytic_gradient='knots': a hierarchical length scale needs batch_features= (the features of the "
+                         "batch elements, gp.tensors.batch_features_tensor), as the objective does")
     if ctx is None:
         raise ValueError("analytic_gradient=True: the objective was not built by make_loo_crossval_fn")
     loss = {id(lool_fn): "lool", id(mse_fn): "mse", id(pseudo_huber_fn): "pseudo_huber", id(looph_fn): "looph",
@@ -160,6 +180,8 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
 
     def value_and_grad(x_array, *args):
         hyper = {h: float(x_array[i]) for i, h in enumerate(x0_names) if i != noise_at}
+        if hier is not None:
+            hyper["batch_features"] = batch_features
         Kin = ctx["kernel_fn"](pair, **hyper)
         if not isinstance(Kin, lazy.LazyCov):
             raise ValueError("analytic_gradient=True: the kernel did not stay a lazy handle")
@@ -180,6 +202,11 @@ def _analytic_value_and_grad(muygps, obj_fn, x0_names):
                                                                scale=scale_mode, boundary_scale=boundary_scale,
                                                                sigma_noise=stored if noise_at is not None else None,
                                                                **free_nu)
+        if hier is not None:
+            # (b, 1) partials, one per neighbourhood, on the device -> the knots: d loss / d knot values
+            if spec.length_scale_batch is None:
+                raise ValueError("analytic_gradient='knots': the hierarchical length scale did not reach the lazy handle")
+            g_ls = hier.pullback(batch_features, g_ls)
         grad = [g_noise if j == noise_at else g_nu[0] if j == nu_at else g_ls[index[j]] for j in range(len(x0_names))]
         return value, np.array(grad, dtype=np.float64)
 
@@ -211,13 +238,16 @@ def _scipy_optimize(muygps, obj_fn: Callable, verbose: bool = False, analytic_gr
     """numpy.py:57-81.  ``analytic_gradient`` (round 5, opt-in; default: the reference's finite differences, the same
     trajectory as the reference's): hand scipy the analytic gradient of the LOOCV loss -- for every
     nn_count the forward serves: beyond ``mgp_max_nn_count_backward`` the gradient comes from the backward on the slab
-    factor (``mgp_hyper_backward_large_*``), up to nn_count = 1022; ``ValueError`` beyond."""
+    factor (``mgp_hyper_backward_large_*``), up to nn_count = 1022; ``ValueError`` beyond.  ``analytic_gradient="knots"``:
+    the same for a model whose length scale is a hierarchical parameter, with respect to its knot values."""
     from scipy import optimize as opt
 
     x0_names, x0, bounds = _get_opt_lists(muygps, verbose=verbose)
     if analytic_gradient:
-        optres = opt.minimize(_analytic_value_and_grad(muygps, obj_fn, x0_names), x0, jac=True, method="L-BFGS-B",
-                              bounds=bounds, **kwargs)
+        if analytic_gradient is not True and analytic_gradient != "knots":
+            raise ValueError(f"analytic_gradient is False, True or 'knots', not {analytic_gradient!r}")
+        value_and_grad = _analytic_value_and_grad(muygps, obj_fn, x0_names, knots=analytic_gradient == "knots")
+        optres = opt.minimize(value_and_grad, x0, jac=True, method="L-BFGS-B", bounds=bounds, **kwargs)
     else:
         optres = opt.minimize(_obj_fn_adapter(obj_fn, x0_names), x0, method="L-BFGS-B", bounds=bounds, **kwargs)
     if verbose:

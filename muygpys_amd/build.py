@@ -75,6 +75,16 @@ PER_FILE_FLAGS = {
     # (... and the prediction kernels of the fast posterior mean, closed-form and general-smoothness:
     # tests/test_fast_gen_cpu.py compares the closed-form records with the ones from before the general ones existed)
     "mgp_fast_mean.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the hyper-parameter backwards with a length scale per neighbourhood, translation units of their own with
+    # the flags of the scalar kernels whose bodies they instantiate -- mgp_backward.hip, mgp_backward_large.hip: at
+    # constant scales they return those kernels' bits, which holds only under the same instruction selection;
+    # tests/test_hyper_backward_ns_status_cpu.py reads their records)
+    "mgp_backward_ns.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"],
+    "mgp_backward_large_ns.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and the wave-sized one, a kernel of its own: the compiler is told not to select packed fp32 instructions for
+    # it, and it contains no hand-written ones)
+    **{f: ["-mllvm", "-pragma-unroll-threshold=1000000", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
+           "-Rpass-analysis=kernel-resource-usage"] for f in ("mgp_backward_wave_ns.hip", "mgp_backward_wave_ns_f32.hip")},
 }
 
 

@@ -95,6 +95,19 @@ __device__ __forceinline__ void ns_refuse_neighbourhood(const FusedArgs& a, int6
   }
 }
 
+// ... and in an NS hyper-parameter backward (BackwardArgs): NaN in the neighbourhood's grad_ls row (ls_count values) and
+// grad_noise row (k values), one count in info; nothing else of it is written
+template <typename T>
+__device__ __forceinline__ void ns_refuse_backward(const BackwardArgs& g, int64_t nb, int tid, int NT) {
+  T* gls = static_cast<T*>(g.grad_ls);
+  T* gnz = static_cast<T*>(g.grad_noise);
+  if (gls)
+    for (int c = tid; c < g.f.ls_count; c += NT) gls[nb * (int64_t)g.f.ls_count + c] = num<T>::nan();
+  if (gnz)
+    for (int r = tid; r < g.f.k; r += NT) gnz[nb * (int64_t)g.f.k + r] = num<T>::nan();
+  if (tid == 0 && g.f.info) atomicAdd(g.f.info, 1);
+}
+
 // idx[0 .. k-1]: the neighbours' rows of feat_nn; idx[k]: the query's row of feat_q (batch_idx == NULL: row nb).
 // Visible behind the caller's barrier.
 __device__ __forceinline__ void fill_index_list(int64_t* idx, const FusedArgs& a, int64_t nb, int k, int tid, int NT) {

@@ -29,91 +29,7 @@ namespace mgp {
 
 template <typename T>
 __global__ void __launch_bounds__(512) hyper_backward_large_kernel(BackwardArgs g, T* workspace, int slab_elems, int factor_elems) {
-  constexpr int E = 16 / (int)sizeof(T);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const FusedArgs& a = g.f;
-  const int k_ = a.k, d = a.d, dc = a.dc;
-  const BackwardLargeLds<T> s = backward_large_carve<T>(smem, k_, dc);
-  T *av = s.av, *wv = s.wv;
-
-  const T* feat = static_cast<const T*>(a.feat_nn);
-  const T* ls = static_cast<const T*>(a.length_scale);
-  const T* gmean = static_cast<const T*>(g.grad_mean);
-  const T* gvar = static_cast<const T*>(g.grad_var);
-  const T* gyk = static_cast<const T*>(g.grad_yk);
-  T* gls = static_cast<T*>(g.grad_ls);
-  T* gnz = static_cast<T*>(g.grad_noise);
-  const int tid = threadIdx.x, NT = blockDim.x;
-  const bool aniso = a.ls_count > 1;
-  const bool l2 = a.metric_id == MGP_METRIC_L2;
-  const bool vec_ok = d % E == 0 && dc % E == 0 && (uintptr_t)feat % 16 == 0;
-  // the distances are read again by the next feature chunk and by the length-scale cotangents: a grad_noise-only call
-  // whose features fit one chunk stores none
-  const bool keep_acc = gls != nullptr || d > dc;
-
-  const IsoScale<T> iso = iso_scale<T, true>(a);
-  const T post_scale = iso.post_scale, inv_l = iso.inv_l;
-
-  for (int64_t nb = blockIdx.x; nb < a.b; nb += gridDim.x) {
-    __syncthreads();  // previous neighbourhood fully consumed
-    int k = k_;
-    asm volatile("" : "+s"(k));
-    const int rows = k + 2;
-    const int npairs = (k + 1) * k / 2;
-    T* slab = workspace + (int64_t)blockIdx.x * slab_elems;
-    const SlabRows<T> row{slab, k};
-    T* Dst = slab + factor_elems;
-
-    // ---- 1. squared distances (kept in Dst), covariances, nugget, the two tail rows ----
-    backward_large_assemble<T>(a, gmean, gyk, keep_acc, post_scale, nb, k, row, Dst, s, tid, NT);
-
-    // ---- 2. factorisation; rows k, k + 1 then hold z = L^-1 c and zy = L^-1 yt ----
-    const bool bad = factor_augmented_slab<T>(row, k, rows, s.Lb, tid, NT);
-    if (bad) {  // uniform
-      if (tid == 0 && a.info) atomicAdd(a.info, 1);
-      continue;  // the partials of a non-SPD neighbourhood are left untouched
-    }
-
-    // ---- 3. back-substitution of both tail rows, in LDS ----
-    backward_large_solve_tails<T>(row, k, av, wv, tid, NT);
-
-    // ---- 4. cotangents: a = K^-1 c in av, w = K^-1 yt in wv ----
-    const T gv = gvar ? gvar[nb] : T(0);
-    const T gyv = gyk ? gyk[nb] : T(0);
-    const T gm1 = gyk ? (gmean ? gmean[nb] : T(0)) : T(1);
-    if (gls) {
-      T liso = T(0);
-      for (int p = tid; p < npairs; p += NT) {
-        int a_, c_;
-        tri_decode(p, a_, c_);
-        const T gK = pair_cotangent<T>(av, wv, a_, c_, k, gv, gm1, gyv);
-        const T x = metric_arg<T>(Dst[p], a.metric_id, post_scale);
-        const T kp = kernel_deriv<T>(a.kernel_id, x);
-        if (aniso) {
-          Dst[p] = gK * dk_dacc<T>(x, kp, post_scale, l2);
-        } else {
-          liso += gK * kp * x;
-        }
-      }
-      if (!aniso) {
-        const T total = block_sum_ordered<T>(liso, s.red, tid, NT);
-        if (tid == 0) gls[nb] = -(l2 ? T(1) : T(2)) * inv_l * total;  // dx/dl = -x/l | -2x/l
-      }
-    }
-    if (gnz)
-      for (int r = tid; r < k; r += NT) gnz[nb * k + r] = noise_cotangent<T>(av[r], wv[r], gv, gm1, gyv);
-    if (!(gls && aniso)) continue;  // uniform
-
-    // ---- 5. Anisotropy: grad_ls[c] = -2 / l_c^3 sum_pairs q_ij (x_ic - x_jc)^2 ----
-    for (int d0 = 0; d0 < d; d0 += dc) {
-      const int w = min(dc, d - d0);
-      const int wp = (w + E - 1) / E * E;
-      __syncthreads();  // q is in the triangle; the previous chunk's rows are consumed
-      gather_tile_lds<T>(s.X, s.XP, feat, feat, s.idx, k, d, d0, w, wp, vec_ok, tid, NT);
-      __syncthreads();
-      backward_large_ls_chunk<T>(Dst, s.X, s.XP, s.red, ls + d0, gls + nb * (int64_t)a.ls_count + d0, w, wp, npairs, tid, NT);
-    }
-  }
+  hyper_backward_large_body<T, false>(g, workspace, slab_elems, factor_elems, NsLaunch{});
 }
 
 // the factor trapezoid with two tail rows, then the triangle of the (k+1)-point set: whole 256-byte lines each

@@ -360,6 +360,52 @@ int hyper_backward_large(const T* feat, int d, const int64_t* bi, const int64_t*
   return launch_hyper_backward_large<T>(g, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024 and the general nu)
 }
 
+// ... with a length scale per neighbourhood (mgp_hyper_backward_ns_*, mgp_hyper_backward_ns_large_*): the checks of
+// hyper_backward_large in its order, `lsb` (b, ls_count) in the place of the launch's length scale(s).  The entry
+// without a workspace chains the wave-sized kernel and the LDS workgroup kernel as posterior_backward does
+// (MGP_BACKWARD_LDS: the LDS rung alone, A/B timing); the general smoothness is a known id the launchers refuse.
+template <typename T>
+static int hyper_backward_ns_args(BackwardArgs& g, const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                                  const T* tg, int R, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id,
+                                  const T* lsb, int ls_count, const T* gmean, const T* gvar, const T* gyk, T* gls, T* gnz, int* info) {
+  g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES | KERNEL_MAY_BE_GEN, feat, feat, d, bi, ni, b, k, tg, R, noise_mode,
+                                  eps, nd, kernel_id, metric_id, lsb, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (gyk && R != 1) return MGP_EINVAL;  // (the LOOCV losses are defined for one response)
+  if ((!gmean && !gvar && !gyk) || (!gls && !gnz)) return MGP_EINVAL;
+  g.grad_mean = gmean, g.grad_var = gvar, g.grad_yk = gyk, g.grad_ls = gls, g.grad_noise = gnz;
+  return ARGS_READY;
+}
+template <typename T>
+static int hyper_backward_ns(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg, int R,
+                             int noise_mode, double eps, const T* nd, int kernel_id, int metric_id, const T* lsb, int ls_count,
+                             const T* gmean, const T* gvar, const T* gyk, T* gls, T* gnz, int* info, void* stream) {
+  BackwardArgs g;
+  const int ready = hyper_backward_ns_args<T>(g, feat, d, bi, ni, b, k, tg, R, noise_mode, eps, nd, kernel_id, metric_id, lsb,
+                                              ls_count, gmean, gvar, gyk, gls, gnz, info);
+  if (ready != ARGS_READY) return ready;
+  static const bool lds_only = getenv("MGP_BACKWARD_LDS") != nullptr;  // A/B switch (timing only)
+  if (!lds_only && kernel_id != MGP_KERNEL_MATERN_GEN) {
+    const int rc = launch_backward_wave_ns<T>(g, lsb, static_cast<hipStream_t>(stream));
+    if (rc != MGP_EUNSUPPORTED) return rc;
+  }
+  return launch_backward_ns<T>(g, lsb, static_cast<hipStream_t>(stream));  // (refuses a system beyond LDS)
+}
+template <typename T>
+static int hyper_backward_ns_large(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
+                                   int R, int noise_mode, double eps, const T* nd, int kernel_id, int metric_id, const T* lsb,
+                                   int ls_count, const T* gmean, const T* gvar, const T* gyk, T* gls, T* gnz, int* info,
+                                   void* ws, int64_t ws_bytes, void* stream) {
+  BackwardArgs g;
+  const int ready = hyper_backward_ns_args<T>(g, feat, d, bi, ni, b, k, tg, R, noise_mode, eps, nd, kernel_id, metric_id, lsb,
+                                              ls_count, gmean, gvar, gyk, gls, gnz, info);
+  if (ready != ARGS_READY) return ready;
+  if (!ws || reinterpret_cast<uintptr_t>(ws) % 16 != 0 || ws_bytes < backward_large_slab_bytes(sizeof(T), k))
+    return MGP_EINVAL;
+  return launch_hyper_backward_large_ns<T>(g, lsb, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024 and the general nu)
+}
+
 // ... of the general-smoothness Matern (mgp_backward_gen_large.hip): the same checks in the same order, the smoothness
 // sign with the sizes (in front of the empty-batch return), its limit with the shapes beyond the kernel; grad_nu is a
 // third output
@@ -923,6 +969,24 @@ int64_t mgp_backward_large_workspace_bytes(int elem_size, int k, int64_t b) {
   }
 MGP_DEFINE_BWD_LARGE(f32, float)
 MGP_DEFINE_BWD_LARGE(f64, double)
+#define MGP_DEFINE_BWD_NS(SUF, T)                                                                                   \
+  int mgp_hyper_backward_ns_##SUF(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,      \
+                                  const T* tg, int R, int nm, double eps, const T* nd, int kid, int mid,             \
+                                  const T* lsb, int lsc, const T* gmean, const T* gvar, const T* gyk, T* gls,        \
+                                  T* gnz, int* info, void* st) {                                                     \
+    return hyper_backward_ns<T>(feat, d, bi, ni, b, k, tg, R, nm, eps, nd, kid, mid, lsb, lsc, gmean, gvar, gyk,     \
+                                gls, gnz, info, st);                                                                 \
+  }                                                                                                                  \
+  int mgp_hyper_backward_ns_large_##SUF(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b,       \
+                                        int k, const T* tg, int R, int nm, double eps, const T* nd, int kid,         \
+                                        int mid, const T* lsb, int lsc, const T* gmean, const T* gvar,               \
+                                        const T* gyk, T* gls, T* gnz, int* info, void* workspace,                    \
+                                        int64_t workspace_bytes, void* st) {                                         \
+    return hyper_backward_ns_large<T>(feat, d, bi, ni, b, k, tg, R, nm, eps, nd, kid, mid, lsb, lsc, gmean, gvar,    \
+                                      gyk, gls, gnz, info, workspace, workspace_bytes, st);                          \
+  }
+MGP_DEFINE_BWD_NS(f32, float)
+MGP_DEFINE_BWD_NS(f64, double)
 int mgp_backward_gen_large_max_nn_count(int elem_size) {
   if (elem_size != 4 && elem_size != 8) return MGP_EINVAL;
   return backward_gen_large_max_nn_count(elem_size);

@@ -102,8 +102,8 @@ def refuse_length_scale_batch(spec: "KernelSpec") -> None:
     length scale per neighbourhood: ``ValueError`` -- none may silently use ``length_scale`` instead."""
     if getattr(spec, "length_scale_batch", None) is not None:
         raise ValueError("KernelSpec.length_scale_batch (a length scale per neighbourhood) is served by "
-                         "fused.posterior_mean_var alone: no LOOCV launch, gradient, fast-prediction, prepared-table "
-                         "or general-smoothness path reads it")
+                         "fused.posterior_mean_var and fused.loocv_value_and_grad alone: no LOOCV plan, classification "
+                         "gradient, autograd, fast-prediction, prepared-table or general-smoothness path reads it")
 
 
 # what a non-zero ``info`` of an NS launch is reported as (``_lib.raise_if_not_spd``): a bad pivot or a bad scale
@@ -756,10 +756,14 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
     the per-neighbourhood partials ``g_nu (b,)`` with respect to the smoothness."""
     P = _lib.ptr
     fn, ls = inp.fn, inp.ls
+    if spec.length_scale_batch is not None and spec.kernel == "matern_gen":
+        raise ValueError("length_scale_batch: the general-smoothness Matern has no per-neighbourhood-scale kernel")
     if spec.kernel == "matern_gen":
         return _hyper_partials_gen(spec, inp, info, gm, gv, gyk, want_noise, want_nu)
     if want_nu:
         raise ValueError(f"kernel {spec.kernel!r} has a fixed smoothness: no gradient with respect to it")
+    if spec.length_scale_batch is not None:
+        return _hyper_partials_ns(spec, inp, info, gm, gv, gyk, want_noise)
     g_l = torch.zeros((inp.b, ls.numel()), device=fn.device, dtype=fn.dtype)
     g_n = torch.zeros((inp.b, inp.k), device=fn.device, dtype=fn.dtype) if want_noise else None
     gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
@@ -781,6 +785,31 @@ def _hyper_partials(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk=None, want
 
     rc, at = _lib.run_ladder((lds,) if spec.kernel == "matern_gen" else (lds, slab))
     _lib.check(rc, what[at])
+    return g_l, g_n
+
+
+def _hyper_partials_ns(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_noise: bool):
+    """:func:`_hyper_partials` of a model with a length scale per neighbourhood (``inp.ls``: the ``(b, ls_count)``
+    tensor): row ``nb`` of ``g_l`` is d / d (the scales of neighbourhood ``nb``).  The ladder is
+    ``mgp_hyper_backward_ns_*`` (the wave-sized backward, the LDS workgroup backward behind it inside the entry), then
+    ``mgp_hyper_backward_ns_large_*`` on the slab factor."""
+    P = _lib.ptr
+    fn, ls = inp.fn, inp.ls
+    g_l = torch.zeros((inp.b, ls.shape[1]), device=fn.device, dtype=fn.dtype)
+    g_n = torch.zeros((inp.b, inp.k), device=fn.device, dtype=fn.dtype) if want_noise else None
+    gm, gv = (None if g is None else g.contiguous() for g in (gm, gv))
+    args = (P(fn), inp.d, P(inp.bi), P(inp.ni), inp.b, inp.k, P(inp.tg), inp.R, _lib.NOISE_SCALAR, float(spec.noise), None,
+            spec.kernel_id(), spec.metric_id(), P(ls), ls.shape[1], P(gm), P(gv), P(gyk), P(g_l), P(g_n), P(info))
+
+    def lds():
+        return _lib.fn("hyper_backward_ns", fn.dtype)(*args, _lib.stream_ptr())
+
+    def slab():  # (beyond the kernel: the ValueError of the scalar ladder, naming the nn_count limit)
+        ws = _lib.backward_large_workspace(fn.dtype, inp.k, inp.b, fn.device)
+        return _lib.fn("hyper_backward_ns_large", fn.dtype)(*args, P(ws), ws.numel(), _lib.stream_ptr())
+
+    rc, at = _lib.run_ladder((lds, slab))
+    _lib.check(rc, ("mgp_hyper_backward_ns", "mgp_hyper_backward_ns_large")[at])
     return g_l, g_n
 
 
@@ -930,8 +959,9 @@ def _hyper_gradient(g_l, g_n, info, what: str, reduce_fn, g_nu=None):
 def _loocv_forward(spec: KernelSpec, train_features, train_targets, bi, ni, packed, huber_delta: float):
     """``(partials, mean, var, ykinvy)`` of one LOOCV evaluation: :func:`loocv_partials`, or -- the general-smoothness
     Matern, which ``mgp_loocv_*`` serves on the wave kernels alone -- the fused posterior with ``y^T K^-1 y`` at any
-    ``nn_count`` followed by the reduction tree over its outputs (:func:`loocv_tree_sums`)."""
-    if spec.kernel != "matern_gen":
+    ``nn_count`` followed by the reduction tree over its outputs (:func:`loocv_tree_sums`); a length scale per
+    neighbourhood (``spec.length_scale_batch``) takes the same route on the NS kernels."""
+    if spec.kernel != "matern_gen" and spec.length_scale_batch is None:
         return loocv_partials(spec, train_features, train_targets, bi, ni, packed=packed, return_ykinvy=True,
                               huber_delta=huber_delta)
     mean, var, yk = posterior_mean_var(spec, train_features, train_features, bi, ni, train_targets, want_ykinvy=True,
@@ -984,10 +1014,28 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     cotangent of ``y^T K^-1 y`` (the analytic sigma^2 with its fixed-point passes, the ``sigma_noise`` split with its
     second backward launch) reaches it the way it reaches the length scales.
 
+    A length scale per neighbourhood (``spec.length_scale_batch``, closed-form kernels): the forward is the fused
+    posterior on the NS kernels with the reduction tree behind it, the backward ``mgp_hyper_backward_ns_*`` /
+    ``mgp_hyper_backward_ns_large_*``, and the second result is then the per-neighbourhood partials ``(b, ls_count)``
+    as a DEVICE tensor, row ``nb`` = d loss / d (the scales of neighbourhood ``nb``), not summed over the batch (the
+    chain to a hierarchical parameter's knots is ``NamedHierarchicalParameter.pullback``).  ``reduce_fn`` is refused
+    there: sharded NS gradients are not built.
+
     Returns ``(value, grad_length_scale (numpy, ls_count), grad_noise (float))`` of the LOSS (the objective the
     drivers maximise is its negative); with ``grad_smoothness`` ``(value, grad_ls, grad_noise, grad_nu (float))``."""
     import copy
     import math
+
+    ns = spec.length_scale_batch is not None
+    if ns:
+        if spec.kernel == "matern_gen":
+            raise ValueError("length_scale_batch: the general-smoothness Matern has no per-neighbourhood-scale kernel")
+        if reduce_fn is not None:
+            raise ValueError("length_scale_batch: sharded gradients (reduce_fn) of a length scale per neighbourhood are "
+                             "not built")
+        if not (isinstance(spec.length_scale_batch, torch.Tensor) and spec.length_scale_batch.is_cuda):
+            raise ValueError("length_scale_batch must be a torch.Tensor on the ROCm device ('cuda') of shape (b,), "
+                             "(b, 1) or (b, d)")
 
     if loss not in ("lool", "mse", "pseudo_huber", "looph"):
         raise NotImplementedError(f"analytic gradients are written out for lool, mse, pseudo_huber and looph, not {loss!r}")
@@ -995,7 +1043,8 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
         raise NotImplementedError("analytic gradients: homoscedastic noise")
     if grad_smoothness and spec.kernel != "matern_gen":
         raise ValueError(f"grad_smoothness: kernel {spec.kernel!r} has a fixed smoothness")
-    inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_targets, responses="single")
+    inp = _normalize(spec, train_features, train_features, batch_indices, nn_indices, train_targets, responses="single",
+                     per_neighbourhood=ns)
     dtype, tg, ni, bi, k = inp.fn.dtype, inp.tg, inp.ni, inp.bi, inp.k
     needs_scale = loss in ("lool", "looph")
     delta = float(boundary_scale) if boundary_scale is not None else (3.0 if loss == "looph" else 1.5)
@@ -1061,6 +1110,9 @@ def loocv_value_and_grad(spec: KernelSpec, train_features: torch.Tensor, train_t
     else:
         g_l, g_n, *g_nu = _hyper_partials(spec, inp, info, gm, gv,
                                           torch.full_like(var, gyk_value) if gyk_value != 0.0 else zeros, **nu)
+    if ns:  # the rows stay apart: one scale (or d) per neighbourhood; a bad pivot or a bad scale raises as in the forward
+        _lib.raise_if_not_spd(info, NS_NOT_SPD)
+        return value, g_l, float(_lib.column_sums(g_n.reshape(-1, 1)).item())
     return (value, *_hyper_gradient(g_l, g_n, info, "LOOCV gradient", reduce_fn, *g_nu))
 
 

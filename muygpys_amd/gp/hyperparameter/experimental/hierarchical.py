@@ -152,6 +152,26 @@ class NamedHierarchicalParameter(_KeywordRouting, HierarchicalParameter):
         self._value = (vkey, out)
         return out
 
+    def pullback(self, batch_features, g):
+        """The chain from per-neighbourhood partials to the knots.  The value is linear in the knot values ``v``,
+        ``C (K + noise I)^-1 v`` with ``C`` the ``(b, knot_count)`` lower cross-covariance, so for ``g`` = d loss / d
+        value, ``(b,)`` or ``(b, 1)`` on the device, d loss / d v = ``solve((K + noise I)^T, C^T g)``: numpy
+        ``(knot_count,)``, fp64.  ``C`` and ``K`` are the cached ones; the contraction over the batch is the
+        deterministic fp64 column sum of ``C * g`` (``mgp_column_sums_*``), not a floating-point reduction whose order
+        changes from run to run."""
+        import torch
+
+        from muygpys_amd import _lib
+
+        if not (isinstance(g, torch.Tensor) and g.is_cuda):
+            raise TypeError("hip backend functions take torch tensors on a ROCm device ('cuda'): g")
+        cross = self._lower_cross(batch_features)
+        if g.numel() != cross.shape[0] or g.ndim > 2:
+            raise ValueError(f"pullback: g must have shape ({cross.shape[0]},) or ({cross.shape[0]}, 1), got {tuple(g.shape)}")
+        _, Kin = self._knots_on(batch_features.device)
+        ctg = _lib.column_sums((cross * g.reshape(-1, 1).to(torch.float64)).contiguous())
+        return torch.linalg.solve(Kin.T, ctg).cpu().numpy()
+
     # ---- keyword routing / optimiser lists ----
     def filter_kwargs(self, **kwargs) -> Tuple[Dict, Dict]:
         mine, rest = self._params.filter_kwargs(**kwargs)
