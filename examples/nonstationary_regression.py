@@ -5,6 +5,7 @@ on the right, a handful of knots whose values are the length scale there, k-NN, 
 
     python examples/nonstationary_regression.py                       # needs a ROCm device
     python examples/nonstationary_regression.py --analytic-gradient   # the knots by the NS backward kernels
+    python examples/nonstationary_regression.py --forward wave        # the wave-sized NS forward kernel first
 
 The length scale of every neighbourhood is the posterior mean of a small higher-level GP over the knots, evaluated at
 the batch element's features; the whole posterior is ONE fused launch with a length scale per neighbourhood.
@@ -38,8 +39,16 @@ def curve(x, rng, noise):
     return np.sin(2 * np.pi * (1.0 + 7.0 * (1.0 - x) ** 2) * x) + np.sqrt(noise) * rng.standard_normal(x.shape)
 
 
-def run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, batch_count=300, verbose=True,
-        analytic_gradient=False):
+def run(forward="workgroup", **kw):
+    """``forward``: the first rung of the NS forward ladder (``fused.NS_FORWARD_MODES``) for training and prediction."""
+    from muygpys_amd import fused
+
+    with fused.ns_forward(forward):
+        return _run(**kw)
+
+
+def _run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, batch_count=300, verbose=True,
+         analytic_gradient=False):
     rng = np.random.default_rng(seed)
     x = np.linspace(0.0, 1.0, n)
     y = curve(x, rng, noise)
@@ -94,4 +103,6 @@ def run(seed=0, n=3000, train_step=3, nn_count=12, knot_count=4, noise=1e-3, bat
 
 
 if __name__ == "__main__":
-    run(analytic_gradient="--analytic-gradient" in sys.argv[1:])
+    args = sys.argv[1:]
+    run(forward=args[args.index("--forward") + 1] if "--forward" in args else "workgroup",
+        analytic_gradient="--analytic-gradient" in args)

@@ -315,6 +315,31 @@ int mgp_posterior_ns_large_f64(const double* feat_q, const double* feat_nn, int 
                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * ... and at wave size (ns_wave_forward_kernel: one wavefront per one or two neighbourhoods, the rows in registers), by
+ * name: the same model -- HierarchicalParameter, gp/hyperparameter/experimental/hierarchical.py:15-158, through
+ * Isotropy's (b,) scale, gp/deformation/isotropy.py:60-89 -- and T1-T4, D1, N1/N2, S1-S3 in one launch.  The parameter
+ * list is that of mgp_posterior_ns_generic_*, name for name, and so are the contract of length_scale_batch, the NaN rows
+ * and the one count in *info of a neighbourhood with a bad scale or a non-positive pivot (both: one count).  No bits are
+ * promised against any other kernel.
+ *   Served: ls_count == 1 (Isotropy), k + 1 + R <= 64, d <= 64 (fp32) / d <= 16 (fp64; d <= 8 where k + 1 + R > 32).
+ *   Order of the checks, all before any HIP call: sizes (MGP_EINVAL), the empty batch (MGP_OK, nothing else looked
+ *   at), pointers (length_scale_batch NULL: MGP_EINVAL), ids, a noise mode without noise_dev, ls_count not in {1, d}
+ *   (MGP_EINVAL), then MGP_KERNEL_MATERN_GEN, ls_count != 1 or a shape outside the list above: MGP_EUNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+int mgp_posterior_ns_wave_f32(const float* feat_q, const float* feat_nn, int d,
+                              const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                              const float* targets, int R, int targets_batch,
+                              int noise_mode, double noise_scalar, const float* noise_dev,
+                              int kernel_id, int metric_id, const float* length_scale_batch, int ls_count,
+                              float* mean, float* var, float* ykinvy, int* info, void* stream);
+int mgp_posterior_ns_wave_f64(const double* feat_q, const double* feat_nn, int d,
+                              const int64_t* batch_idx, const int64_t* nn_idx, int64_t b, int k,
+                              const double* targets, int R, int targets_batch,
+                              int noise_mode, double noise_scalar, const double* noise_dev,
+                              int kernel_id, int metric_id, const double* length_scale_batch, int ls_count,
+                              double* mean, double* var, double* ykinvy, int* info, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Run-time specialisation.  mgp_posterior_* / mgp_loocv_* serve a shape (k, R, d) with a kernel whose
  * loops are compiled for exactly that shape: built into the library for the BASELINE shapes, compiled
  * on first use (hiprtc, ~1 s, cached on disk next to the library) for any other shape with

@@ -84,7 +84,9 @@ PER_FILE_FLAGS = {
     # (... and the wave-sized one, a kernel of its own: the compiler is told not to select packed fp32 instructions for
     # it, and it contains no hand-written ones)
     **{f: ["-mllvm", "-pragma-unroll-threshold=1000000", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",
-           "-Rpass-analysis=kernel-resource-usage"] for f in ("mgp_backward_wave_ns.hip", "mgp_backward_wave_ns_f32.hip")},
+           "-Rpass-analysis=kernel-resource-usage"]
+       # (... and the wave-sized forward of the same models: tests/test_posterior_ns_wave_status_cpu.py reads its records)
+       for f in ("mgp_backward_wave_ns.hip", "mgp_backward_wave_ns_f32.hip", "mgp_forward_wave_ns.hip", "mgp_forward_wave_ns_f32.hip")},
 }
 
 

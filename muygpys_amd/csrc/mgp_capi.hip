@@ -521,6 +521,20 @@ static int posterior_ns(const T* fq, const T* fn, int d, const int64_t* bi, cons
   if (kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
   return launch_fused_generic_ns<T>(a, lsb, static_cast<hipStream_t>(stream));  // (refuses a system beyond LDS)
 }
+// ... and the wave-sized kernel by name (mgp_posterior_ns_wave_*, mgp_forward_wave_ns.hip): the same checks; the launcher
+// refuses (b, d) scales and every shape beyond its instantiations before any HIP call
+template <typename T>
+static int posterior_ns_wave(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
+                             const T* tg, int R, int targets_batch, int noise_mode, double eps, const T* nd, int kernel_id,
+                             int metric_id, const T* lsb, int ls_count, T* mean, T* var, T* yk, int* info, void* stream) {
+  FusedArgs a;
+  const int ready = fused_args<T>(a, NEED_RESPONSES | NEED_OUTPUTS | KERNEL_MAY_BE_GEN, fq, fn, d, bi, ni, b, k, tg, R,
+                                  noise_mode, eps, nd, kernel_id, metric_id, lsb, ls_count, mean, var, yk, info, nullptr, 0,
+                                  nullptr, 0, targets_batch != 0);
+  if (ready != ARGS_READY) return ready;
+  if (kernel_id == MGP_KERNEL_MATERN_GEN) return MGP_EUNSUPPORTED;
+  return launch_forward_wave_ns<T>(a, lsb, static_cast<hipStream_t>(stream));
+}
 template <typename T>
 static int posterior_ns_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
                               const T* tg, int R, int targets_batch, int noise_mode, double eps, const T* nd, int kernel_id,
@@ -794,6 +808,13 @@ MGP_DEFINE_LARGE(f64, double)
                                      int* info, void* st) {                                                          \
     return posterior_ns<T>(fq, fn, d, bi, ni, b, k, tg, R, targets_batch, nm, eps, nd, kid, mid, lsb, lsc, mean,     \
                            var, yk, info, st);                                                                       \
+  }                                                                                                                  \
+  int mgp_posterior_ns_wave_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,             \
+                                  int64_t b, int k, const T* tg, int R, int targets_batch, int nm, double eps,       \
+                                  const T* nd, int kid, int mid, const T* lsb, int lsc, T* mean, T* var, T* yk,      \
+                                  int* info, void* st) {                                                             \
+    return posterior_ns_wave<T>(fq, fn, d, bi, ni, b, k, tg, R, targets_batch, nm, eps, nd, kid, mid, lsb, lsc,      \
+                                mean, var, yk, info, st);                                                            \
   }                                                                                                                  \
   int mgp_posterior_ns_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,            \
                                    int64_t b, int k, const T* tg, int R, int targets_batch, int nm, double eps,      \

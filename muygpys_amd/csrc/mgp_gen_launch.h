@@ -143,6 +143,8 @@ int max_nn_count_gen(int elem_size, int R);
 template <typename T> int launch_fused_generic_ns(const FusedArgs&, const void* ls_batch, hipStream_t);
 template <typename T>
 int launch_fused_large_ns(const FusedArgs&, const void* ls_batch, void* workspace, int64_t workspace_bytes, hipStream_t);
+// ... and the wave-sized forward in front of them (mgp_forward_wave_ns.hip: Isotropy, k + 1 + R <= 64)
+template <typename T> int launch_forward_wave_ns(const FusedArgs&, const void* ls_batch, hipStream_t);
 // ... and their hyper-parameter backwards (mgp_backward_wave_ns.hip: Isotropy at wave size; mgp_backward_ns.hip: LDS;
 // mgp_backward_large_ns.hip: the slab factor): grad_ls (b, ls_count) and grad_noise (b, k), no other cotangent
 template <typename T> int launch_backward_wave_ns(const BackwardArgs&, const void* ls_batch, hipStream_t);

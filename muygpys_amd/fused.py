@@ -421,7 +421,8 @@ def posterior_mean_var(
     (:44-67 with Kout = 1); ``ykinvy (b, R)`` holds ``y_r^T K^-1 y_r`` per neighbourhood
     (the summand of _analytic_scale_optim_unnormalized, scale/numpy.py:9-15).
 
-    ``path``: "auto" (dispatcher), or one kernel family by name -- "generic" / "rhs" / "large" (parity tests; the
+    ``path``: "auto" (dispatcher), or one kernel family by name -- "generic" / "rhs" / "large", and "wave" with a
+    ``length_scale_batch`` (``mgp_posterior_ns_wave_*``; :func:`ns_forward` puts it in front of "auto") (parity tests; the
     general-smoothness Matern has no "rhs").  Which entry points a call tries, in which order: the lists of rungs in
     the body, and the table in DESIGN.md §1.  A closed-form kernel is served up to ``nn_count + 1 + R = 1024`` rows
     (``ValueError`` beyond); the general-smoothness Matern raises :class:`FusedUnsupported` where no fused kernel
@@ -435,8 +436,10 @@ def posterior_mean_var(
     ns = spec.length_scale_batch is not None
     if ns and spec.kernel == "matern_gen":
         raise ValueError("length_scale_batch: the general-smoothness Matern has no per-neighbourhood-scale kernel")
-    if ns and path not in ("auto", "generic", "large"):
-        raise ValueError(f"length_scale_batch: path is 'auto', 'generic' or 'large', not {path!r}")
+    if ns and path not in ("auto", "wave", "generic", "large"):
+        raise ValueError(f"length_scale_batch: path is 'auto', 'wave', 'generic' or 'large', not {path!r}")
+    if path == "wave" and not ns:  # (a name of the NS ladder alone; decided with the check above, before the tensors are looked at)
+        raise ValueError(f"unknown kernel path {path!r}")
     inp = _normalize(spec, test_features, train_features, batch_indices, nn_indices, train_targets, gathered=gathered,
                      per_neighbourhood=ns)
     _debug_check_indices(inp)
@@ -444,14 +447,14 @@ def posterior_mean_var(
     mean = out_mean if out_mean is not None else torch.empty((b, R), device=fn.device, dtype=dtype)
     var = out_var if out_var is not None else torch.empty((b,), device=fn.device, dtype=dtype)
     yk = torch.empty((b, R), device=fn.device, dtype=dtype) if want_ykinvy else None
-    if path not in ("auto", "generic", "rhs", "large"):
+    if path not in ("auto", "wave", "generic", "rhs", "large"):
         raise ValueError(f"unknown kernel path {path!r}")
     gen = spec.kernel == "matern_gen"  # one entry point for every table form (mgp_posterior_gen_*)
     if gen and path == "rhs":
         raise ValueError("the general-smoothness Matern goes through the dispatcher (path='auto')")
     if gen and (spec.smoothness is None or not float(spec.smoothness) > 0.0):
         raise ValueError(f"kernel 'matern_gen' needs a positive smoothness, got {spec.smoothness}")
-    if gathered and path not in ("auto", "large") and not ((gen or ns) and path == "generic"):
+    if gathered and path not in ("auto", "large") and not ((gen or ns) and path == "generic") and not (ns and path == "wave"):
         raise ValueError("gathered responses go through the dispatcher (path='auto') or path='large'")
     # (a separate test table is packed too -- one more pass over ITS rows -- so it counts as table size)
     rows = fn.shape[0] + (0 if test_features is train_features else inp.fq.shape[0])
@@ -480,9 +483,12 @@ def posterior_mean_var(
         return _posterior_plain(base, inp, model, outs, gathered, slab)
 
     # the ladders: a rung is tried when the one before it answered MGP_EUNSUPPORTED
-    if ns:  # plain tables, the two workgroup families (own info: a bad scale counts there like a bad pivot)
+    if ns:  # plain tables: the two workgroup families, the wave-sized kernel in front of them under ns_forward("wave")
+        # (own info: a bad scale counts there like a bad pivot)
         lds, slab = (lambda: ns_family("posterior_ns_generic", False)), (lambda: ns_family("posterior_ns_large", True))
-        rungs = {"auto": (lds, slab), "generic": (lds,), "large": (slab,)}[path]
+        wave = lambda: ns_family("posterior_ns_wave", False)  # noqa: E731
+        auto = (wave, lds, slab) if _NS_FORWARD == "wave" else (lds, slab)
+        rungs = {"auto": auto, "wave": (wave,), "generic": (lds,), "large": (slab,)}[path]
     elif gen:
         def gen_slab():  # (more than 1024 rows: refused without a call)
             try:
@@ -852,6 +858,42 @@ def gen_backward(mode: str):
 def gen_backward_default() -> str:
     """The mode in force right now (the environment's choice, or an enclosing block's)."""
     return _GEN_BACKWARD
+
+
+# which rung serves the forward of a model with a length scale per neighbourhood first (``path="auto"`` of
+# posterior_mean_var, hence lazy_eval._ns_launch, MuyGPS, the optimisers and the forward inside loocv_value_and_grad):
+# "workgroup" (the LDS workgroup kernel, then the slab) or "wave" (mgp_posterior_ns_wave_* in front of them: Isotropy up
+# to 64 slots, csrc/mgp_forward_wave_ns.h).  MUYGPYS_HIP_NS_FORWARD, unset = workgroup.
+NS_FORWARD_MODES = ("workgroup", "wave")
+
+
+def _ns_forward_from_env() -> str:
+    mode = os.environ.get("MUYGPYS_HIP_NS_FORWARD", "") or "workgroup"
+    if mode not in NS_FORWARD_MODES:
+        raise ValueError(f"MUYGPYS_HIP_NS_FORWARD={mode!r} is none of {NS_FORWARD_MODES}")
+    return mode
+
+
+_NS_FORWARD = _ns_forward_from_env()
+
+
+@contextlib.contextmanager
+def ns_forward(mode: str):
+    """``with fused.ns_forward("wave"):`` -- the first rung of the NS ladder inside the block; the previous mode is
+    restored on the way out."""
+    global _NS_FORWARD
+    if mode not in NS_FORWARD_MODES:
+        raise ValueError(f"ns_forward mode {mode!r} is none of {NS_FORWARD_MODES}")
+    previous, _NS_FORWARD = _NS_FORWARD, mode
+    try:
+        yield
+    finally:
+        _NS_FORWARD = previous
+
+
+def ns_forward_default() -> str:
+    """The mode in force right now (the environment's choice, or an enclosing block's)."""
+    return _NS_FORWARD
 
 
 # how the fast-posterior-mean workflow serves the general-smoothness Matern: "materialised" (coefficients through

@@ -76,7 +76,8 @@ def _spec(Kin: lazy.LazyCov):
 
 def _ns_launch(spec, Kin: lazy.LazyCov, Kcross: lazy.LazyCov, tg, info, gathered: bool):
     """The one fused launch of a triple whose handles carry a length scale per batch element (the NS ladder of
-    ``fused.posterior_mean_var``: ``mgp_posterior_ns_generic_*``, then ``mgp_posterior_ns_large_*``)."""
+    ``fused.posterior_mean_var``: ``mgp_posterior_ns_generic_*``, then ``mgp_posterior_ns_large_*``; under
+    ``fused.ns_forward("wave")`` ``mgp_posterior_ns_wave_*`` in front of them)."""
     from .fused import posterior_mean_var
 
     a, c = Kin.diffs, Kcross.diffs

@@ -12,6 +12,8 @@ Three comparisons per shape, the two sides of each alternating in one process (r
                       gets -- against the NS launch: what a nonstationary model gives up on the workgroup kernel
 
     python tools/nsbench.py [--quick] [--out profiles/nonstationary_bench.json]
+
+``--wave`` measures the wave-sized NS forward instead (``wave_main``) -> profiles/nonstationary_wave_bench.json.
 """
 
 import argparse
@@ -77,18 +79,70 @@ def materialised(spec_kernel, metric, X, bi, ni, y, ls, noise):
     return M._solve(Kin, Kc, y[ni], want=("mean", "var"))
 
 
+WAVE_SHAPES = [("float32", 30, 40), ("float32", 10, 8), ("float64", 50, 8), ("float64", 30, 16)]  # 200 000 neighbourhoods each
+WAVE_OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "nonstationary_wave_bench.json")
+
+
+def wave_main(a, dev, rounds, reps):
+    """--wave: the NS wave launch (path="wave"), the NS LDS launch of the same call (path="generic": the baseline) and the
+    scalar wave kernel a stationary model gets at the same shape, alternating -> profiles/nonstationary_wave_bench.json
+    (whose "gradient" records, written by tools/nsgradbench.py --forward wave, are kept)."""
+    results = []
+    for dtype, k, d in WAVE_SHAPES:
+        b = 20_000 if a.quick else 200_000
+        dt = getattr(torch, dtype)
+        rng = np.random.default_rng(k * 1000 + d)
+        n = 20_000
+        X = torch.as_tensor(rng.uniform(size=(n, d)) * 3.0 / np.sqrt(d / 6.0), device=dev, dtype=dt)
+        y = torch.as_tensor(rng.normal(size=n), device=dev, dtype=dt)
+        bi = torch.as_tensor(rng.integers(0, n, size=b), device=dev)
+        ni = torch.as_tensor(rng.integers(0, n, size=(b, k)), device=dev)
+        ls = torch.as_tensor(np.exp(rng.uniform(np.log(1.0), np.log(5.0), size=b)), device=dev, dtype=dt)
+        specs = dict(scalar=KernelSpec("matern15", "l2", 3.0, 0.05), ns=KernelSpec("matern15", "l2", 1.0, 0.05, length_scale_batch=ls))
+        mean, var = torch.empty((b, 1), device=dev, dtype=dt), torch.empty(b, device=dev, dtype=dt)
+        info = torch.zeros(1, device=dev, dtype=torch.int32)
+        names = {}
+
+        def run(tag, spec, path):
+            def fn():
+                posterior_mean_var(specs[spec], X, X, bi, ni, y, path=path, info=info, out_mean=mean, out_var=var, packed=False)
+                names[tag] = _lib.last_kernel()
+            return fn
+
+        t = alternate({"ns_wave": run("ns_wave", "ns", "wave"), "ns_lds": run("ns_lds", "ns", "generic"),
+                       "scalar_wave": run("scalar_wave", "scalar", "auto")}, rounds, reps)
+        assert int(info.item()) == 0, "a neighbourhood did not factorise: the timings are not of the intended work"
+        med = {s: float(np.median(v)) for s, v in t.items()}
+        rec = dict(dtype=dtype, k=k, d=d, neighbourhoods=b, rounds=rounds, reps=reps, kernels=dict(names),
+                   **{s: summary(v) for s, v in t.items()}, lds_spread=summary(t["ns_lds"])["spread"],
+                   lds_over_wave=med["ns_lds"] / med["ns_wave"], wave_over_scalar=med["ns_wave"] / med["scalar_wave"])
+        print(json.dumps(rec), flush=True)
+        results.append(rec)
+    out = dict(device=torch.cuda.get_device_name(0), tool="tools/nsbench.py --wave", quick=bool(a.quick), shapes=results)
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out.update({key: v for key, v in json.load(f).items() if key.startswith("gradient")})
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="a tenth of the neighbourhoods, fewer rounds (rehearsal)")
+    ap.add_argument("--wave", action="store_true", help="the wave-sized NS forward against the LDS launch and the scalar wave kernel")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
-                                                  "nonstationary_bench.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or (WAVE_OUT if a.wave else os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                                          "nonstationary_bench.json"))
     if not torch.cuda.is_available():
         raise SystemExit("nsbench needs a ROCm device: nothing is measured without one")
     dev = torch.device("cuda:0")
     rounds, reps = (3, 2) if a.quick else (a.rounds, a.reps)
+    if a.wave:
+        return wave_main(a, dev, rounds, reps)
     results = []
     for dtype, k, d, b, family in SHAPES:
         b = b // 10 if a.quick else b

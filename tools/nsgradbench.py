@@ -12,6 +12,9 @@ spread of the scalar side next to every ratio.
                          forward, p the knot count of examples/nonstationary_regression.py
 
     python tools/nsgradbench.py [--quick] [--out profiles/nonstationary_backward_bench.json]
+
+``--forward wave`` times one analytic gradient evaluation under ``fused.ns_forward("wave")`` next to the default route's
+instead (``forward_wave_main``) -> the "gradient" records of profiles/nonstationary_wave_bench.json.
 """
 
 import argparse
@@ -43,6 +46,51 @@ def hierarchical(d, knots, rng):
     return Isotropy(l2, length_scale=raw).length_scale
 
 
+def forward_wave_main(a, dev, rounds, reps):
+    """--forward wave: one analytic knot-gradient evaluation (gradient_vs_forwards' `analytic`) under
+    fused.ns_forward("wave") and under the default mode, alternating, at the first two shapes -> the "gradient" records of
+    profiles/nonstationary_wave_bench.json (tools/nsbench.py --wave writes the rest of that file and keeps these)."""
+    from tools.nsbench import WAVE_OUT
+
+    records = []
+    for dtype, k, d, b, _ in SHAPES[:2]:
+        b = b // 10 if a.quick else b
+        dt = getattr(torch, dtype)
+        rng = np.random.default_rng(k * 1000 + d)
+        n = max(4 * k, 20_000)
+        X = torch.as_tensor(rng.uniform(size=(n, d)) * 3.0 / np.sqrt(d / 6.0), device=dev, dtype=dt)
+        y = torch.as_tensor(rng.normal(size=n), device=dev, dtype=dt)
+        bi = torch.as_tensor(rng.integers(0, n, size=b), device=dev)
+        ni = torch.as_tensor(rng.integers(0, n, size=(b, k)), device=dev)
+        hp, bf, trial = hierarchical(d, KNOTS, rng), X[bi].contiguous(), [0]
+
+        def analytic(mode):
+            def fn():
+                trial[0] += 1  # (a new trial point every evaluation: nothing comes out of the parameter's caches)
+                knots = {f"length_scale{j}": 3.0 + 1e-3 * ((trial[0] + j) % 97) for j in range(KNOTS)}
+                spec = KernelSpec("matern15", "l2", 1.0, 0.05, length_scale_batch=hp(bf, **knots))
+                with fused.ns_forward(mode):
+                    _, g_l, _ = fused.loocv_value_and_grad(spec, X, y, bi, ni, packed=False)
+                hp.pullback(bf, g_l)
+            return fn
+
+        t = alternate({"workgroup": analytic("workgroup"), "wave": analytic("wave")}, rounds, reps)
+        rec = dict(dtype=dtype, k=k, d=d, neighbourhoods=b, knots=KNOTS, rounds=rounds, reps=reps,
+                   workgroup=summary(t["workgroup"]), wave=summary(t["wave"]),
+                   speedup=float(np.median(t["workgroup"]) / np.median(t["wave"])))
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+    out = dict(device=torch.cuda.get_device_name(0), tool="tools/nsbench.py --wave", shapes=[])
+    if os.path.exists(WAVE_OUT):
+        with open(WAVE_OUT) as f:
+            out = json.load(f)
+    out["gradient"] = records
+    out["gradient_tool"] = "tools/nsgradbench.py --forward wave"
+    with open(WAVE_OUT, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", WAVE_OUT)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="a tenth of the neighbourhoods, fewer rounds (rehearsal)")
@@ -50,11 +98,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
                                                   "nonstationary_backward_bench.json"))
+    ap.add_argument("--forward", choices=fused.NS_FORWARD_MODES, default="workgroup",
+                    help="wave: one analytic gradient evaluation under fused.ns_forward('wave') next to the default route's")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("nsgradbench needs a ROCm device: nothing is measured without one")
     dev = torch.device("cuda:0")
     rounds, reps = (3, 2) if a.quick else (a.rounds, a.reps)
+    if a.forward == "wave":
+        return forward_wave_main(a, dev, rounds, reps)
     results = []
     for at, (dtype, k, d, b, _) in enumerate(SHAPES):
         b = b // 10 if a.quick else b
