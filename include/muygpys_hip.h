@@ -1090,6 +1090,39 @@ int mgp_hyper_backward_gen_large_f64(const double* features, int d, const int64_
                                      const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
                                      double* grad_ls, double* grad_noise, double* grad_nu, int* info,
                                      void* workspace, int64_t workspace_bytes, void* stream);
+/* The same three partials at wave size (csrc/mgp_backward_wave_gen.h): one wavefront per workgroup holds 64 / NP
+ * neighbourhoods of NP = 32 or 64 slots, k + 2 <= NP, the system in registers (a row per lane) and no workspace.  The
+ * parameter list is mgp_hyper_backward_gen_large_*'s without `workspace` and `workspace_bytes`, the semantics are that
+ * entry's: the LOOCV form (grad_ykinvy, R = 1) and the posterior form (grad_mean (b, R), any R >= 1), the three noise
+ * modes, both metrics, scalar or per-feature length scale, batch_idx optional, one table on both sides, no feature or
+ * response cotangents.
+ *   Shapes served: k + 2 <= 64; d <= 64 in fp32; d <= 16 in fp64 up to 32 slots, d <= 8 beyond; 0 < nu <= 30.  Every
+ *       other shape: MGP_EUNSUPPORTED -- the caller goes on to mgp_posterior_backward_gen_* or
+ *       mgp_hyper_backward_gen_large_*.
+ *   grad_ls (b, ls_count), grad_noise (b, k), grad_nu (b): written; any may be NULL, not all three.  With grad_nu NULL
+ *       the kernel evaluates one exponential per quadrature node and pair in its derivative pass, with it three.  At 32
+ *       slots two neighbourhoods share a wavefront: each half-wave sums the quadrature to its OWN node count, and every
+ *       sum over pairs is closed inside the half in a fixed order (no floating-point atomic), so a neighbourhood's
+ *       three partials are the same bits whatever its place in the batch, its partner in the wave, the batch and the
+ *       grid.  A pair at zero distance contributes nothing to grad_ls or grad_nu, also below nu = 1/2.  A non-SPD
+ *       neighbourhood counts once in *info and leaves its rows of all three untouched; its partner is not affected.
+ *   Order of the checks, all before any HIP call: sizes b < 0, k < 1, d < 1, R < 1 and a smoothness that is not > 0
+ *   (NaN included) (MGP_EINVAL); the empty batch (MGP_OK, nothing else looked at); required pointers, grad_ykinvy with
+ *   R != 1, all three cotangents NULL, all three outputs NULL, ids, a noise mode without noise_dev, ls_count not in
+ *   {1, d} (MGP_EINVAL); then smoothness > 30, k + 2 > 64 or d beyond the shapes above: MGP_EUNSUPPORTED.  The
+ *   closed-form entries go on refusing MGP_KERNEL_MATERN_GEN. */
+int mgp_hyper_backward_gen_wave_f32(const float* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                    int64_t b, int k, const float* targets, int R,
+                                    int noise_mode, double noise_scalar, const float* noise_dev,
+                                    double smoothness, int metric_id, const float* length_scale, int ls_count,
+                                    const float* grad_mean, const float* grad_var, const float* grad_ykinvy,
+                                    float* grad_ls, float* grad_noise, float* grad_nu, int* info, void* stream);
+int mgp_hyper_backward_gen_wave_f64(const double* features, int d, const int64_t* batch_idx, const int64_t* nn_idx,
+                                    int64_t b, int k, const double* targets, int R,
+                                    int noise_mode, double noise_scalar, const double* noise_dev,
+                                    double smoothness, int metric_id, const double* length_scale, int ls_count,
+                                    const double* grad_mean, const double* grad_var, const double* grad_ykinvy,
+                                    double* grad_ls, double* grad_noise, double* grad_nu, int* info, void* stream);
 /* The whole vector-Jacobian product of mgp_posterior_backward_* for any such k: what the reference obtains from torch
  * autograd when a deep-kernel model trains through MuyGPs_layer (torch/muygps_layer.py:129-164) with an nn_count beyond
  * mgp_max_nn_count_backward, on the same blocked factor and the same backward slab.  Arguments and semantics as

@@ -87,6 +87,12 @@ PER_FILE_FLAGS = {
            "-Rpass-analysis=kernel-resource-usage"]
        # (... and the wave-sized forward of the same models: tests/test_posterior_ns_wave_status_cpu.py reads its records)
        for f in ("mgp_backward_wave_ns.hip", "mgp_backward_wave_ns_f32.hip", "mgp_forward_wave_ns.hip", "mgp_forward_wave_ns_f32.hip")},
+    # (... and the wave-sized backward of the general-smoothness Matern: tests/test_hyper_backward_gen_wave_status_cpu.py
+    # reads its records.  The packed fp32 instructions stay ON here, unlike the NS units: the quadrature evaluators are
+    # written on f2 arithmetic -- one packed add, FMA and add per two covariances and node -- and the distances use the
+    # packed subtraction; every instantiation fits its register cap with them, see the records)
+    **{f: ["-mllvm", "-pragma-unroll-threshold=1000000", "-Rpass-analysis=kernel-resource-usage"]
+       for f in ("mgp_backward_wave_gen.hip", "mgp_backward_wave_gen_f32.hip")},
 }
 
 

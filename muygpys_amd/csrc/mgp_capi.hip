@@ -429,6 +429,26 @@ int hyper_backward_gen_large(const T* feat, int d, const int64_t* bi, const int6
   return launch_hyper_backward_gen_large<T>(g, gnu, ws, ws_bytes, static_cast<hipStream_t>(stream));  // (refuses k + 2 > 1024)
 }
 
+// ... and at wave size (mgp_backward_wave_gen.hip): the same checks in the same order without the workspace's; the
+// launcher refuses k + 2 > 64 and the feature counts beyond its instantiations
+template <typename T>
+int hyper_backward_gen_wave(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k, const T* tg,
+                            int R, int noise_mode, double eps, const T* nd, double smoothness, int metric_id, const T* ls,
+                            int ls_count, const T* gmean, const T* gvar, const T* gyk, T* gls, T* gnz, T* gnu, int* info,
+                            void* stream) {
+  if (!(smoothness > 0.0)) return MGP_EINVAL;
+  BackwardArgs g = BackwardArgs();
+  const int ready = fused_args<T>(g.f, NEED_RESPONSES | KERNEL_IS_GEN, feat, feat, d, bi, ni, b, k, tg, R, noise_mode, eps,
+                                  nd, MGP_KERNEL_MATERN_GEN, metric_id, ls, ls_count, nullptr, nullptr, nullptr, info);
+  if (ready != ARGS_READY) return ready;
+  if (gyk && R != 1) return MGP_EINVAL;  // (the LOOCV losses are defined for one response)
+  if ((!gmean && !gvar && !gyk) || (!gls && !gnz && !gnu)) return MGP_EINVAL;
+  if (smoothness > 30.0) return MGP_EUNSUPPORTED;
+  g.f.smoothness = smoothness;
+  g.grad_mean = gmean, g.grad_var = gvar, g.grad_yk = gyk, g.grad_ls = gls, g.grad_noise = gnz;
+  return launch_hyper_backward_gen_wave<T>(g, gnu, static_cast<hipStream_t>(stream));
+}
+
 // ... and the whole vector-Jacobian product there: two tables, every cotangent of mgp_posterior_backward_*
 template <typename T>
 int posterior_backward_large(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni, int64_t b, int k,
@@ -1023,6 +1043,16 @@ int mgp_backward_gen_large_max_nn_count(int elem_size) {
   }
 MGP_DEFINE_BWD_GEN_LARGE(f32, float)
 MGP_DEFINE_BWD_GEN_LARGE(f64, double)
+#define MGP_DEFINE_BWD_GEN_WAVE(SUF, T)                                                                             \
+  int mgp_hyper_backward_gen_wave_##SUF(const T* feat, int d, const int64_t* bi, const int64_t* ni, int64_t b,       \
+                                        int k, const T* tg, int R, int nm, double eps, const T* nd,                  \
+                                        double smoothness, int mid, const T* ls, int lsc, const T* gmean,            \
+                                        const T* gvar, const T* gyk, T* gls, T* gnz, T* gnu, int* info, void* st) {  \
+    return hyper_backward_gen_wave<T>(feat, d, bi, ni, b, k, tg, R, nm, eps, nd, smoothness, mid, ls, lsc, gmean,    \
+                                      gvar, gyk, gls, gnz, gnu, info, st);                                           \
+  }
+MGP_DEFINE_BWD_GEN_WAVE(f32, float)
+MGP_DEFINE_BWD_GEN_WAVE(f64, double)
 #define MGP_DEFINE_BWD_LARGE_FULL(SUF, T)                                                                          \
   int mgp_posterior_backward_large_##SUF(const T* fq, const T* fn, int d, const int64_t* bi, const int64_t* ni,      \
                                          int64_t b, int k, const T* tg, int R, int nm, double eps, const T* nd,      \

@@ -821,13 +821,20 @@ def _hyper_partials_ns(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_n
 
 # which rung serves the hyper-parameter partials of the general-smoothness Matern first: "slab" (the backward on the slab
 # factor alone, csrc/mgp_backward_gen_large.hip) or "lds" (the LDS workgroup backward, csrc/mgp_backward_gen.hip, with
-# the slab behind it for an nn_count beyond mgp_max_nn_count_backward_gen).  MUYGPYS_HIP_GEN_BACKWARD, unset = slab.
-GEN_BACKWARD_MODES = ("slab", "lds")
+# the slab behind it for an nn_count beyond mgp_max_nn_count_backward_gen) or "wavefront" (the wave-sized backward,
+# csrc/mgp_backward_wave_gen.h, with what "lds" does behind it).  MUYGPYS_HIP_GEN_BACKWARD, unset = slab.
+GEN_BACKWARD_MODES = ("slab", "lds", "wavefront")
 # ... and the largest nn_count at which the "lds" rung is tried, by element size: where it was measured to beat the slab
 # backward (profiles/gen_backward_lds_bench.json, d = 40, 200 000 neighbourhoods, nu = 1.3: fp32 4.0x at nn_count 30 and
 # 2.1x at 63, 0.77x at 100; fp64 2.5x at 30, 0.72x at 63 -- one 128-thread workgroup per CU there).  Nothing was
 # measured between those shapes: the rung ends at the last one it won.
 GEN_BACKWARD_LDS_MAX_NN_COUNT = {4: 63, 8: 30}
+# ... and the same for the "wavefront" rung (profiles/gen_backward_wave_bench.json, 200 000 neighbourhoods, nu = 1.3; the
+# wave-sized launch against the faster of the other two, without / with grad_nu: fp32 at d = 40 3.1x / 2.4x at nn_count 30
+# and 3.0x / 2.8x at 62; fp64 at d = 8 1.9x / 2.3x at 30 and, per-feature scales, 1.4x at 50 without grad_nu -- with it
+# the launcher refuses fp64 beyond 32 slots and the next rung serves the call; the slab's spread was 0.3 % at most).  The
+# rung ends at the largest measured nn_count at which it won.
+GEN_BACKWARD_WAVE_MAX_NN_COUNT = {4: 62, 8: 50}
 
 
 def _gen_backward_from_env() -> str:
@@ -842,7 +849,7 @@ _GEN_BACKWARD = _gen_backward_from_env()
 
 @contextlib.contextmanager
 def gen_backward(mode: str):
-    """``with fused.gen_backward("lds"):`` -- the first rung of the general-smoothness Matern's analytic gradients inside
+    """``with fused.gen_backward("lds"):`` (or ``"wavefront"``) -- the first rung of the general-smoothness Matern's analytic gradients inside
     the block (:func:`loocv_value_and_grad`, :func:`class_value_and_grad` and the optimisers on top of them); the
     previous mode is restored on the way out."""
     global _GEN_BACKWARD
@@ -944,7 +951,8 @@ def _gen_smoothness(spec: KernelSpec) -> float:
 def _hyper_partials_gen(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_noise: bool, want_nu: bool):
     """:func:`_hyper_partials` of the general-smoothness Matern: ``(g_l, g_n or None[, g_nu])``.  The ladder is the
     slab backward alone, or -- :func:`gen_backward` ``"lds"``, up to ``GEN_BACKWARD_LDS_MAX_NN_COUNT`` --
-    ``mgp_posterior_backward_gen_*`` with the slab behind it."""
+    ``mgp_posterior_backward_gen_*`` with the slab behind it, or -- ``"wavefront"``, up to
+    ``GEN_BACKWARD_WAVE_MAX_NN_COUNT`` -- ``mgp_hyper_backward_gen_wave_*`` in front of those two."""
     P = _lib.ptr
     fn, ls = inp.fn, inp.ls
     nu = spec.smoothness
@@ -971,8 +979,15 @@ def _hyper_partials_gen(spec: KernelSpec, inp: _Inputs, info, gm, gv, gyk, want_
         return _lib.fn("hyper_backward_gen_large", fn.dtype)(
             P(fn), *shape, *model, *cotangents, P(g_l), P(g_n), P(g_nu), P(info), P(ws), ws.numel(), _lib.stream_ptr())
 
-    use_lds = _GEN_BACKWARD == "lds" and inp.k <= GEN_BACKWARD_LDS_MAX_NN_COUNT[fn.element_size()]
-    rungs = ((lds, "mgp_posterior_backward_gen"),) if use_lds else ()
+    def wave():
+        return _lib.fn("hyper_backward_gen_wave", fn.dtype)(
+            P(fn), *shape, *model, *cotangents, P(g_l), P(g_n), P(g_nu), P(info), _lib.stream_ptr())
+
+    es = fn.element_size()
+    use_wave = _GEN_BACKWARD == "wavefront" and inp.k <= GEN_BACKWARD_WAVE_MAX_NN_COUNT[es]
+    use_lds = _GEN_BACKWARD in ("lds", "wavefront") and inp.k <= GEN_BACKWARD_LDS_MAX_NN_COUNT[es]
+    rungs = ((wave, "mgp_hyper_backward_gen_wave"),) if use_wave else ()
+    rungs += ((lds, "mgp_posterior_backward_gen"),) if use_lds else ()
     rungs += ((slab, "mgp_hyper_backward_gen_large"),)
     rc, at = _lib.run_ladder([r for r, _ in rungs])
     _lib.check(rc, rungs[at][1])

@@ -32,6 +32,12 @@ Shapes: nn_count = 30, 63 and 100 at d = 40, 200 000 neighbourhoods, otherwise a
 median, smallest and largest of 3 alternating rounds after a warm-up; ``lds_wins`` / ``lds_nu_wins``: the LDS kernel's
 largest time is below the slab's smallest (faster by more than the spread of the repeats).  A shape beyond
 ``mgp_max_nn_count_backward_gen`` is recorded as refused.
+
+``--wave``: the wave-sized backward (csrc/mgp_backward_wave_gen.h, ``mgp_hyper_backward_gen_wave_*``) against both other
+rungs and the forward launch -> profiles/gen_backward_wave_bench.json.  Shapes: fp32 nn_count 30 and 62 at d = 40, fp64
+nn_count 30 and 50 (per-feature length scales) at d = 8, 200 000 neighbourhoods.  All sides alternate in one process, 7
+rounds of 5 calls each, medians of the per-call times; ``spread`` is (max - min) / median of the slab side, and the wave
+launch ``wins`` where it beats BOTH other rungs by more than that spread.  A form the launcher refuses is recorded so.
 """
 
 import argparse
@@ -227,13 +233,110 @@ def one_lds(dtype: str, k: int, d: int, b: int) -> dict:
     return out
 
 
+WAVE_SHAPES = [("float32", 30, 40, False), ("float32", 62, 40, False), ("float64", 30, 8, False), ("float64", 50, 8, True)]
+WAVE_ROUNDS, WAVE_CALLS = 7, 5
+
+
+def one_wave(dtype: str, k: int, d: int, b: int, aniso: bool) -> dict:
+    import statistics
+
+    import torch
+
+    from muygpys_amd import _lib
+    from muygpys_amd.fused import KernelSpec, posterior_mean_var
+
+    t = getattr(torch, dtype)
+    dev = torch.device("cuda:0")
+    n = 20000
+    g = torch.Generator(device=dev).manual_seed(k * 100 + d)
+    X = torch.rand((n, d), device=dev, dtype=t, generator=g)
+    y = (torch.sin(3.0 * X.sum(1)) + 0.1 * torch.randn(n, device=dev, dtype=t, generator=g)).reshape(n, 1).contiguous()
+    ell = 0.5 * max(1.0, (d / 8.0) ** 0.5)
+    ells = [ell * (1.0 + 0.1 * i / d) for i in range(d)] if aniso else [ell]
+    spec = KernelSpec("matern_gen", "l2", ells if aniso else ell, 1e-2, smoothness=NU)
+    starts = torch.randint(0, n - k, (b, 1), device=dev, generator=g)
+    bi = torch.randint(0, n, (b,), device=dev, generator=g)
+    ni = (starts + torch.arange(k, device=dev)[None, :]).contiguous()
+    cot = [torch.randn(b, device=dev, dtype=t, generator=g) for _ in range(3)]
+    ls = torch.tensor(ells, device=dev, dtype=t)
+    P, lib = _lib.ptr, _lib.load()
+    ws = torch.empty(lib.mgp_backward_large_workspace_bytes(X.element_size(), k, b), dtype=torch.uint8, device=dev)
+    g_l = torch.zeros((b, len(ells)), device=dev, dtype=t)
+    g_n = torch.zeros((b, k), device=dev, dtype=t)
+    g_nu = torch.zeros((b,), device=dev, dtype=t)
+    info = torch.zeros(1, dtype=torch.int32, device=dev)
+    shape = (d, P(bi), P(ni), b, k, P(y), 1, 0, 1e-2, None, NU, 0, P(ls), len(ells), *[P(c) for c in cot])
+
+    def call(entry, nu_out):
+        gnu = P(g_nu) if nu_out else None
+        if entry == "slab":
+            return _lib.fn("hyper_backward_gen_large", t)(P(X), *shape, P(g_l), P(g_n), gnu, P(info), P(ws), ws.numel(), _lib.stream_ptr())
+        if entry == "lds":
+            return _lib.fn("posterior_backward_gen", t)(P(X), P(X), *shape, None, None, None, P(g_l), P(g_n), gnu, P(info), _lib.stream_ptr())
+        return _lib.fn("hyper_backward_gen_wave", t)(P(X), *shape, P(g_l), P(g_n), gnu, P(info), _lib.stream_ptr())
+
+    what = {"forward": lambda: posterior_mean_var(spec, X, X, bi, ni, y, want_ykinvy=True, packed=False)}
+    refused = []
+    for entry in ("slab", "lds", "wave"):
+        for nu_out in (False, True):
+            name = entry + ("_nu" if nu_out else "")
+            if call(entry, nu_out) == -2:  # MGP_EUNSUPPORTED: the ladder's next rung serves this form
+                refused.append(name)
+            else:
+                what[name] = lambda e=entry, u=nu_out: _lib.check(call(e, u), e)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(WAVE_CALLS):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / WAVE_CALLS
+
+    kernels = {}
+    for name, fn in what.items():  # warm-up: code objects loaded, every buffer touched
+        timed(fn)
+        kernels[name] = _lib.last_kernel()
+    times = {name: [] for name in what}
+    for _ in range(WAVE_ROUNDS):
+        for name, fn in what.items():
+            times[name].append(timed(fn))
+    assert int(info.item()) == 0, "a neighbourhood did not factorise"
+    out = {"dtype": dtype, "nn_count": k, "features": d, "neighbourhoods": b, "smoothness": NU, "per_feature_length_scale": aniso,
+           "kernels": kernels, "refused": refused}
+    for name, v in times.items():
+        out[name + "_ms"] = {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+    for sfx in ("", "_nu"):
+        s = out["slab" + sfx + "_ms"]
+        out["spread" + sfx] = round((s["max"] - s["min"]) / s["median"], 3)
+        if "wave" + sfx in times:
+            w = out["wave" + sfx + "_ms"]["median"]
+            others = [out[o + sfx + "_ms"]["median"] for o in ("slab", "lds") if o + sfx in times]
+            out["wave" + sfx + "_over_forward"] = round(w / out["forward_ms"]["median"], 2)
+            out["wave" + sfx + "_wins"] = all(w * (1.0 + out["spread" + sfx]) < o for o in others)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--wave", action="store_true", help="the wave-sized backward against both other rungs (see the module docstring)")
     ap.add_argument("--lds", action="store_true", help="the LDS backward against the slab backward (see the module docstring)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--step-timeout", type=int, default=150)
     ap.add_argument("--one", nargs=4, metavar=("DTYPE", "K", "D", "B"))
     a = ap.parse_args()
+    if a.wave:
+        rows = [one_wave(dtype, k, d, 200000, aniso) for dtype, k, d, aniso in WAVE_SHAPES]
+        doc = {"what": "general-smoothness Matern: forward launch, slab / LDS workgroup / wave-sized backward without and with "
+                       "grad_nu, same inputs, one process; HIP events, medians of 7 alternating rounds of 5 calls after a warm-up",
+               "tool": "tools/genbwdbench.py --wave", "rows": rows}
+        with open(a.out or os.path.join(ROOT, "profiles", "gen_backward_wave_bench.json"), "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        for r in rows:
+            print(json.dumps(r), flush=True)
+        return 0
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "gen_backward_lds_bench.json" if a.lds else "gen_backward_bench.json")
     if a.one:
