@@ -6,13 +6,15 @@ model is told about.)
 
     python examples/anisotropic_bayes_pipeline.py [--points 1000000] [--batch 1000000] [--optimizer bayes]
                                                   [--nn-method exact|ivf] [--nlist N] [--nprobe P]
+                                                  [--cell-scan query|block]
 
 Stages (each timed): synthetic data with planted per-feature length scales -> exact k-NN on the
 GPU (fused MFMA scan, fp32 features) -> LOOCV batch -> optimiser over the d length scales (every
 objective evaluation is ONE fused launch + a 7-scalar reduction) -> analytic sigma^2 -> posterior
 mean / variance for held-out points.  ``--points 10000000`` is the BASELINE size.  ``--nn-method ivf`` swaps the exact
 search for the approximate inverted-cell index (fp32, d <= 64, k <= 64) and reports its recall against the exact scan
-on 4 000 sampled batch rows.
+on 4 000 sampled batch rows; ``--cell-scan block`` has it scan the probed cells per block of 128 queries on the matrix
+cores instead of per query.
 """
 
 import argparse
@@ -66,7 +68,8 @@ def synth(n, d, true_ls, gen, noise_std=0.03, features=2048, chunk=1 << 20):
 
 
 def run(points=1_000_000, test_points=100_000, batch=1_000_000, d=8, k=50, optimizer="bayes", seed=0, n_iter=20,
-        init_points=5, verbose=True, x0=1.0, bounds=(0.1, 10.0), nn_method="exact", nlist=None, nprobe=None):
+        init_points=5, verbose=True, x0=1.0, bounds=(0.1, 10.0), nn_method="exact", nlist=None, nprobe=None,
+        cell_scan="query"):
     clock = Clock()
     gen = torch.Generator(device="cuda").manual_seed(seed)
     rng = np.random.default_rng(2)
@@ -78,7 +81,8 @@ def run(points=1_000_000, test_points=100_000, batch=1_000_000, d=8, k=50, optim
     if nn_method == "exact":
         nbrs = clock("k-NN index (norms)", lambda: NN_Wrapper(Xtr32, k))
     else:
-        nbrs = clock(f"k-NN index ({nn_method})", lambda: NN_Wrapper(Xtr32, k, nn_method=nn_method, nlist=nlist, nprobe=nprobe))
+        nbrs = clock(f"k-NN index ({nn_method})", lambda: NN_Wrapper(Xtr32, k, nn_method=nn_method, nlist=nlist, nprobe=nprobe,
+                                                                       cell_scan=cell_scan))
     batch = min(batch, points)
     bi = torch.randperm(points, generator=gen, device="cuda")[:batch].sort().values
     ni = clock(f"k-NN, {batch} batch rows x {points} points", lambda: nbrs.get_batch_nns(bi)[0])
@@ -152,7 +156,7 @@ def run(points=1_000_000, test_points=100_000, batch=1_000_000, d=8, k=50, optim
         rows = torch.randperm(batch, generator=gen, device="cuda")[:4000]
         want = NN_Wrapper(Xtr32, k).get_batch_nns(bi[rows])[0]
         hits = (ni[rows][:, :, None] == want[:, None, :]).any(2).double().mean()
-        out.update(nn_method=nn_method, nlist=nbrs.nlist, nprobe=nbrs.nprobe, recall_at_k=float(hits),
+        out.update(nn_method=nn_method, cell_scan=nbrs.last_cell_scan, nlist=nbrs.nlist, nprobe=nbrs.nprobe, recall_at_k=float(hits),
                    recall_queries=int(rows.numel()), short_queries_of_the_test_search=int(nbrs.last_short.sum()))
     if verbose:
         for name, s in clock.rows:
@@ -171,10 +175,12 @@ if __name__ == "__main__":
     ap.add_argument("--nn-method", default="exact", choices=["exact", "ivf"])
     ap.add_argument("--nlist", type=int, default=None, help="cells of the ivf index (default: round(sqrt(points)), at most 4096)")
     ap.add_argument("--nprobe", type=int, default=None, help="cells every query scans (default: min(nlist, 16))")
+    ap.add_argument("--cell-scan", default="query", choices=["query", "block"],
+                    help="ivf: scan the probed cells per query (vector unit) or per block of 128 queries (matrix cores)")
     ap.add_argument("--out", default="", help="write the result (per-stage seconds included) as JSON to this file")
     a = ap.parse_args()
     res = run(points=a.points, test_points=a.test_points, batch=a.batch, optimizer=a.optimizer, n_iter=a.n_iter,
-              nn_method=a.nn_method, nlist=a.nlist, nprobe=a.nprobe)
+              nn_method=a.nn_method, nlist=a.nlist, nprobe=a.nprobe, cell_scan=a.cell_scan)
     if a.out:
         import json
 

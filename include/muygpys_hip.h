@@ -732,6 +732,33 @@ int mgp_knn_cells_scan(const float* table, int64_t n, int d, const int64_t* cell
                        const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
                        void* stream);
 
+/* The same search with a BLOCK of queries per workgroup on the matrix cores (csrc/mgp_knn_cells_block.hip): 128
+ * consecutive queries walk the union of their probed cells in ascending cell order, the cells staged through LDS in
+ * 64-row tiles, distances by v_mfma_f32_32x32x2_f32 in the Gram form of mgp_knn_scan_f32; a (query, row) pair counts
+ * only where the row's cell is one of that query's probes, so the candidate set is mgp_knn_cells_scan's.  Opt-in
+ * (NN_Wrapper.cell_scan = "block"); queries that share most of their probes (sorted by nearest cell) keep the union small.
+ *   table, n, d, cell_start, nlist, queries, m, nprobe, self_pos: as for mgp_knn_cells_scan
+ *   table_sqn (n + 1) fp32: |x|^2 of every stored row, then ONE +inf (the norm the kernel gives the rows of a tile that
+ *       lie past their cell's end)
+ *   query_sqn (m) fp32: |q|^2
+ *   probes (m, nprobe) int32: the cells each query visits, distinct and SORTED ASCENDING within a row
+ *   skip_cell (m) int64 or NULL: a probed cell the query does not scan (the one its lists were seeded from)
+ *   best_d / best_i (m, k), 1 <= k <= 64, IN/OUT: Gram-form squared distances |q|^2 + |x|^2 - 2 q.x and stored
+ *       positions, UNORDERED.  IN: a list over rows outside the scanned cells (mgp_knn_cells_scan on skip_cell), missing
+ *       entries best_i = -1, best_d = +inf.  OUT: the k smallest by (distance, position) of list + scanned rows; the
+ *       result of a query depends on its own arguments alone, not on the block it sits in.  Entries still -1 mean that
+ *       fewer than k rows were seen.  mgp_knn_finish_f32 re-measures and sorts.
+ *   overflow (m) int32 OUT: 1 for a query whose list was not full (k-th distance +inf) when more than 16 rows of one
+ *       tile passed for it -- rows were dropped, the caller recomputes the query with mgp_knn_cells_scan -- else 0.
+ *       A full list never overflows: the owning wave re-scans the tile against the tightened bound.
+ * MGP_EINVAL for null pointers and sizes out of range, MGP_EUNSUPPORTED for d (a multiple of 4 up to 64), k (<= 64),
+ * n (< 2^31), nlist (<= 4096) or an alignment outside the above: both before any HIP call.  m == 0 is MGP_OK.  No
+ * global atomics, no workgroup waits on another; nothing synchronises. */
+int mgp_knn_cells_scan_block(const float* table, const float* table_sqn, int64_t n, int d, const int64_t* cell_start,
+                             int nlist, const float* queries, const float* query_sqn, int64_t m, const int32_t* probes,
+                             int nprobe, const int64_t* skip_cell, const int64_t* self_pos, int k, float* best_d,
+                             int32_t* best_i, int32_t* overflow, void* stream);
+
 /* Exact search over a rectilinear grid for tables of 1 to 3 features (csrc/mgp_knn_grid.hip): every query walks the
  * cells around its own, shell by shell, until the distance to the faces of the walked block proves its list final.
  * Fills the role of the reference's algorithm="kd_tree" / "ball_tree" (scikit-learn behind NN_Wrapper,

@@ -39,7 +39,13 @@ cell by cell, and every query scans only its ``nprobe`` nearest cells (``mgp_knn
 ``csrc/mgp_knn_cells.hip``).  fp32 only, ``d <= 64``, ``k <= 64``; the neighbours are exact within the probed
 cells and approximate over the table -- good on data with low-dimensional structure (clusters, manifolds), poor on
 data without (i.i.d. Gaussian at d = 40: recall 0.49 at 8 of 64 cells in a CPU simulation).  A query whose probed
-cells hold fewer than k rows is recomputed exactly on the dense path.
+cells hold fewer than k rows is recomputed exactly on the dense path.  ``cell_scan`` (keyword and plain attribute, read
+at every search; ``last_cell_scan`` names what ran) chooses the kernel that scans the probed cells: ``"query"``, the
+default, is one wave per query on the vector unit; ``"block"`` (opt-in) is ``mgp_knn_cells_scan_block``
+(``csrc/mgp_knn_cells_block.hip``): 128 queries per workgroup walk the union of their probed cells on the matrix cores,
+after a per-query scan of each query's nearest cell has seeded the lists.  Same candidate set, same contract;
+``last_overflow`` then holds the block launch's per-query flags, and a flagged query is rescanned by the per-query
+kernel over all its probes.  Any other value is a ``ValueError``.
 
 ``nn_method="exact", algorithm="grid"`` is the exact search for tables of 1 to 3 features (the role of the reference's
 ``algorithm="kd_tree"`` / ``"ball_tree"``, which it hands to scikit-learn; every other value of ``algorithm`` is
@@ -74,6 +80,7 @@ WIDE_MAX_K = 1024      # mgp_knn_wide_max_nn_count(): the longest list of the wi
 LONG_MAX_D = 256       # mgp_knn_long_max_features(): the widest row of the long-row scans (64 < d: csrc/mgp_knn_long.hip)
 CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
 CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
+CELL_SCANS = ("query", "block")  # the cell scans of nn_method="ivf": mgp_knn_cells_scan | mgp_knn_cells_scan_block
 GRID_MAX_D = 3         # most features of the grid walk (3^d cells around a query: csrc/mgp_knn_grid.hip)
 GRID_MAX_CELLS = 1 << 24  # most cells of a grid (mgp_knn_grid_scan's limit): beyond that the cells grow
 GRID_CELL_ROWS = 16    # mean rows per cell of a grid where the caller names none: the sweep's best at 1 M rows
@@ -178,9 +185,11 @@ class NN_Wrapper:
     def __init__(self, train: torch.Tensor, nn_count: int, nn_method: str = "exact", chunk: int = 4096,
                  use_scan: bool = True, scan_kind: str = "auto", shuffle: bool = True, nlist=None, nprobe=None,
                  kmeans_iters: int = 10, seed: int = 0, _cells=None, algorithm=None, edges="uniform",
-                 cell_rows=GRID_CELL_ROWS, **kwargs):
+                 cell_rows=GRID_CELL_ROWS, cell_scan: str = "query", **kwargs):
         if nn_method.lower() not in ("exact", "ivf"):
             raise NotImplementedError(f"Nearest Neighbor algorithm {nn_method} is not implemented.")
+        # which kernel scans the probed cells of nn_method="ivf" (read at search time: A/B on a live object)
+        self.cell_scan = self._check_cell_scan(cell_scan)
         self.algorithm = None  # "grid": the grid walk serves every search (any other value of the keyword is ignored)
         grid = nn_method.lower() == "exact" and algorithm == "grid" and isinstance(train, torch.Tensor)
         if grid:  # (its limits before anything else: they need no device)
@@ -520,6 +529,8 @@ class NN_Wrapper:
         self.nn_count, self.nn_method, self.chunk = k, "ivf", int(chunk)
         self.use_scan, self.scan_kind, self.last_overflow, self.last_route = False, None, None, None
         self.last_short = None  # per query: 1 where the probed cells held fewer than k rows (recomputed exactly)
+        self.last_cell_scan = None  # "query" | "block": the cell scan of the most recent search
+        self._sq_block = None  # the block scan's norms (n + 1: made on its first search)
         self._width = max(4, -(-d // 4) * 4)
         self._mean = table.double().mean(0).to(table.dtype)
         x = self._pad_features(table - self._mean)
@@ -606,9 +617,57 @@ class NN_Wrapper:
         q = self._pad_features(queries.to(self.train.dtype) - self._mean)
         return self._probe(q)[0].to(torch.int64)
 
+    @staticmethod
+    def _check_cell_scan(cell_scan):
+        if cell_scan not in CELL_SCANS:
+            raise ValueError(f"cell_scan must be one of {CELL_SCANS}, got {cell_scan!r}")
+        return cell_scan
+
+    def _cell_scan_query(self, qs, ps, ex, k):
+        """mgp_knn_cells_scan: one wave per query over the cells ``ps`` (m, p) int32 -> (best_d, best_i, short)."""
+        m, dev = qs.shape[0], qs.device
+        best_d = torch.empty((m, k), device=dev, dtype=torch.float32)
+        best_i = torch.empty((m, k), device=dev, dtype=torch.int32)
+        short = torch.empty((m,), device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().mgp_knn_cells_scan(
+            _lib.ptr(self.train), self.train_count, self._width, _lib.ptr(self.cell_start), self.nlist, _lib.ptr(qs), m,
+            _lib.ptr(ps), ps.shape[1], _lib.ptr(ex), k, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(short),
+            _lib.stream_ptr()), "mgp_knn_cells_scan")
+        return best_d, best_i, short
+
+    def _cell_scan_block(self, qs, ps, nearest, ex, k):
+        """The block scan (mgp_knn_cells_scan_block) of queries ordered by nearest cell -> (best_i, short, overflow).
+        Seed: the per-query scan of one cell, the nearest; block: every other probed cell, 128 queries per workgroup
+        on the matrix cores; a query the block scan flags (its seed held fewer than k rows and a queue overflowed) or
+        leaves with an unfilled list is rescanned by the per-query kernel over all its probes."""
+        m, dev = qs.shape[0], qs.device
+        ps = ps.sort(1).values.contiguous()  # the block kernel walks the cells in ascending order
+        seed = nearest.to(torch.int32)
+        # (a tie among centroid distances can leave argmin's cell out of the selected probes: seed from a probed one)
+        seed = torch.where((ps == seed[:, None]).any(1), seed, ps[:, 0]).contiguous()
+        best_d, best_i, short = self._cell_scan_query(qs, seed[:, None].contiguous(), ex, k)
+        if self._sq_block is None:  # |x|^2 per stored row, then the +inf of the rows past a cell's end: made once
+            self._sq_block = torch.cat([self._sq, torch.full((1,), float("inf"), device=dev, dtype=self._sq.dtype)])
+        qn = (qs.double() ** 2).sum(1).to(qs.dtype)
+        skip = seed.to(torch.int64)
+        overflow = torch.empty((m,), device=dev, dtype=torch.int32)
+        _lib.check(_lib.load().mgp_knn_cells_scan_block(
+            _lib.ptr(self.train), _lib.ptr(self._sq_block), self.train_count, self._width, _lib.ptr(self.cell_start),
+            self.nlist, _lib.ptr(qs), _lib.ptr(qn), m, _lib.ptr(ps), self.nprobe, _lib.ptr(skip), _lib.ptr(ex), k,
+            _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr()), "mgp_knn_cells_scan_block")
+        short.zero_()
+        redo = ((overflow != 0) | (best_i < 0).any(1)).nonzero().reshape(-1)
+        if redo.numel():  # still exact within the probed cells; from its `short` flag on, the per-query route's path
+            _, bi, sh = self._cell_scan_query(qs[redo].contiguous(), ps[redo].contiguous(),
+                                              None if ex is None else ex[redo].contiguous(), k)
+            best_i[redo], short[redo] = bi, sh
+        return best_i, short, overflow
+
     def _cells_nns(self, samples, nn_count, exclude=None):
-        """Probe selection, the cell scan, the finish kernel; queries with too few candidates go dense.  Returns the
-        caller's row numbers."""
+        """Probe selection, the cell scan (``cell_scan``: per query, or per block of queries on the matrix cores), the
+        finish kernel; queries with too few candidates go dense.  Returns the caller's row numbers."""
+        scan = self._check_cell_scan(self.cell_scan)
+        self.last_cell_scan, self.last_overflow = scan, None
         q = self._pad_features(samples)
         m, k, dev = q.shape[0], int(nn_count), q.device
         idx = torch.empty((m, k), dtype=torch.int64, device=dev)
@@ -623,13 +682,12 @@ class NN_Wrapper:
         order = nearest.argsort()
         qs, ps = q[order].contiguous(), probes[order].contiguous()
         ex = None if exclude is None else exclude.to(torch.int64)[order].contiguous()
-        best_d = torch.empty((m, k), device=dev, dtype=torch.float32)
-        best_i = torch.empty((m, k), device=dev, dtype=torch.int32)
-        short = torch.empty((m,), device=dev, dtype=torch.int32)
-        _lib.check(_lib.load().mgp_knn_cells_scan(
-            _lib.ptr(self.train), self.train_count, self._width, _lib.ptr(self.cell_start), self.nlist, _lib.ptr(qs), m,
-            _lib.ptr(ps), self.nprobe, _lib.ptr(ex), k, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(short),
-            _lib.stream_ptr()), "mgp_knn_cells_scan")
+        if scan == "block":
+            best_i, short, overflow = self._cell_scan_block(qs, ps, nearest[order], ex, k)
+            self.last_overflow = torch.empty_like(overflow)
+            self.last_overflow[order] = overflow
+        else:
+            _, best_i, short = self._cell_scan_query(qs, ps, ex, k)
         best_i.clamp_(min=0)  # (the -1 of a short list: that query is recomputed below, the finish kernel reads rows)
         si = torch.empty((m, k), dtype=torch.int64, device=dev)
         sd = torch.empty((m, k), dtype=q.dtype, device=dev)

@@ -11,6 +11,13 @@ Every shape runs in a fresh child process under its own time limit; the children
 fails ends the run.  Writes profiles/knn_ivf_bench.json.
 
     python tools/ivfbench.py [--shapes d8_1m d8_10m d40_mixture d40_gaussian] [--repeats 3] [--out FILE]
+
+``--cell-scan block`` measures the block cell scan (``NN_Wrapper.cell_scan = "block"``) instead: per shape and nprobe
+the per-query scan, the block scan and the exact scan alternate in one process for ``--repeats`` rounds after a warm-up
+round, HIP events around the whole call; medians, the block / per-query ratio with the per-query side's
+(max - min) / median next to it, recall of both, the entries in which their results differ, the share of queries the
+block launch flagged in ``last_overflow`` and the mean size of a block's cell union relative to nprobe.  Writes
+profiles/knn_ivf_block_bench.json.
 """
 import argparse
 import json
@@ -117,19 +124,110 @@ def child(name, repeats):
     print("RESULT " + json.dumps(rec), flush=True)
 
 
+def event_ms(fn):
+    import torch
+
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return out, a.elapsed_time(b)
+
+
+def union_per_probe(nn, bi, blocks=512):
+    """Mean number of distinct cells a block of 128 queries (in the search's order: by nearest cell) walks, its seed
+    cells aside, relative to nprobe -- on `blocks` blocks spread evenly over the batch."""
+    import torch
+
+    q = nn.train[nn._inv[bi]]
+    probes, nearest = nn._probe(q)
+    order = nearest.argsort()
+    ps, seed = probes[order].to(torch.int64), nearest[order]
+    nblocks = ps.shape[0] // 128
+    pick = torch.arange(0, nblocks, max(1, nblocks // blocks), device=ps.device)
+    rows = (pick[:, None] * 128 + torch.arange(128, device=ps.device)[None, :]).reshape(-1)
+    keys = (rows // 128)[:, None] * nn.nlist + ps[rows]
+    keys = keys[ps[rows] != seed[rows][:, None]]
+    return float(torch.unique(keys).numel()) / float(pick.numel()) / nn.nprobe
+
+
+def child_block(name, rounds):
+    """The per-query cell scan, the block cell scan and the exact scan, alternating in one process: per nprobe the
+    medians over `rounds` rounds (one warm-up round first), block / query ratios next to the per-query side's spread."""
+    import torch
+
+    from muygpys_amd.neighbors import NN_Wrapper
+
+    n, m, d, k, data, _ = SHAPES[name]
+    gen = torch.Generator(device="cuda").manual_seed(20260 + len(name))
+    X = make_table(n, d, data, gen)
+    bi = torch.randperm(n, generator=gen, device="cuda")[:m].sort().values
+    rows = torch.randperm(m, generator=gen, device="cuda")[:RECALL_QUERIES]
+    rec = {"shape": name, "table_rows": n, "queries": m, "feature_count": d, "nn_count": k, "data": data,
+           "device": torch.cuda.get_device_name(0), "rounds": rounds}
+    exact = NN_Wrapper(X, k)
+    want = exact.get_batch_nns(bi)[0][rows].clone()
+    nn = NN_Wrapper(X, k, nn_method="ivf", nlist=None, nprobe=1)
+    rec["nlist"] = nn.nlist
+
+    def recall(got):
+        return round(float((got[rows][:, :, None] == want[:, None, :]).any(2).double().mean()), 5)
+
+    def stats(ms):
+        return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+    rec["ivf"] = []
+    for nprobe in NPROBES:
+        if nprobe > nn.nlist:
+            continue
+        nn.nprobe = nprobe
+        ms = {"query": [], "block": [], "exact": []}
+        got, over = {}, 0
+        for rnd in range(rounds + 1):  # (round 0 warms up)
+            for side in ("query", "block", "exact"):
+                if side == "exact":
+                    _, t = event_ms(lambda: exact.get_batch_nns(bi))
+                else:
+                    nn.cell_scan = side
+                    (got[side], _), t = event_ms(lambda: nn.get_batch_nns(bi))
+                    if side == "block":
+                        over = int(nn.last_overflow.sum())
+                if rnd:
+                    ms[side].append(t)
+        qs, bs, es = stats(ms["query"]), stats(ms["block"]), stats(ms["exact"])
+        row = {"nprobe": nprobe, "query": qs, "block": bs, "exact": es,
+               "block_over_query_speedup": round(qs["median_ms"] / bs["median_ms"], 3),
+               "query_spread": round((qs["max_ms"] - qs["min_ms"]) / qs["median_ms"], 4),
+               "block_over_exact_speedup": round(es["median_ms"] / bs["median_ms"], 3),
+               "query_over_exact_speedup": round(es["median_ms"] / qs["median_ms"], 3),
+               "recall_at_k": {"query": recall(got["query"]), "block": recall(got["block"])},
+               "entries_that_differ": int((got["query"] != got["block"]).sum()), "entries": int(got["query"].numel()),
+               "overflow_share": round(over / m, 5), "short_queries": int(nn.last_short.sum()),
+               "union_cells_per_probe": round(union_per_probe(nn, bi), 3)}
+        rec["ivf"].append(row)
+        print(json.dumps({"shape": name, **row}), flush=True)
+    print("RESULT " + json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "knn_ivf_bench.json"))
+    ap.add_argument("--cell-scan", default="query", choices=["query", "block"],
+                    help="block: the block cell scan against the per-query one and the exact scan, alternating "
+                         "(--repeats rounds) -> profiles/knn_ivf_block_bench.json")
+    ap.add_argument("--out", default="")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        return child(args.child, args.repeats)
+        return (child_block if args.cell_scan == "block" else child)(args.child, args.repeats)
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", "knn_ivf_block_bench.json" if args.cell_scan == "block" else "knn_ivf_bench.json")
     results = []
     for name in args.shapes:  # chained: a child that fails, faults or runs out of time ends the run
         cmd = ["timeout", "-k", "10", str(SHAPES[name][5]), sys.executable, os.path.abspath(__file__), "--child", name,
-               "--repeats", str(args.repeats)]
+               "--repeats", str(args.repeats), "--cell-scan", args.cell_scan]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         sys.stdout.flush()
@@ -139,7 +237,8 @@ def main():
         results += [json.loads(ln[7:]) for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
-        json.dump({"tool": "tools/ivfbench.py", "nprobes": NPROBES, "shapes": results}, f, indent=1)
+        tool = "tools/ivfbench.py" + (" --cell-scan block" if args.cell_scan == "block" else "")
+        json.dump({"tool": tool, "nprobes": NPROBES, "shapes": results}, f, indent=1)
         f.write("\n")
     return 0 if len(results) == len(args.shapes) else 1
 
