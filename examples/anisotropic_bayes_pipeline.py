@@ -6,7 +6,7 @@ model is told about.)
 
     python examples/anisotropic_bayes_pipeline.py [--points 1000000] [--batch 1000000] [--optimizer bayes]
                                                   [--nn-method exact|ivf] [--nlist N] [--nprobe P]
-                                                  [--cell-scan query|block]
+                                                  [--cell-scan query|block|wide]
 
 Stages (each timed): synthetic data with planted per-feature length scales -> exact k-NN on the
 GPU (fused MFMA scan, fp32 features) -> LOOCV batch -> optimiser over the d length scales (every
@@ -14,7 +14,7 @@ objective evaluation is ONE fused launch + a 7-scalar reduction) -> analytic sig
 mean / variance for held-out points.  ``--points 10000000`` is the BASELINE size.  ``--nn-method ivf`` swaps the exact
 search for the approximate inverted-cell index (fp32, d <= 64, k <= 64) and reports its recall against the exact scan
 on 4 000 sampled batch rows; ``--cell-scan block`` has it scan the probed cells per block of 128 queries on the matrix
-cores instead of per query.
+cores instead of per query, ``--cell-scan wide`` per query with the list in LDS (the scan that serves k up to 1024).
 """
 
 import argparse
@@ -175,8 +175,9 @@ if __name__ == "__main__":
     ap.add_argument("--nn-method", default="exact", choices=["exact", "ivf"])
     ap.add_argument("--nlist", type=int, default=None, help="cells of the ivf index (default: round(sqrt(points)), at most 4096)")
     ap.add_argument("--nprobe", type=int, default=None, help="cells every query scans (default: min(nlist, 16))")
-    ap.add_argument("--cell-scan", default="query", choices=["query", "block"],
-                    help="ivf: scan the probed cells per query (vector unit) or per block of 128 queries (matrix cores)")
+    ap.add_argument("--cell-scan", default="query", choices=["query", "block", "wide"],
+                    help="ivf: scan the probed cells per query (vector unit), per block of 128 queries (matrix cores) or "
+                         "per query with a list of up to 1024 entries in LDS (wide)")
     ap.add_argument("--out", default="", help="write the result (per-stage seconds included) as JSON to this file")
     a = ap.parse_args()
     res = run(points=a.points, test_points=a.test_points, batch=a.batch, optimizer=a.optimizer, n_iter=a.n_iter,

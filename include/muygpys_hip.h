@@ -732,6 +732,26 @@ int mgp_knn_cells_scan(const float* table, int64_t n, int d, const int64_t* cell
                        const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
                        void* stream);
 
+/* The same per-query scan for k-best lists of up to 1 024 entries (csrc/mgp_knn_cells_wide.hip): the reference's
+ * approximate branch takes any nn_count (hnswlib behind NN_Wrapper, src/MuyGPyS/neighbors.py:109-127 build, :213-262
+ * query), and the posterior entries above serve nn_count + 1 + response_count <= 1024.  Opt-in
+ * (NN_Wrapper.cell_scan = "wide").
+ *   mgp_knn_cells_wide_max_nn_count   the largest k the entry below takes: 1024.
+ *   mgp_knn_cells_scan_wide           the parameters and the whole contract of mgp_knn_cells_scan -- table, cell_start,
+ *       probes (entries outside [0, nlist) are skipped), self_pos, best_d / best_i (m, k) UNORDERED with -1 / +inf for
+ *       missing entries, short_flag; the same fp32 difference-form distances, bit for bit; the k smallest by (distance,
+ *       stored position) of the candidate set -- for 1 <= k <= 1024.  One wave per query; its list lives in LDS,
+ *       64 ceil(k / 64) slots plus max(128, half of that) for the rows admitted since the last selection, sized at launch
+ *       (48 KiB per workgroup at k = 1024).  mgp_knn_finish_wide (mgp_knn_finish_f32 up to k = 64) re-measures and sorts.
+ * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), nothing to do (m == 0: MGP_OK, pointers not looked
+ * at), NULL pointers (MGP_EINVAL; self_pos and the stream are optional), then MGP_EUNSUPPORTED for k > 1024, d outside
+ * {4, 8, .. 64}, n >= 2^31 and alignment.  Nothing synchronises. */
+int mgp_knn_cells_wide_max_nn_count(void);
+int mgp_knn_cells_scan_wide(const float* table, int64_t n, int d, const int64_t* cell_start, int nlist,
+                            const float* queries, int64_t m, const int32_t* probes, int nprobe,
+                            const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
+                            void* stream);
+
 /* The same search with a BLOCK of queries per workgroup on the matrix cores (csrc/mgp_knn_cells_block.hip): 128
  * consecutive queries walk the union of their probed cells in ascending cell order, the cells staged through LDS in
  * 64-row tiles, distances by v_mfma_f32_32x32x2_f32 in the Gram form of mgp_knn_scan_f32; a (query, row) pair counts

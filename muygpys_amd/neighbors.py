@@ -36,7 +36,8 @@ distances carry no cancellation error and ties resolve by distance then index or
 ``nn_method="ivf"`` is the approximate search (the role of the reference's ``nn_method="hnsw"``,
 neighbors.py:109-127,213-262; a graph walk suits a GPU badly): k-means cells over the table, the table stored
 cell by cell, and every query scans only its ``nprobe`` nearest cells (``mgp_knn_cells_scan``,
-``csrc/mgp_knn_cells.hip``).  fp32 only, ``d <= 64``, ``k <= 64``; the neighbours are exact within the probed
+``csrc/mgp_knn_cells.hip``).  fp32 only, ``d <= 64``, ``k <= 64`` (``k <= 1024`` under ``cell_scan="wide"``); the
+neighbours are exact within the probed
 cells and approximate over the table -- good on data with low-dimensional structure (clusters, manifolds), poor on
 data without (i.i.d. Gaussian at d = 40: recall 0.49 at 8 of 64 cells in a CPU simulation).  A query whose probed
 cells hold fewer than k rows is recomputed exactly on the dense path.  ``cell_scan`` (keyword and plain attribute, read
@@ -45,7 +46,9 @@ default, is one wave per query on the vector unit; ``"block"`` (opt-in) is ``mgp
 (``csrc/mgp_knn_cells_block.hip``): 128 queries per workgroup walk the union of their probed cells on the matrix cores,
 after a per-query scan of each query's nearest cell has seeded the lists.  Same candidate set, same contract;
 ``last_overflow`` then holds the block launch's per-query flags, and a flagged query is rescanned by the per-query
-kernel over all its probes.  Any other value is a ``ValueError``.
+kernel over all its probes.  ``"wide"`` (opt-in) is ``mgp_knn_cells_scan_wide`` (``csrc/mgp_knn_cells_wide.hip``): the
+per-query scan with its list in LDS, ``1 <= k <= 1024`` -- the only cell scan past ``k = 64``; its winners are ordered
+by ``mgp_knn_finish_wide`` there.  Any other value is a ``ValueError``.
 
 ``nn_method="exact", algorithm="grid"`` is the exact search for tables of 1 to 3 features (the role of the reference's
 ``algorithm="kd_tree"`` / ``"ball_tree"``, which it hands to scikit-learn; every other value of ``algorithm`` is
@@ -80,7 +83,9 @@ WIDE_MAX_K = 1024      # mgp_knn_wide_max_nn_count(): the longest list of the wi
 LONG_MAX_D = 256       # mgp_knn_long_max_features(): the widest row of the long-row scans (64 < d: csrc/mgp_knn_long.hip)
 CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
 CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
-CELL_SCANS = ("query", "block")  # the cell scans of nn_method="ivf": mgp_knn_cells_scan | mgp_knn_cells_scan_block
+# the cell scans of nn_method="ivf": mgp_knn_cells_scan | mgp_knn_cells_scan_block | mgp_knn_cells_scan_wide
+CELL_SCANS = ("query", "block", "wide")
+CELLS_WIDE_MAX_K = 1024  # mgp_knn_cells_wide_max_nn_count(): the longest list of cell_scan="wide"; the others stop at 64
 GRID_MAX_D = 3         # most features of the grid walk (3^d cells around a query: csrc/mgp_knn_grid.hip)
 GRID_MAX_CELLS = 1 << 24  # most cells of a grid (mgp_knn_grid_scan's limit): beyond that the cells grow
 GRID_CELL_ROWS = 16    # mean rows per cell of a grid where the caller names none: the sweep's best at 1 M rows
@@ -521,15 +526,14 @@ class NN_Wrapper:
             raise ValueError(f"nn_method='ivf' serves float32 tables only (fp32 only), got {table.dtype}")
         if d > 64:
             raise ValueError(f"nn_method='ivf' serves at most 64 features (d <= 64), got d = {d}")
-        if not 1 <= k <= 64:
-            raise ValueError(f"nn_method='ivf' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+        self._check_cells_k(k, self.cell_scan)
         if not 1 <= n < 2**31:
             raise ValueError(f"nn_method='ivf' serves 1 <= n < 2^31 table rows, got n = {n}")
         self.train_count, self.feature_count = n, d
         self.nn_count, self.nn_method, self.chunk = k, "ivf", int(chunk)
         self.use_scan, self.scan_kind, self.last_overflow, self.last_route = False, None, None, None
         self.last_short = None  # per query: 1 where the probed cells held fewer than k rows (recomputed exactly)
-        self.last_cell_scan = None  # "query" | "block": the cell scan of the most recent search
+        self.last_cell_scan = None  # "query" | "block" | "wide": the cell scan of the most recent search
         self._sq_block = None  # the block scan's norms (n + 1: made on its first search)
         self._width = max(4, -(-d // 4) * 4)
         self._mean = table.double().mean(0).to(table.dtype)
@@ -623,16 +627,28 @@ class NN_Wrapper:
             raise ValueError(f"cell_scan must be one of {CELL_SCANS}, got {cell_scan!r}")
         return cell_scan
 
-    def _cell_scan_query(self, qs, ps, ex, k):
-        """mgp_knn_cells_scan: one wave per query over the cells ``ps`` (m, p) int32 -> (best_d, best_i, short)."""
+    @staticmethod
+    def _check_cells_k(k, cell_scan):
+        """The list length the cell scan ``cell_scan`` serves: 64, the width of a wave -- 1024 under "wide"."""
+        if cell_scan == "wide":
+            if not 1 <= k <= CELLS_WIDE_MAX_K:
+                raise ValueError(f"nn_method='ivf' with cell_scan='wide' serves 1 <= nn_count <= {CELLS_WIDE_MAX_K} "
+                                 f"(k <= {CELLS_WIDE_MAX_K}), got k = {k}")
+        elif not 1 <= k <= 64:
+            raise ValueError(f"nn_method='ivf' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+
+    def _cell_scan_query(self, qs, ps, ex, k, wide=False):
+        """mgp_knn_cells_scan (``wide``: mgp_knn_cells_scan_wide, the same contract up to k = 1024): one wave per query
+        over the cells ``ps`` (m, p) int32 -> (best_d, best_i, short)."""
         m, dev = qs.shape[0], qs.device
         best_d = torch.empty((m, k), device=dev, dtype=torch.float32)
         best_i = torch.empty((m, k), device=dev, dtype=torch.int32)
         short = torch.empty((m,), device=dev, dtype=torch.int32)
-        _lib.check(_lib.load().mgp_knn_cells_scan(
+        name = "mgp_knn_cells_scan_wide" if wide else "mgp_knn_cells_scan"
+        _lib.check(getattr(_lib.load(), name)(
             _lib.ptr(self.train), self.train_count, self._width, _lib.ptr(self.cell_start), self.nlist, _lib.ptr(qs), m,
             _lib.ptr(ps), ps.shape[1], _lib.ptr(ex), k, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(short),
-            _lib.stream_ptr()), "mgp_knn_cells_scan")
+            _lib.stream_ptr()), name)
         return best_d, best_i, short
 
     def _cell_scan_block(self, qs, ps, nearest, ex, k):
@@ -664,8 +680,9 @@ class NN_Wrapper:
         return best_i, short, overflow
 
     def _cells_nns(self, samples, nn_count, exclude=None):
-        """Probe selection, the cell scan (``cell_scan``: per query, or per block of queries on the matrix cores), the
-        finish kernel; queries with too few candidates go dense.  Returns the caller's row numbers."""
+        """Probe selection, the cell scan (``cell_scan``: per query, per block of queries on the matrix cores, or per query
+        with a list of up to 1024 entries), the finish kernel; queries with too few candidates go dense.  Returns the
+        caller's row numbers."""
         scan = self._check_cell_scan(self.cell_scan)
         self.last_cell_scan, self.last_overflow = scan, None
         q = self._pad_features(samples)
@@ -675,8 +692,7 @@ class NN_Wrapper:
         self.last_short = torch.zeros((m,), dtype=torch.int32, device=dev)
         if m == 0:
             return idx, dist
-        if not 1 <= k <= 64:
-            raise ValueError(f"nn_method='ivf' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
+        self._check_cells_k(k, scan)
         probes, nearest = self._probe(q)
         # queries in order of their nearest cell: consecutive workgroups meet the same cells in L2
         order = nearest.argsort()
@@ -687,13 +703,14 @@ class NN_Wrapper:
             self.last_overflow = torch.empty_like(overflow)
             self.last_overflow[order] = overflow
         else:
-            _, best_i, short = self._cell_scan_query(qs, ps, ex, k)
+            _, best_i, short = self._cell_scan_query(qs, ps, ex, k, wide=scan == "wide")
         best_i.clamp_(min=0)  # (the -1 of a short list: that query is recomputed below, the finish kernel reads rows)
         si = torch.empty((m, k), dtype=torch.int64, device=dev)
         sd = torch.empty((m, k), dtype=q.dtype, device=dev)
-        _lib.check(_lib.load().mgp_knn_finish_f32(_lib.ptr(qs), _lib.ptr(self.train), self._width, _lib.ptr(best_i), m, k,
-                                                  _lib.ptr(self._perm), _lib.ptr(si), _lib.ptr(sd), _lib.stream_ptr()),
-                   "mgp_knn_finish_f32")
+        finish = "mgp_knn_finish_wide" if k > 64 else "mgp_knn_finish_f32"  # (one workgroup / one wave per query)
+        _lib.check(getattr(_lib.load(), finish)(_lib.ptr(qs), _lib.ptr(self.train), self._width, _lib.ptr(best_i), m, k,
+                                                _lib.ptr(self._perm), _lib.ptr(si), _lib.ptr(sd), _lib.stream_ptr()),
+                   finish)
         redo = short.nonzero().reshape(-1)
         if redo.numel():  # exactly, over the whole table (as the exact scan treats its overflow flags)
             ri, rd = self._dense_nns(qs[redo], k, None if ex is None else ex[redo])

@@ -18,6 +18,12 @@ round, HIP events around the whole call; medians, the block / per-query ratio wi
 (max - min) / median next to it, recall of both, the entries in which their results differ, the share of queries the
 block launch flagged in ``last_overflow`` and the mean size of a block's cell union relative to nprobe.  Writes
 profiles/knn_ivf_block_bench.json.
+
+``--cell-scan wide --nn-count K [K ...]`` measures the wide cell scan (``cell_scan="wide"``, 1 <= K <= 1024) against the
+exact wide scan (``last_route == "wide"``) of the same table: per shape, K and nprobe the two alternate in one process
+for ``--repeats`` rounds after a warm-up round; medians, the exact / index ratio with the exact side's
+(max - min) / median next to it, recall@K on 4 000 sampled queries, the index build time.  Writes
+profiles/knn_ivf_wide_bench.json.
 """
 import argparse
 import json
@@ -210,25 +216,87 @@ def child_block(name, rounds):
     print("RESULT " + json.dumps(rec), flush=True)
 
 
+def child_wide(name, rounds, k):
+    """The wide cell scan (cell_scan="wide") at nn_count = k and the exact wide scan, alternating in one process: per
+    nprobe the medians over `rounds` rounds (one warm-up round first), exact / index ratio next to the exact side's
+    spread, recall against the exact result."""
+    import torch
+
+    from muygpys_amd.neighbors import NN_Wrapper
+
+    n, m, d, _, data, _ = SHAPES[name]
+    gen = torch.Generator(device="cuda").manual_seed(20260 + len(name))
+    X = make_table(n, d, data, gen)
+    bi = torch.randperm(n, generator=gen, device="cuda")[:m].sort().values
+    rows = torch.randperm(m, generator=gen, device="cuda")[:RECALL_QUERIES]
+    rec = {"shape": name, "table_rows": n, "queries": m, "feature_count": d, "nn_count": k, "data": data,
+           "device": torch.cuda.get_device_name(0), "rounds": rounds}
+    exact = NN_Wrapper(X, k)
+    want = exact.get_batch_nns(bi)[0][rows].clone()
+    rec["exact_route"] = exact.last_route
+    if k > 64 and exact.last_route != "wide":
+        raise RuntimeError(f"the yardstick is the exact wide scan, got last_route = {exact.last_route!r}")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    nn = NN_Wrapper(X, k, nn_method="ivf", nlist=None, nprobe=1, cell_scan="wide")
+    torch.cuda.synchronize()
+    rec["ivf_build_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
+    rec["nlist"] = nn.nlist
+
+    def stats(ms):
+        return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+    rec["ivf"] = []
+    for nprobe in NPROBES:
+        if nprobe > nn.nlist:
+            continue
+        nn.nprobe = nprobe
+        ms = {"wide": [], "exact": []}
+        for rnd in range(rounds + 1):  # (round 0 warms up)
+            (got, _), t = event_ms(lambda: nn.get_batch_nns(bi))
+            got = got[rows].clone()
+            _, te = event_ms(lambda: exact.get_batch_nns(bi))
+            if rnd:
+                ms["wide"].append(t)
+                ms["exact"].append(te)
+        ws, es = stats(ms["wide"]), stats(ms["exact"])
+        row = {"nprobe": nprobe, "wide": ws, "exact": es,
+               "wide_over_exact_speedup": round(es["median_ms"] / ws["median_ms"], 3),
+               "exact_spread": round((es["max_ms"] - es["min_ms"]) / es["median_ms"], 4),
+               # (in slices of 256 queries: the (queries, k, k) comparison is 4 GB at k = 1023)
+               "recall_at_k": round(sum(float((got[s:s + 256, :, None] == want[s:s + 256, None, :]).any(2).sum())
+                                        for s in range(0, len(got), 256)) / got.numel(), 5),
+               "short_queries": int(nn.last_short.sum()), "share_of_table_scanned": round(nprobe / nn.nlist, 5)}
+        rec["ivf"].append(row)
+        print(json.dumps({"shape": name, "nn_count": k, **row}), flush=True)
+    print("RESULT " + json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--cell-scan", default="query", choices=["query", "block"],
+    ap.add_argument("--cell-scan", default="query", choices=["query", "block", "wide"],
                     help="block: the block cell scan against the per-query one and the exact scan, alternating "
-                         "(--repeats rounds) -> profiles/knn_ivf_block_bench.json")
+                         "(--repeats rounds) -> profiles/knn_ivf_block_bench.json; wide: the wide cell scan at "
+                         "--nn-count against the exact wide scan, alternating -> profiles/knn_ivf_wide_bench.json")
+    ap.add_argument("--nn-count", type=int, nargs="+", default=[100], help="--cell-scan wide: the list lengths (1 .. 1024)")
     ap.add_argument("--out", default="")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child and args.cell_scan == "wide":
+        return child_wide(args.child, args.repeats, args.nn_count[0])
     if args.child:
         return (child_block if args.cell_scan == "block" else child)(args.child, args.repeats)
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", "knn_ivf_block_bench.json" if args.cell_scan == "block" else "knn_ivf_bench.json")
+        args.out = os.path.join(ROOT, "profiles", {"block": "knn_ivf_block_bench.json", "wide": "knn_ivf_wide_bench.json"}
+                                .get(args.cell_scan, "knn_ivf_bench.json"))
     results = []
-    for name in args.shapes:  # chained: a child that fails, faults or runs out of time ends the run
+    runs = [(name, k) for name in args.shapes for k in (args.nn_count if args.cell_scan == "wide" else [None])]
+    for name, k in runs:  # chained: a child that fails, faults or runs out of time ends the run
         cmd = ["timeout", "-k", "10", str(SHAPES[name][5]), sys.executable, os.path.abspath(__file__), "--child", name,
                "--repeats", str(args.repeats), "--cell-scan", args.cell_scan]
-        p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        p = subprocess.run(cmd + ([] if k is None else ["--nn-count", str(k)]), stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         sys.stdout.flush()
         if p.returncode != 0:
@@ -237,10 +305,10 @@ def main():
         results += [json.loads(ln[7:]) for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
-        tool = "tools/ivfbench.py" + (" --cell-scan block" if args.cell_scan == "block" else "")
+        tool = "tools/ivfbench.py" + (f" --cell-scan {args.cell_scan}" if args.cell_scan != "query" else "")
         json.dump({"tool": tool, "nprobes": NPROBES, "shapes": results}, f, indent=1)
         f.write("\n")
-    return 0 if len(results) == len(args.shapes) else 1
+    return 0 if len(results) == len(runs) else 1
 
 
 if __name__ == "__main__":
