@@ -22,35 +22,9 @@
 // Distances in the lists are the Gram form |q|^2 + |x|^2 - 2 q.x; the host re-measures the k
 // winners in difference form and sorts them (as the dense path does).
 #include "mgp_args.h"
+#include "mgp_knn_tile.h"
 
 namespace mgp {
-
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4x __attribute__((ext_vector_type(4)));
-
-constexpr int KNN_TN = 64;    // training rows per staged tile
-constexpr int KNN_QW = 32;    // queries per wave
-constexpr int KNN_QB = 128;   // queries per workgroup
-constexpr int KNN_CAP = 16;   // queue entries per query
-
-// 16 bytes per lane from global memory straight into LDS at (wave-uniform byte offset) + 16 * lane.
-// Raw instruction on purpose: through the builtin the compiler orders every later LDS write (the
-// candidate queues) behind the transfer with s_waitcnt vmcnt(0), i.e. a full memory latency inside
-// the compare loop for one block in six; the kernels wait for their tiles explicitly instead.
-__device__ __forceinline__ void lds_dma16(const void* gsrc, unsigned lds_byte_offset) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
-               :
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_byte_offset))
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_offset(const void* p) { return (unsigned)(uintptr_t)p; }
-
-template <typename T>
-__device__ __forceinline__ T wave_max(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
-}
 
 template <int DP>
 __global__ __launch_bounds__(256) void knn_scan_kernel(KnnArgs a) {
@@ -98,32 +72,20 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(KnnArgs a) {
     }
   }
   __syncthreads();
-  // accumulator register v of this lane belongs to query row  8 (v/4) + 4 half + v%4  of the wave
   float qn[16], thr[16];
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int row = 8 * (v >> 2) + 4 * half + (v & 3);
+    const int row = tile_acc_row(v, half);
     const int64_t q = qbase + w * KNN_QW + row;
     qn[v] = q < a.m ? a.query_sqn[q] : 0.f;
     thr[v] = 0.5f * (qn[v] - tau_s[w * KNN_QW + row]);
   }
 
-  // Double-buffered staging with direct global->LDS loads: the tile after the current one is in
-  // flight while the MFMAs run, one barrier per tile.  A wave-instruction fills 64 consecutive
-  // 16-byte slots; slot sigma of a tile is row sigma / SPR, column sigma % SPR (the padding column
-  // and the columns past d repeat the row's last data slot -- finite values the zero-padded query
-  // operand cancels).  Rows past n repeat row n-1; their |x|^2 is +inf (host-padded table).
-  constexpr int SPR = XS / 4;
-  constexpr int NPASS = (KNN_TN * SPR + 63) / 64;
+  // Double-buffered staging (tile_stage_rows): the tile after the current one is in flight while the MFMAs run, one
+  // barrier per tile.  Rows past n repeat row n-1; their |x|^2 is +inf (host-padded table).
   const int dslots = d / 4;
   auto issue_tile = [&](int buf, int64_t t0) {
-    for (int p = w; p < NPASS; p += 4) {
-      const int sigma = 64 * p + lane;
-      const int row = min(sigma / SPR, KNN_TN - 1);
-      const int c = min(sigma - row * SPR, dslots - 1);
-      const int64_t grow = min(t0 + row, a.n - 1);
-      lds_dma16(a.train + grow * (int64_t)d + c * 4, lds_offset(tile0 + buf * KNN_TN * XS) + p * 1024);
-    }
+    tile_stage_rows<DP>(tile0 + buf * KNN_TN * XS, a.train, a.n, d, dslots, t0, w, lane);
     if (w == 3 && lane < KNN_TN / 4) lds_dma16(a.train_sqn + t0 + lane * 4, lds_offset(xn0 + buf * KNN_TN));
   };
   // Every workgroup walks the whole table, but starts at its own tile and wraps around: in lockstep
@@ -145,8 +107,6 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(KnnArgs a) {
     const float* tl = tile0 + buf * KNN_TN * XS;
     const float* xnt = xn0 + buf * KNN_TN;
 
-    // ---- two 32 x 32 blocks per wave: both MFMA chains are issued before the first accumulator is
-    // read, so the compares of block 0 run under the MFMAs of block 1 ----------------------------
     f16x acc2[KNN_TN / 32];
 #pragma unroll
     for (int ct = 0; ct < KNN_TN / 32; ++ct) {
@@ -317,7 +277,6 @@ namespace mgp {
 #endif
 
 typedef __bf16 bf8x __attribute__((ext_vector_type(8)));
-typedef unsigned int u4x __attribute__((ext_vector_type(4)));
 
 constexpr int KB_RB = 32;     // queries per row block (one 32 x 32 matrix tile's rows)
 constexpr int KB_CAP = 16;    // queue entries per query

@@ -1,8 +1,8 @@
 // Approximate k-NN over the inverted-cell (IVF) index: the BLOCK scan of the probed cells, on the matrix cores.
 //
-// mgp_knn_cells.hip serves one query per wave on the vector unit.  This kernel reuses the structure of the exact scan
-// (knn_scan_kernel, mgp_knn.hip) and streams a different thing through it: not the whole table, but the union of the
-// cells that the workgroup's queries probe.
+// mgp_knn_cells.hip serves one query per wave on the vector unit.  This kernel is built on the tile of the exact scan
+// (knn_scan_kernel, mgp_knn.hip; the shared pieces are in mgp_knn_tile.h) and streams a different thing through it: not
+// the whole table, but the union of the cells that the workgroup's queries probe.
 //
 //   work split  a workgroup of four waves owns 128 consecutive queries, 32 per wave; their feature rows are the resident
 //               MFMA A operand (v_mfma_f32_32x32x2_f32, fp32 in / fp32 accumulate).  The caller orders the queries by
@@ -55,18 +55,12 @@
 
 #include "mgp_args.h"
 #include "mgp_knn_list.h"
+#include "mgp_knn_tile.h"
 
 namespace mgp {
 
 namespace {
 
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4x __attribute__((ext_vector_type(4)));
-
-constexpr int CB_TN = 64;      // table rows per staged tile
-constexpr int CB_QW = 32;      // queries per wave
-constexpr int CB_QB = 128;     // queries per workgroup
-constexpr int CB_CAP = 16;     // queue entries per query (KNN_CAP of the exact scan)
 constexpr int CB_WORDS = 128;  // bitmap words: nlist <= 4 096
 
 struct CellBlockArgs {
@@ -85,29 +79,6 @@ struct CellBlockArgs {
   int nlist, nprobe, k, d;
 };
 
-// 16 / 4 bytes per lane from global memory straight into LDS at (wave-uniform byte offset) + 16 / 4 * lane; raw
-// instructions for the reason given at lds_dma16 in mgp_knn.hip (the kernel waits for its tiles explicitly)
-__device__ __forceinline__ void cb_dma16(const void* gsrc, unsigned lds_byte_offset) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
-               :
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_byte_offset))
-               : "memory");
-}
-__device__ __forceinline__ void cb_dma4(const void* gsrc, unsigned lds_byte_offset) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dword %0, off"
-               :
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_byte_offset))
-               : "memory");
-}
-__device__ __forceinline__ unsigned cb_lds_offset(const void* p) { return (unsigned)(uintptr_t)p; }
-
-template <typename T>
-__device__ __forceinline__ T cb_wave_max(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 struct CellTile {
   int64_t t0, end;  // first row of the tile, end of its cell
   int cell;
@@ -120,24 +91,24 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
   constexpr int HD = DP / 2;  // features per lane half
   // one extern array carved by hand, see knn_scan_kernel
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* tile0 = reinterpret_cast<float*>(smem);                    // [2][CB_TN * XS]
-  float* xn0 = tile0 + 2 * CB_TN * XS;                              // [2][CB_TN]
-  float* q_d = xn0 + 2 * CB_TN;                                     // [CB_QB * CB_CAP]
-  int* q_i = reinterpret_cast<int*>(q_d + CB_QB * CB_CAP);          // [CB_QB * CB_CAP]
-  int* q_cnt = q_i + CB_QB * CB_CAP;                                // [CB_QB]
-  float* tau_s = reinterpret_cast<float*>(q_cnt + CB_QB);           // [CB_QB] the k-th best of every query
-  float* eff_s = tau_s + CB_QB;                                     // [CB_QB] ... or -inf where the cell is not probed
-  unsigned* bitmap = reinterpret_cast<unsigned*>(eff_s + CB_QB);    // [CB_WORDS] the union of the probed cells
+  float* tile0 = reinterpret_cast<float*>(smem);                          // [2][KNN_TN * XS]
+  float* xn0 = tile0 + 2 * KNN_TN * XS;                                   // [2][KNN_TN]
+  float* q_d = xn0 + 2 * KNN_TN;                                          // [KNN_QB * KNN_CAP]
+  int* q_i = reinterpret_cast<int*>(q_d + KNN_QB * KNN_CAP);              // [KNN_QB * KNN_CAP]
+  int* q_cnt = q_i + KNN_QB * KNN_CAP;                                    // [KNN_QB]
+  float* tau_s = reinterpret_cast<float*>(q_cnt + KNN_QB);                // [KNN_QB] the k-th best of every query
+  float* eff_s = tau_s + KNN_QB;                                          // [KNN_QB] ... or -inf where the cell is not probed
+  unsigned* bitmap = reinterpret_cast<unsigned*>(eff_s + KNN_QB);         // [CB_WORDS] the union of the probed cells
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5, r32 = lane & 31;
-  const int64_t qbase = (int64_t)blockIdx.x * CB_QB;
+  const int64_t qbase = (int64_t)blockIdx.x * KNN_QB;
   const int d = a.d, k = a.k;
   const float inf = __builtin_inff();
 
   // ---- per-query state, the union of the probed cells ------------------------------------------------------------
-  if (tid < CB_QB) {
+  if (tid < KNN_QB) {
     const int64_t q = qbase + tid;
     float t = -inf;  // rows past the end never accept anything
     if (q < a.m) {
@@ -152,7 +123,7 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
   }
   __syncthreads();
   {
-    const int slot = tid & (CB_QB - 1);
+    const int slot = tid & (KNN_QB - 1);
     const int64_t q = qbase + slot;
     if (q < a.m) {
       const int* pr = a.probes + q * (int64_t)a.nprobe;
@@ -166,7 +137,7 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
   // A operand: lane (r32, half) holds features [half*HD, half*HD + HD) of query qbase + 32 w + r32
   float aq[HD];
   {
-    const int64_t q = qbase + w * CB_QW + r32;
+    const int64_t q = qbase + w * KNN_QW + r32;
     const float* qrow = a.queries + (q < a.m ? q : 0) * (int64_t)d;
 #pragma unroll
     for (int j = 0; j < HD / 4; ++j) {
@@ -176,22 +147,21 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
       aq[4 * j] = v.x, aq[4 * j + 1] = v.y, aq[4 * j + 2] = v.z, aq[4 * j + 3] = v.w;
     }
   }
-  // accumulator register v of this lane belongs to query row  8 (v/4) + 4 half + v%4  of the wave
   float qn[16], thr[16];
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int64_t q = qbase + w * CB_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+    const int64_t q = qbase + w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
     qn[v] = q < a.m ? a.query_sqn[q] : 0.f;
     thr[v] = inf;
   }
   auto load_thr = [&]() {
 #pragma unroll
-    for (int v = 0; v < 16; ++v) thr[v] = 0.5f * (qn[v] - eff_s[w * CB_QW + 8 * (v >> 2) + 4 * half + (v & 3)]);
+    for (int v = 0; v < 16; ++v) thr[v] = 0.5f * (qn[v] - eff_s[w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3)]);
   };
   // the membership cursor of query 32 w + lane (lanes 0 .. 31): pv = probes[q][pc], the first one not yet passed
-  const int myslot = w * CB_QW + r32;
+  const int myslot = w * KNN_QW + r32;
   const int64_t myq = qbase + myslot;
-  const bool owner = lane < CB_QW && myq < a.m;
+  const bool owner = lane < KNN_QW && myq < a.m;
   const int* mypr = a.probes + (owner ? myq : 0) * (int64_t)a.nprobe;
   const int64_t myskip = owner && a.skip_cell ? a.skip_cell[myq] : (int64_t)-1;
   int pc = 0;
@@ -221,27 +191,17 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
       fresh = true;
     }
     t.t0 = r, t.end = e, t.cell = cell, t.fresh = fresh;
-    r += CB_TN;
+    r += KNN_TN;
     return true;
   };
-  // A wave-instruction fills 64 consecutive 16-byte slots; slot sigma of a tile is row sigma / SPR, column sigma % SPR
-  // (the padding column and the columns past d repeat the row's last data slot -- finite values the zero-padded query
-  // operand cancels).  Rows past the cell's end are read as they are (rows of the next cell; past n, row n - 1) and
-  // masked by their norm alone.
-  constexpr int SPR = XS / 4;
-  constexpr int NPASS = (CB_TN * SPR + 63) / 64;
+  // staging (tile_stage_rows): rows past the cell's end are read as they are (rows of the next cell; past n, row n - 1)
+  // and masked by their norm alone
   const int dslots = d / 4;
   auto issue_tile = [&](int buf, const CellTile& t) {
-    for (int p = w; p < NPASS; p += 4) {
-      const int sigma = 64 * p + lane;
-      const int row = min(sigma / SPR, CB_TN - 1);
-      const int c = min(sigma - row * SPR, dslots - 1);
-      const int64_t grow = min(t.t0 + row, a.n - 1);
-      cb_dma16(a.table + grow * (int64_t)d + c * 4, cb_lds_offset(tile0 + buf * CB_TN * XS) + p * 1024);
-    }
+    tile_stage_rows<DP>(tile0 + buf * KNN_TN * XS, a.table, a.n, d, dslots, t.t0, w, lane);
     if (w == 3) {
       const int64_t row = t.t0 + lane;
-      cb_dma4(a.table_sqn + (row < t.end ? row : a.n), cb_lds_offset(xn0 + buf * CB_TN));
+      lds_dma4(a.table_sqn + (row < t.end ? row : a.n), lds_offset(xn0 + buf * KNN_TN));
     }
   };
 
@@ -255,12 +215,12 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
     __builtin_amdgcn_s_waitcnt(0);  // this wave's share of tile `buf` has landed
     __syncthreads();                // ... everyone's has, and nobody still reads the other buffer
     if (have_next) issue_tile(buf ^ 1, nxt);
-    const float* tl = tile0 + buf * CB_TN * XS;
-    const float* xnt = xn0 + buf * CB_TN;
+    const float* tl = tile0 + buf * KNN_TN * XS;
+    const float* xnt = xn0 + buf * KNN_TN;
     const int64_t t0 = cur.t0;
 
     if (cur.fresh) {
-      if (lane < CB_QW) {
+      if (lane < KNN_QW) {
         while (pv < cur.cell) {
           ++pc;
           pv = pc < a.nprobe ? mypr[pc] : 0x7FFFFFFF;
@@ -273,10 +233,9 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
       if (active) load_thr();
     }
     if (active) {
-      // ---- two 32 x 32 blocks per wave: both MFMA chains are issued before the first accumulator is read ----------
-      f16x acc2[CB_TN / 32];
+      f16x acc2[KNN_TN / 32];
 #pragma unroll
-      for (int ct = 0; ct < CB_TN / 32; ++ct) {
+      for (int ct = 0; ct < KNN_TN / 32; ++ct) {
         const int col = ct * 32 + r32;
         const float* xrow = tl + col * XS + half * HD;
         float bx[HD];
@@ -292,7 +251,7 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
         acc2[ct] = acc;
       }
 #pragma unroll
-      for (int ct = 0; ct < CB_TN / 32; ++ct) {
+      for (int ct = 0; ct < KNN_TN / 32; ++ct) {
         const int col = ct * 32 + r32;
         const f16x acc = acc2[ct];
         bool any = false;
@@ -302,11 +261,11 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
 #pragma unroll
           for (int v = 0; v < 16; ++v) {
             if (acc[v] > thr[v]) {
-              const int qslot = w * CB_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+              const int qslot = w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
               const int pos = atomicAdd(&q_cnt[qslot], 1);
-              if (pos < CB_CAP) {
-                q_d[qslot * CB_CAP + pos] = qn[v] - 2.0f * acc[v];
-                q_i[qslot * CB_CAP + pos] = (int)(t0 + col);
+              if (pos < KNN_CAP) {
+                q_d[qslot * KNN_CAP + pos] = qn[v] - 2.0f * acc[v];
+                q_i[qslot * KNN_CAP + pos] = (int)(t0 + col);
               }
             }
           }
@@ -315,33 +274,33 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
       wave_lds_fence();
 
       // ---- drain this wave's queues into the k-best lists (wave-private state: no barrier) ----------------------
-      const int mycnt = lane < CB_QW ? q_cnt[myslot] : 0;
+      const int mycnt = lane < KNN_QW ? q_cnt[myslot] : 0;
       unsigned long long pending = __ballot(mycnt > 0);
       const bool drained = pending != 0ull;
       while (pending) {
         const int qr = __builtin_ctzll(pending);
         pending &= pending - 1;
-        const int qslot = w * CB_QW + qr;
+        const int qslot = w * KNN_QW + qr;
         const int64_t q = qbase + qslot;  // (< m: the other slots are no members of any cell)
         int cnt = q_cnt[qslot];
         const int self = a.self_pos ? (int)a.self_pos[q] : -1;
         float bd = lane < k ? a.best_d[q * k + lane] : -inf;
         int bi = lane < k ? a.best_i[q * k + lane] : -1;
-        float tau = cb_wave_max(bd);
+        float tau = wave_max(bd);
         // (cd, ci) replaces the list's largest element by (distance, position) if it is smaller in that order
         auto insert = [&](float cd, int ci) {
           if (ci == self || !(cd <= tau)) return;
           const unsigned long long at_max = __ballot(bd == tau);
           int at = __builtin_ctzll(at_max);
           if (!(cd < tau) || (at_max & (at_max - 1))) {
-            const int pm = cb_wave_max(bd == tau ? bi : (int)0x80000000);
+            const int pm = wave_max(bd == tau ? bi : (int)0x80000000);
             if (!(cd < tau) && ci > pm) return;
             at = __builtin_ctzll(__ballot(bd == tau && bi == pm));
           }
           if (lane == at) bd = cd, bi = ci;
-          tau = cb_wave_max(bd);
+          tau = wave_max(bd);
         };
-        if (cnt > CB_CAP && tau < inf) {
+        if (cnt > KNN_CAP && tau < inf) {
           // a full list and a queue that lost pairs: the tile's 64 rows against this query, one row per lane
           const float* qrow = a.queries + q * (int64_t)d;
           const float* xrow = tl + lane * XS;
@@ -362,11 +321,11 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
             insert(__shfl(mine, l, 64), (int)(t0 + l));
           }
         } else {
-          if (cnt > CB_CAP) {
+          if (cnt > KNN_CAP) {
             if (lane == 0) a.overflow[q] = 1;
-            cnt = CB_CAP;
+            cnt = KNN_CAP;
           }
-          for (int c = 0; c < cnt; ++c) insert(q_d[qslot * CB_CAP + c], q_i[qslot * CB_CAP + c]);
+          for (int c = 0; c < cnt; ++c) insert(q_d[qslot * KNN_CAP + c], q_i[qslot * KNN_CAP + c]);
         }
         if (lane < k) {
           a.best_d[q * k + lane] = bd;
@@ -379,7 +338,7 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
       }
       if (drained) {  // (wave-uniform) only this wave's slots have changed
         wave_lds_fence();
-        if (lane < CB_QW && member) eff_s[myslot] = tau_s[myslot];
+        if (lane < KNN_QW && member) eff_s[myslot] = tau_s[myslot];
         wave_lds_fence();
         load_thr();
       }
@@ -392,8 +351,8 @@ __global__ __launch_bounds__(256) void knn_cells_block_kernel(const CellBlockArg
 
 template <int DP>
 int launch_cells_block(const CellBlockArgs& a, hipStream_t s) {
-  const unsigned grid = (unsigned)((a.m + CB_QB - 1) / CB_QB);
-  const size_t lds = (2 * CB_TN * (DP + 4) + 2 * CB_TN + 2 * CB_QB * CB_CAP + 3 * CB_QB + CB_WORDS) * sizeof(float);
+  const unsigned grid = (unsigned)((a.m + KNN_QB - 1) / KNN_QB);
+  const size_t lds = (2 * KNN_TN * (DP + 4) + 2 * KNN_TN + 2 * KNN_QB * KNN_CAP + 3 * KNN_QB + CB_WORDS) * sizeof(float);
   hipLaunchKernelGGL(knn_cells_block_kernel<DP>, dim3(grid), dim3(256), lds, s, a);
   MGP_HIP_CHECK_LAUNCH();
   return MGP_OK;
@@ -411,7 +370,7 @@ extern "C" int mgp_knn_cells_scan_block(const float* table, const float* table_s
   using namespace mgp;
   if (n < 0 || m < 0 || d < 1 || k < 1 || nlist < 1 || nprobe < 1 || nprobe > nlist) return MGP_EINVAL;
   if (d % 4 != 0 || d > 64 || k > 64 || nlist > 32 * CB_WORDS || n >= ((int64_t)1 << 31) ||
-      (m + CB_QB - 1) / CB_QB >= ((int64_t)1 << 31))
+      (m + KNN_QB - 1) / KNN_QB >= ((int64_t)1 << 31))
     return MGP_EUNSUPPORTED;
   if (m == 0) return MGP_OK;
   if (!table || !table_sqn || !cell_start || !queries || !query_sqn || !probes || !best_d || !best_i || !overflow)

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kCellWaves * 64) void knn_grid_scan_kernel(const Gr
         cur_end = nxt_end;
       }
     }
-    if (list.npend > 0) list.merge();
+    list.finish();
 
     // the faces behind which cells remain; done: tau is below the squared distance to every one of them
     constexpr float kSlack = 1.f - 0x1p-20f;

@@ -14,26 +14,14 @@
 
 #include <cstdint>
 
+#include "mgp_knn_common.h"
+
 namespace mgp {
 
 constexpr int kCellWaves = 4;     // queries per workgroup
 constexpr int kCellList = 64;     // list slots per wave (k <= 64)
 constexpr int kCellPending = 128; // pending slots per wave: merged when fewer than 64 are free
 constexpr int kCellSlots = kCellList + kCellPending;
-
-__device__ __forceinline__ unsigned cell_key(float x) {  // float_key of mgp_knn_select.hip
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float cell_unkey(unsigned key) {
-  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-__device__ __forceinline__ int popc64(unsigned long long m) { return __builtin_popcountll(m); }
-// the LDS traffic of one wave is in program order; this keeps the compiler from moving it
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 struct WaveList {
   float* ld;  // kCellSlots distances of this wave (LDS)
@@ -117,6 +105,12 @@ struct WaveList {
       if (npend > kCellPending - 64) merge();
     }
   }
+
+  // after the last step
+  __device__ __forceinline__ void finish() {
+    if (npend > 0) merge();
+  }
+  __device__ __forceinline__ int filled() const { return held; }
 
   // the list -> row q of best_d / best_i (m, k): +inf / -1 in the slots the candidates did not fill
   __device__ __forceinline__ void store(float* best_d, int* best_i, int64_t q) const {

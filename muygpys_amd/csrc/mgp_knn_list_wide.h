@@ -136,6 +136,7 @@ struct WideWaveList {
   __device__ __forceinline__ void finish() {
     if (total > k) select();
   }
+  __device__ __forceinline__ int filled() const { return total; }
 
   // the list -> row q of best_d / best_i (m, k): +inf / -1 in the slots the candidates did not fill
   __device__ __forceinline__ void store(float* best_d, int* best_i, int64_t q) const {

@@ -47,57 +47,18 @@
 #include <cstdint>
 
 #include "mgp_args.h"
+#include "mgp_knn_common.h"
 
 namespace mgp {
 namespace {
 
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4x __attribute__((ext_vector_type(4)));
-
-constexpr int KL_TN = 64;     // training rows per staged tile = queue slots per query of the wide form
-constexpr int KL_QW = 32;     // queries per wave
-constexpr int KL_QB = 128;    // queries per workgroup
-constexpr int KL_CAP = 16;    // queue entries per query, narrow form
 constexpr int KL_XS = 68;     // LDS row stride in floats: a 64-feature chunk + one 16-byte slot
 constexpr int KL_SPR = KL_XS / 4;
-constexpr int KL_NPASS = KL_TN * KL_SPR / 64;  // wave passes of 64 x 16 bytes per staged chunk
-constexpr int KL_EPL = KNN_WIDE_MAX_K / 64;    // list entries per lane, wide form
-static_assert(KL_TN * KL_SPR % 64 == 0, "a staged chunk is whole wave passes");
-
-// 16 bytes per lane from global memory straight into LDS (see csrc/mgp_knn.hip: lds_dma16)
-__device__ __forceinline__ void lds_dma16(const void* gsrc, unsigned lds_byte_offset) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
-               :
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_byte_offset))
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_offset(const void* p) { return (unsigned)(uintptr_t)p; }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-// (csrc/mgp_knn_wide.hip) the distances of query q's list, entry e * 64 + lane in v[e]; -inf where there is no such entry
-__device__ __forceinline__ void load_list(const float* best_d, int64_t q, int k, int lane, float (&v)[KL_EPL]) {
-  const float* ld = best_d + q * (int64_t)k;
-#pragma unroll
-  for (int e = 0; e < KL_EPL; ++e) {
-    v[e] = -__builtin_inff();
-    if (e * 64 < k) {  // (wave-uniform)
-      const int j = e * 64 + lane;
-      if (j < k) v[e] = ld[j];
-    }
-  }
-}
-__device__ __forceinline__ void lane_max(const float (&v)[KL_EPL], float& lmax, int& lpos) {
-  lmax = v[0], lpos = 0;
-#pragma unroll
-  for (int e = 1; e < KL_EPL; ++e)
-    if (v[e] > lmax) lmax = v[e], lpos = e;
-}
+constexpr int KL_NPASS = KNN_TN * KL_SPR / 64;  // wave passes of 64 x 16 bytes per staged chunk
+static_assert(KNN_TN * KL_SPR % 64 == 0, "a staged chunk is whole wave passes");
 
 constexpr size_t long_lds_bytes(bool wide) {
-  return (2 * KL_TN * KL_XS + 2 * KL_TN + (wide ? KL_QB * KL_TN + 4 * KL_QB : 2 * KL_QB * KL_CAP + 3 * KL_QB)) * sizeof(float);
+  return (2 * KNN_TN * KL_XS + 2 * KNN_TN + (wide ? KNN_QB * KNN_TN + 4 * KNN_QB : 2 * KNN_QB * KNN_CAP + 3 * KNN_QB)) * sizeof(float);
 }
 
 template <int NCH, bool WIDE>
@@ -106,28 +67,28 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
   constexpr int JMIN = (64 * (NCH - 1) + 4 + 8 * NCH - 1) / (8 * NCH);
   // dynamic LDS, carved by hand (see knn_scan_kernel)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* tile0 = reinterpret_cast<float*>(smem);                 // [2][KL_TN * KL_XS]
-  float* xn0 = tile0 + 2 * KL_TN * KL_XS;                        // [2][KL_TN]
-  float* q_d = xn0 + 2 * KL_TN;                                  // narrow [KL_QB * KL_CAP] | wide [KL_QB][KL_TN]
+  float* tile0 = reinterpret_cast<float*>(smem);                          // [2][KNN_TN * KL_XS]
+  float* xn0 = tile0 + 2 * KNN_TN * KL_XS;                                // [2][KNN_TN]
+  float* q_d = xn0 + 2 * KNN_TN;                                          // narrow [KNN_QB * KNN_CAP] | wide [KNN_QB][KNN_TN]
   // narrow: row numbers, counters; wide: masks of the occupied slots
-  int* q_i = reinterpret_cast<int*>(q_d + (WIDE ? KL_QB * KL_TN : KL_QB * KL_CAP));
-  int* q_cnt = q_i + (WIDE ? 0 : KL_QB * KL_CAP);                // narrow [KL_QB]
-  unsigned* q_mask = reinterpret_cast<unsigned*>(q_i);           // wide [KL_QB][2]
-  float* tau_s = reinterpret_cast<float*>(q_i + (WIDE ? 2 * KL_QB : KL_QB * KL_CAP + KL_QB));  // [KL_QB]
-  float* qn_s = tau_s + KL_QB;                                   // [KL_QB]  |q|^2 (read on the survivors' path only)
+  int* q_i = reinterpret_cast<int*>(q_d + (WIDE ? KNN_QB * KNN_TN : KNN_QB * KNN_CAP));
+  int* q_cnt = q_i + (WIDE ? 0 : KNN_QB * KNN_CAP);                       // narrow [KNN_QB]
+  unsigned* q_mask = reinterpret_cast<unsigned*>(q_i);                    // wide [KNN_QB][2]
+  float* tau_s = reinterpret_cast<float*>(q_i + (WIDE ? 2 * KNN_QB : KNN_QB * KNN_CAP + KNN_QB));// [KNN_QB]
+  float* qn_s = tau_s + KNN_QB;                                           // [KNN_QB]  |q|^2 (read on the survivors' path only)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int half = lane >> 5, r32 = lane & 31;
-  const int64_t qbase = (int64_t)blockIdx.x * KL_QB;
+  const int64_t qbase = (int64_t)blockIdx.x * KNN_QB;
   const int d = a.d, k = a.k;
   const int cw = (d + 8 * NCH - 1) / (8 * NCH) * 8;  // features per chunk (<= 64), hd per lane half
   const int hd = cw / 2;
 
   // ---- per-query state: tau = the largest entry of the list -------------------------------------------------------
   if constexpr (WIDE) {
-    for (int r = 0; r < KL_QW; ++r) {
-      const int qslot = w * KL_QW + r;
+    for (int r = 0; r < KNN_QW; ++r) {
+      const int qslot = w * KNN_QW + r;
       const int64_t q = qbase + qslot;
       float t = -__builtin_inff();  // rows past the end never accept anything
       if (q < a.m) {
@@ -136,9 +97,9 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
       }
       if (lane == 0) tau_s[qslot] = t;
     }
-    if (tid < 2 * KL_QB) q_mask[tid] = 0;
+    if (tid < 2 * KNN_QB) q_mask[tid] = 0;
   } else {
-    if (tid < KL_QB) {
+    if (tid < KNN_QB) {
       const int64_t q = qbase + tid;
       float t = -__builtin_inff();
       if (q < a.m) {
@@ -149,12 +110,12 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
       q_cnt[tid] = 0;
     }
   }
-  if (tid < KL_QB) qn_s[tid] = qbase + tid < a.m ? a.query_sqn[qbase + tid] : 0.f;
+  if (tid < KNN_QB) qn_s[tid] = qbase + tid < a.m ? a.query_sqn[qbase + tid] : 0.f;
   // A operand: lane (r32, half) holds features [c cw + half hd, c cw + half hd + hd) of chunk c of query
   // qbase + 32 w + r32; zero past hd and past d
   float aq[NCH][32];
   {
-    const int64_t q = qbase + w * KL_QW + r32;
+    const int64_t q = qbase + w * KNN_QW + r32;
     const float* qrow = a.queries + (q < a.m ? q : 0) * (int64_t)d;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -172,7 +133,7 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
   float thr[16];
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int row = w * KL_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+    const int row = w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
     thr[v] = 0.5f * (qn_s[row] - tau_s[row]);
   }
 
@@ -186,24 +147,24 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
       const int row = sigma / KL_SPR;
       const int s = min(c * cwslots + min(sigma - row * KL_SPR, cwslots - 1), dslots - 1);
       const int64_t grow = min(t0 + row, a.n - 1);
-      lds_dma16(a.train + grow * (int64_t)d + s * 4, lds_offset(tile0 + buf * KL_TN * KL_XS) + p * 1024);
+      lds_dma16(a.train + grow * (int64_t)d + s * 4, lds_offset(tile0 + buf * KNN_TN * KL_XS) + p * 1024);
     }
   };
   auto issue_norms = [&](int xb, int64_t t0) {
-    if (w == 3 && lane < KL_TN / 4) lds_dma16(a.train_sqn + t0 + lane * 4, lds_offset(xn0 + xb * KL_TN));
+    if (w == 3 && lane < KNN_TN / 4) lds_dma16(a.train_sqn + t0 + lane * 4, lds_offset(xn0 + xb * KNN_TN));
   };
   // staggered walk over the table (see knn_scan_kernel)
-  const int64_t ntiles = (a.n - a.start + KL_TN - 1) / KL_TN;
+  const int64_t ntiles = (a.n - a.start + KNN_TN - 1) / KNN_TN;
   const int64_t tile_off = ((int64_t)blockIdx.x * 7919) % ntiles;
   auto tile_after = [&](int64_t t) { return t + 1 == ntiles ? (int64_t)0 : t + 1; };
   int64_t tcur = tile_off;
-  issue_chunk(0, a.start + tcur * KL_TN, 0);
-  issue_norms(0, a.start + tcur * KL_TN);
+  issue_chunk(0, a.start + tcur * KNN_TN, 0);
+  issue_norms(0, a.start + tcur * KNN_TN);
   int buf = 0, xb = 0;
   [[maybe_unused]] int64_t next_drain = 0;
   for (int64_t tj = 0; tj < ntiles; ++tj, xb ^= 1, tcur = tile_after(tcur)) {
-    const int64_t t0 = a.start + tcur * KL_TN;
-    f16x acc2[KL_TN / 32];
+    const int64_t t0 = a.start + tcur * KNN_TN;
+    f16x acc2[KNN_TN / 32];
 #pragma unroll
     for (int c = 0; c < NCH; ++c, buf ^= 1) {
       __builtin_amdgcn_s_waitcnt(0);  // this wave's share of buffer `buf` has landed
@@ -212,13 +173,13 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
       if (c + 1 < NCH) {
         issue_chunk(buf ^ 1, t0, c + 1);
       } else if (tj + 1 < ntiles) {
-        const int64_t tn = a.start + tile_after(tcur) * KL_TN;
+        const int64_t tn = a.start + tile_after(tcur) * KNN_TN;
         issue_chunk(buf ^ 1, tn, 0);
         issue_norms(xb ^ 1, tn);  // (last read at the first chunk of the tile before this one)
       }
-      const float* tl = tile0 + buf * KL_TN * KL_XS;
+      const float* tl = tile0 + buf * KNN_TN * KL_XS;
 #pragma unroll
-      for (int ct = 0; ct < KL_TN / 32; ++ct) {
+      for (int ct = 0; ct < KNN_TN / 32; ++ct) {
         const int col = ct * 32 + r32;
         const float* xrow = tl + col * KL_XS + half * hd;
         float bx[32];
@@ -229,7 +190,7 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
         }
         f16x acc;
         if (c == 0) {
-          const float c0 = -0.5f * xn0[xb * KL_TN + col];
+          const float c0 = -0.5f * xn0[xb * KNN_TN + col];
           acc = f16x{c0, c0, c0, c0, c0, c0, c0, c0, c0, c0, c0, c0, c0, c0, c0, c0};
         } else {
           acc = acc2[ct];
@@ -247,7 +208,7 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
 
     // ---- the compare, after the last chunk ------------------------------------------------------------------------
 #pragma unroll
-    for (int ct = 0; ct < KL_TN / 32; ++ct) {
+    for (int ct = 0; ct < KNN_TN / 32; ++ct) {
       const int col = ct * 32 + r32;
       const f16x acc = acc2[ct];
       bool any = false;
@@ -257,15 +218,15 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
           if (acc[v] > thr[v]) {
-            const int qslot = w * KL_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+            const int qslot = w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
             if constexpr (WIDE) {
-              q_d[qslot * KL_TN + col] = qn_s[qslot] - 2.0f * acc[v];
+              q_d[qslot * KNN_TN + col] = qn_s[qslot] - 2.0f * acc[v];
               atomicOr(&q_mask[qslot * 2 + ct], 1u << r32);
             } else {
               const int pos = atomicAdd(&q_cnt[qslot], 1);
-              if (pos < KL_CAP) {
-                q_d[qslot * KL_CAP + pos] = qn_s[qslot] - 2.0f * acc[v];
-                q_i[qslot * KL_CAP + pos] = (int)(t0 + col);
+              if (pos < KNN_CAP) {
+                q_d[qslot * KNN_CAP + pos] = qn_s[qslot] - 2.0f * acc[v];
+                q_i[qslot * KNN_CAP + pos] = (int)(t0 + col);
               }
             }
           }
@@ -277,23 +238,23 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
     if constexpr (WIDE) {
       // (knn_scan_wide_kernel's drain)
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      const unsigned mymask = lane < KL_QW ? (q_mask[(w * KL_QW + lane) * 2] | q_mask[(w * KL_QW + lane) * 2 + 1]) : 0u;
+      const unsigned mymask = lane < KNN_QW ? (q_mask[(w * KNN_QW + lane) * 2] | q_mask[(w * KNN_QW + lane) * 2 + 1]) : 0u;
       unsigned long long pending = __ballot(mymask != 0u);
       if (!pending) continue;  // nothing passed: no list is touched
-      float vnext[KL_EPL];
-      load_list(a.best_d, qbase + w * KL_QW + __builtin_ctzll(pending), k, lane, vnext);
+      float vnext[KNN_EPL];
+      load_list(a.best_d, qbase + w * KNN_QW + __builtin_ctzll(pending), k, lane, vnext);
       while (pending) {
         const int r = __builtin_ctzll(pending);
         pending &= pending - 1;
-        const int qslot = w * KL_QW + r;
+        const int qslot = w * KNN_QW + r;
         const int64_t q = qbase + qslot;  // (< m: a row past the end has tau = -inf and accepts nothing)
-        float v[KL_EPL];
+        float v[KNN_EPL];
 #pragma unroll
-        for (int e = 0; e < KL_EPL; ++e) v[e] = vnext[e];
-        if (pending) load_list(a.best_d, qbase + w * KL_QW + __builtin_ctzll(pending), k, lane, vnext);
+        for (int e = 0; e < KNN_EPL; ++e) v[e] = vnext[e];
+        if (pending) load_list(a.best_d, qbase + w * KNN_QW + __builtin_ctzll(pending), k, lane, vnext);
         const unsigned long long occupied = (unsigned long long)q_mask[qslot * 2] | ((unsigned long long)q_mask[qslot * 2 + 1] << 32);
         const int self = a.self_idx ? (int)a.self_idx[q] : -1;
-        const float cd = q_d[qslot * KL_TN + lane];  // lane = column of the tile
+        const float cd = q_d[qslot * KNN_TN + lane];  // lane = column of the tile
         float lmax;
         int lpos;
         lane_max(v, lmax, lpos);
@@ -311,7 +272,7 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
           const unsigned long long at_max = __ballot(lmax == tau);
           if (lane == __builtin_ctzll(at_max)) {
 #pragma unroll
-            for (int e = 0; e < KL_EPL; ++e)
+            for (int e = 0; e < KNN_EPL; ++e)
               if (e == lpos) v[e] = ccd;
             ld[lpos * 64 + lane] = ccd;
             li[lpos * 64 + lane] = (int)(t0 + c);
@@ -330,34 +291,34 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int row = w * KL_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+        const int row = w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
         thr[v] = 0.5f * (qn_s[row] - tau_s[row]);
       }
     } else {
       // (knn_scan_kernel's drain: batched, with an interval that grows with the rows already seen)
       if (tj < next_drain && tj + 1 < ntiles) continue;
       next_drain = tj + (tj < 64 ? 1 : tj < 256 ? 4 : tj < 1024 ? 8 : 16);
-      const int mycnt = lane < KL_QW ? q_cnt[w * KL_QW + lane] : 0;
+      const int mycnt = lane < KNN_QW ? q_cnt[w * KNN_QW + lane] : 0;
       unsigned long long pending = __ballot(mycnt > 0);
       bool drained = false;
       while (pending) {
         const int r = __builtin_ctzll(pending);
         pending &= pending - 1;
-        const int qslot = w * KL_QW + r;
+        const int qslot = w * KNN_QW + r;
         const int64_t q = qbase + qslot;
         int cnt = q_cnt[qslot];
         if (q >= a.m) continue;
-        if (cnt > KL_CAP) {
+        if (cnt > KNN_CAP) {
           if (lane == 0) a.overflow[q] = 1;
-          cnt = KL_CAP;
+          cnt = KNN_CAP;
         }
         const int self = a.self_idx ? (int)a.self_idx[q] : -1;
         float bd = lane < k ? a.best_d[q * k + lane] : -__builtin_inff();
         int bi = lane < k ? a.best_i[q * k + lane] : -1;
         float tau = wave_max(bd);
         for (int c = 0; c < cnt; ++c) {
-          const float cd = q_d[qslot * KL_CAP + c];
-          const int ci = q_i[qslot * KL_CAP + c];
+          const float cd = q_d[qslot * KNN_CAP + c];
+          const int ci = q_i[qslot * KNN_CAP + c];
           if (ci == self || !(cd < tau)) continue;
           // replace the (first) lane that holds the current maximum
           const unsigned long long at_max = __ballot(bd == tau);
@@ -378,7 +339,7 @@ __device__ __forceinline__ void knn_scan_long_body(const KnnArgs& a) {
         __builtin_amdgcn_s_waitcnt(0);
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int row = w * KL_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+          const int row = w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
           thr[v] = 0.5f * (qn_s[row] - tau_s[row]);
         }
       }
@@ -399,7 +360,7 @@ __global__ __launch_bounds__(256) void knn_scan_long_wide_kernel(KnnArgs a) {
 
 template <int NCH, bool WIDE>
 static int launch_knn_long_nch(const KnnArgs& a, hipStream_t stream) {
-  const int64_t grid = (a.m + KL_QB - 1) / KL_QB;
+  const int64_t grid = (a.m + KNN_QB - 1) / KNN_QB;
   constexpr size_t lds = long_lds_bytes(WIDE);
   if constexpr (WIDE) {
     if (lds > 64 * 1024) {
@@ -423,12 +384,12 @@ static int launch_knn_long(const KnnArgs& a, hipStream_t stream) {
   if (((uintptr_t)a.train | (uintptr_t)a.queries | (uintptr_t)(a.train_sqn + a.start)) % 16 != 0)
     return MGP_EUNSUPPORTED;
   if (a.n >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;  // list indices are 32-bit
-  if (a.start % KL_TN != 0) return MGP_EUNSUPPORTED;     // whole tiles of the padded norms (see launch_knn_scan)
+  if (a.start % KNN_TN != 0) return MGP_EUNSUPPORTED;     // whole tiles of the padded norms (see launch_knn_scan)
   if constexpr (WIDE) {
     // the IN lists must be whole: k rows below start, one more where a query's own row may be among them
     if ((int64_t)a.k + (a.self_idx ? 1 : 0) > a.start) return MGP_EUNSUPPORTED;
   }
-  if ((a.m + KL_QB - 1) / KL_QB >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;
+  if ((a.m + KNN_QB - 1) / KNN_QB >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;
   switch ((a.d + 63) / 64) {
     case 2: return launch_knn_long_nch<2, WIDE>(a, stream);
     case 3: return launch_knn_long_nch<3, WIDE>(a, stream);

@@ -14,17 +14,10 @@
 #include <cstdint>
 
 #include "mgp_args.h"
+#include "mgp_knn_common.h"
 
 namespace mgp {
 
-// order-preserving map of a float to an unsigned integer (NaN sorts last, whatever its sign bit: every NaN takes the
-// one key KEY_NAN above +inf's; KEY_PAD above that is left to entries that do not exist)
-constexpr unsigned KEY_NAN = 0xFFFFFFFEu, KEY_PAD = 0xFFFFFFFFu;
-__device__ __forceinline__ unsigned float_key(float x) {
-  const unsigned u = __float_as_uint(x);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return KEY_NAN;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 __device__ __forceinline__ int wave_sum_int(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

@@ -40,60 +40,9 @@
 #include <cstdint>
 
 #include "mgp_args.h"
+#include "mgp_knn_tile.h"
 
 namespace mgp {
-namespace {
-
-typedef float f16x __attribute__((ext_vector_type(16)));
-typedef float f4x __attribute__((ext_vector_type(4)));
-typedef unsigned u4x __attribute__((ext_vector_type(4)));
-
-constexpr int KW_TN = 64;    // training rows per staged tile = queue slots per query
-constexpr int KW_QW = 32;    // queries per wave
-constexpr int KW_QB = 128;   // queries per workgroup
-constexpr int KW_EPL = KNN_WIDE_MAX_K / 64;  // list entries per lane, at most
-
-// 16 bytes per lane from global memory straight into LDS (see csrc/mgp_knn.hip: lds_dma16)
-__device__ __forceinline__ void lds_dma16(const void* gsrc, unsigned lds_byte_offset) {
-  asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off"
-               :
-               : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_byte_offset))
-               : "memory");
-}
-__device__ __forceinline__ unsigned lds_offset(const void* p) { return (unsigned)(uintptr_t)p; }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-constexpr unsigned KEY_NAN = 0xFFFFFFFEu;
-__device__ __forceinline__ unsigned float_key(float x) {  // (csrc/mgp_knn_select.hip: NaN behind +inf)
-  const unsigned u = __float_as_uint(x);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return KEY_NAN;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// the distances of query q's list, entry e * 64 + lane in v[e]; -inf where the list has no such entry
-__device__ __forceinline__ void load_list(const float* best_d, int64_t q, int k, int lane, float (&v)[KW_EPL]) {
-  const float* ld = best_d + q * (int64_t)k;
-#pragma unroll
-  for (int e = 0; e < KW_EPL; ++e) {
-    v[e] = -__builtin_inff();
-    if (e * 64 < k) {  // (wave-uniform)
-      const int j = e * 64 + lane;
-      if (j < k) v[e] = ld[j];
-    }
-  }
-}
-// the largest of a lane's entries and the first place it stands at
-__device__ __forceinline__ void lane_max(const float (&v)[KW_EPL], float& lmax, int& lpos) {
-  lmax = v[0], lpos = 0;
-#pragma unroll
-  for (int e = 1; e < KW_EPL; ++e)
-    if (v[e] > lmax) lmax = v[e], lpos = e;
-}
-
-}  // namespace
 
 template <int DP>
 __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
@@ -101,21 +50,21 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
   constexpr int HD = DP / 2;      // features per lane half
   // dynamic LDS, carved by hand (see knn_scan_kernel)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* tile0 = reinterpret_cast<float*>(smem);                          // [2][KW_TN * XS]
-  float* xn0 = tile0 + 2 * KW_TN * XS;                                    // [2][KW_TN]
-  float* q_d = xn0 + 2 * KW_TN;                                           // [KW_QB][KW_TN]  slot = column of the tile
-  unsigned* q_mask = reinterpret_cast<unsigned*>(q_d + KW_QB * KW_TN);    // [KW_QB][2]      occupied slots
-  float* tau_s = reinterpret_cast<float*>(q_mask + 2 * KW_QB);            // [KW_QB]
+  float* tile0 = reinterpret_cast<float*>(smem);                          // [2][KNN_TN * XS]
+  float* xn0 = tile0 + 2 * KNN_TN * XS;                                   // [2][KNN_TN]
+  float* q_d = xn0 + 2 * KNN_TN;                                          // [KNN_QB][KNN_TN]  slot = column of the tile
+  unsigned* q_mask = reinterpret_cast<unsigned*>(q_d + KNN_QB * KNN_TN);  // [KNN_QB][2]      occupied slots
+  float* tau_s = reinterpret_cast<float*>(q_mask + 2 * KNN_QB);           // [KNN_QB]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int half = lane >> 5, r32 = lane & 31;
-  const int64_t qbase = (int64_t)blockIdx.x * KW_QB;
+  const int64_t qbase = (int64_t)blockIdx.x * KNN_QB;
   const int d = a.d, k = a.k;
 
   // ---- per-query state: tau = the largest entry of the list (a wave per 32 queries, coalesced) ------------------
-  for (int r = 0; r < KW_QW; ++r) {
-    const int qslot = w * KW_QW + r;
+  for (int r = 0; r < KNN_QW; ++r) {
+    const int qslot = w * KNN_QW + r;
     const int64_t q = qbase + qslot;
     float t = -__builtin_inff();  // rows past the end never accept anything
     if (q < a.m) {
@@ -124,11 +73,11 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
     }
     if (lane == 0) tau_s[qslot] = t;
   }
-  if (tid < 2 * KW_QB) q_mask[tid] = 0;
+  if (tid < 2 * KNN_QB) q_mask[tid] = 0;
   // A operand: lane (r32, half) holds features [half*HD, half*HD + HD) of query qbase + 32 w + r32
   float aq[HD];
   {
-    const int64_t q = qbase + w * KW_QW + r32;
+    const int64_t q = qbase + w * KNN_QW + r32;
     const float* qrow = a.queries + (q < a.m ? q : 0) * (int64_t)d;
 #pragma unroll
     for (int j = 0; j < HD / 4; ++j) {
@@ -139,49 +88,39 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
     }
   }
   __syncthreads();
-  // accumulator register v of this lane belongs to query row  8 (v/4) + 4 half + v%4  of the wave
   float qn[16], thr[16];
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int row = 8 * (v >> 2) + 4 * half + (v & 3);
-    const int64_t q = qbase + w * KW_QW + row;
+    const int row = tile_acc_row(v, half);
+    const int64_t q = qbase + w * KNN_QW + row;
     qn[v] = q < a.m ? a.query_sqn[q] : 0.f;
-    thr[v] = 0.5f * (qn[v] - tau_s[w * KW_QW + row]);
+    thr[v] = 0.5f * (qn[v] - tau_s[w * KNN_QW + row]);
   }
 
-  // staging as in knn_scan_kernel: slot sigma of a tile is row sigma / SPR, column sigma % SPR; rows past n repeat row
-  // n - 1, their |x|^2 is +inf (host-padded norms)
-  constexpr int SPR = XS / 4;
-  constexpr int NPASS = (KW_TN * SPR + 63) / 64;
+  // staging as in knn_scan_kernel: rows past n repeat row n - 1, their |x|^2 is +inf (host-padded norms)
   const int dslots = d / 4;
   auto issue_tile = [&](int buf, int64_t t0) {
-    for (int p = w; p < NPASS; p += 4) {
-      const int sigma = 64 * p + lane;
-      const int row = min(sigma / SPR, KW_TN - 1);
-      const int c = min(sigma - row * SPR, dslots - 1);
-      const int64_t grow = min(t0 + row, a.n - 1);
-      lds_dma16(a.train + grow * (int64_t)d + c * 4, lds_offset(tile0 + buf * KW_TN * XS) + p * 1024);
-    }
-    if (w == 3 && lane < KW_TN / 4) lds_dma16(a.train_sqn + t0 + lane * 4, lds_offset(xn0 + buf * KW_TN));
+    tile_stage_rows<DP>(tile0 + buf * KNN_TN * XS, a.train, a.n, d, dslots, t0, w, lane);
+    if (w == 3 && lane < KNN_TN / 4) lds_dma16(a.train_sqn + t0 + lane * 4, lds_offset(xn0 + buf * KNN_TN));
   };
   // staggered walk over the table (see knn_scan_kernel)
-  const int64_t ntiles = (a.n - a.start + KW_TN - 1) / KW_TN;
+  const int64_t ntiles = (a.n - a.start + KNN_TN - 1) / KNN_TN;
   const int64_t tile_off = ((int64_t)blockIdx.x * 7919) % ntiles;
   auto tile_after = [&](int64_t t) { return t + 1 == ntiles ? (int64_t)0 : t + 1; };
   int64_t tcur = tile_off;
-  issue_tile(0, a.start + tcur * KW_TN);
+  issue_tile(0, a.start + tcur * KNN_TN);
   int buf = 0;
   for (int64_t tj = 0; tj < ntiles; ++tj, buf ^= 1, tcur = tile_after(tcur)) {
-    const int64_t t0 = a.start + tcur * KW_TN;
+    const int64_t t0 = a.start + tcur * KNN_TN;
     __builtin_amdgcn_s_waitcnt(0);  // this wave's share of tile `buf` has landed
     __syncthreads();                // ... everyone's has, and nobody still reads the other buffer
-    if (tj + 1 < ntiles) issue_tile(buf ^ 1, a.start + tile_after(tcur) * KW_TN);
-    const float* tl = tile0 + buf * KW_TN * XS;
-    const float* xnt = xn0 + buf * KW_TN;
+    if (tj + 1 < ntiles) issue_tile(buf ^ 1, a.start + tile_after(tcur) * KNN_TN);
+    const float* tl = tile0 + buf * KNN_TN * XS;
+    const float* xnt = xn0 + buf * KNN_TN;
 
-    f16x acc2[KW_TN / 32];
+    f16x acc2[KNN_TN / 32];
 #pragma unroll
-    for (int ct = 0; ct < KW_TN / 32; ++ct) {
+    for (int ct = 0; ct < KNN_TN / 32; ++ct) {
       const int col = ct * 32 + r32;
       const float* xrow = tl + col * XS + half * HD;
       float bx[HD];
@@ -197,7 +136,7 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
       acc2[ct] = acc;
     }
 #pragma unroll
-    for (int ct = 0; ct < KW_TN / 32; ++ct) {
+    for (int ct = 0; ct < KNN_TN / 32; ++ct) {
       const f16x acc = acc2[ct];
       bool any = false;
 #pragma unroll
@@ -206,8 +145,8 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
           if (acc[v] > thr[v]) {
-            const int qslot = w * KW_QW + 8 * (v >> 2) + 4 * half + (v & 3);
-            q_d[qslot * KW_TN + ct * 32 + r32] = qn[v] - 2.0f * acc[v];
+            const int qslot = w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3);
+            q_d[qslot * KNN_TN + ct * 32 + r32] = qn[v] - 2.0f * acc[v];
             atomicOr(&q_mask[qslot * 2 + ct], 1u << r32);
           }
         }
@@ -216,23 +155,23 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
 
     // ---- drain this wave's queues into the k-best lists (wave-private state: no barrier) ---------------------------
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const unsigned mymask = lane < KW_QW ? (q_mask[(w * KW_QW + lane) * 2] | q_mask[(w * KW_QW + lane) * 2 + 1]) : 0u;
+    const unsigned mymask = lane < KNN_QW ? (q_mask[(w * KNN_QW + lane) * 2] | q_mask[(w * KNN_QW + lane) * 2 + 1]) : 0u;
     unsigned long long pending = __ballot(mymask != 0u);
     if (!pending) continue;  // nothing passed: no list is touched
-    float vnext[KW_EPL];
-    load_list(a.best_d, qbase + w * KW_QW + __builtin_ctzll(pending), k, lane, vnext);
+    float vnext[KNN_EPL];
+    load_list(a.best_d, qbase + w * KNN_QW + __builtin_ctzll(pending), k, lane, vnext);
     while (pending) {
       const int r = __builtin_ctzll(pending);
       pending &= pending - 1;
-      const int qslot = w * KW_QW + r;
+      const int qslot = w * KNN_QW + r;
       const int64_t q = qbase + qslot;  // (< m: a row past the end has tau = -inf and accepts nothing)
-      float v[KW_EPL];
+      float v[KNN_EPL];
 #pragma unroll
-      for (int e = 0; e < KW_EPL; ++e) v[e] = vnext[e];
-      if (pending) load_list(a.best_d, qbase + w * KW_QW + __builtin_ctzll(pending), k, lane, vnext);
+      for (int e = 0; e < KNN_EPL; ++e) v[e] = vnext[e];
+      if (pending) load_list(a.best_d, qbase + w * KNN_QW + __builtin_ctzll(pending), k, lane, vnext);
       const unsigned long long occupied = (unsigned long long)q_mask[qslot * 2] | ((unsigned long long)q_mask[qslot * 2 + 1] << 32);
       const int self = a.self_idx ? (int)a.self_idx[q] : -1;
-      const float cd = q_d[qslot * KW_TN + lane];  // lane = column of the tile
+      const float cd = q_d[qslot * KNN_TN + lane];  // lane = column of the tile
       float lmax;
       int lpos;
       lane_max(v, lmax, lpos);
@@ -250,7 +189,7 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
         const unsigned long long at_max = __ballot(lmax == tau);
         if (lane == __builtin_ctzll(at_max)) {
 #pragma unroll
-          for (int e = 0; e < KW_EPL; ++e)
+          for (int e = 0; e < KNN_EPL; ++e)
             if (e == lpos) v[e] = ccd;
           ld[lpos * 64 + lane] = ccd;
           li[lpos * 64 + lane] = (int)(t0 + c);
@@ -269,7 +208,7 @@ __global__ __launch_bounds__(256) void knn_scan_wide_kernel(KnnArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
     for (int v = 0; v < 16; ++v)
-      thr[v] = 0.5f * (qn[v] - tau_s[w * KW_QW + 8 * (v >> 2) + 4 * half + (v & 3)]);
+      thr[v] = 0.5f * (qn[v] - tau_s[w * KNN_QW + 8 * (v >> 2) + 4 * half + (v & 3)]);
   }
 }
 
@@ -337,8 +276,8 @@ __global__ __launch_bounds__(256) void knn_finish_wide_kernel(const float* queri
 
 template <int DP>
 static int launch_knn_wide_dp(const KnnArgs& a, hipStream_t stream) {
-  const int64_t grid = (a.m + KW_QB - 1) / KW_QB;
-  const size_t lds = (2 * KW_TN * (DP + 4) + 2 * KW_TN + KW_QB * KW_TN + 3 * KW_QB) * sizeof(float);
+  const int64_t grid = (a.m + KNN_QB - 1) / KNN_QB;
+  const size_t lds = (2 * KNN_TN * (DP + 4) + 2 * KNN_TN + KNN_QB * KNN_TN + 3 * KNN_QB) * sizeof(float);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_scan_wide_kernel<DP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -354,10 +293,10 @@ int launch_knn_scan_wide(const KnnArgs& a, hipStream_t stream) {
   if (((uintptr_t)a.train | (uintptr_t)a.queries | (uintptr_t)(a.train_sqn + a.start)) % 16 != 0)
     return MGP_EUNSUPPORTED;
   if (a.n >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;  // list indices are 32-bit
-  if (a.start % KW_TN != 0) return MGP_EUNSUPPORTED;     // whole tiles of the padded norms (see launch_knn_scan)
+  if (a.start % KNN_TN != 0) return MGP_EUNSUPPORTED;     // whole tiles of the padded norms (see launch_knn_scan)
   // the IN lists must be whole: k rows below start, one more where a query's own row may be among them
   if ((int64_t)a.k + (a.self_idx ? 1 : 0) > a.start) return MGP_EUNSUPPORTED;
-  if ((a.m + KW_QB - 1) / KW_QB >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;
+  if ((a.m + KNN_QB - 1) / KNN_QB >= (int64_t)1 << 31) return MGP_EUNSUPPORTED;
   const int dp = (a.d + 7) / 8 * 8;
   switch (dp) {
     case 8: return launch_knn_wide_dp<8>(a, stream);

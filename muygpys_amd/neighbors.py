@@ -412,30 +412,8 @@ class NN_Wrapper:
         if rc == _lib.EUNSUPPORTED:  # MGP_EUNSUPPORTED (alignment)
             return None
         _lib.check(rc, "mgp_knn_scan_f32")
-        # the winners re-measured in difference form, put in order and mapped to the caller's row numbers in one launch
-        # (csrc/mgp_knn_select.hip) -- was gather (m, k, d) / subtract / square / sum / argsort / gather / gather
-        idx = torch.empty((m, k), dtype=torch.int64, device=q.device)
-        dist = torch.empty((m, k), dtype=q.dtype, device=q.device)
-        rc_fin = _lib.load().mgp_knn_finish_f32(_lib.ptr(q), _lib.ptr(self.train), self._width, _lib.ptr(best_i), m, k,
-                                                None, _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr())
-        if rc_fin == _lib.EUNSUPPORTED:
-            cand = best_i.to(torch.int64)
-            for s in range(0, m, 65536):
-                c = cand[s:s + 65536]
-                diff = q[s:s + 65536, None, :] - self.train[c]
-                dd = (diff * diff).sum(-1)
-                order = dd.argsort(dim=1, stable=True)
-                idx[s:s + 65536] = c.gather(1, order)
-                dist[s:s + 65536] = dd.gather(1, order)
-        else:
-            _lib.check(rc_fin, "mgp_knn_finish_f32")
-        self.last_overflow = overflow
-        redo = overflow.nonzero().reshape(-1)
-        if redo.numel():  # queues overflowed (adversarial row order): those queries go dense
-            ri, rd = self._dense_nns(q[redo], k, None if exclude is None else exclude[redo])
-            idx[redo], dist[redo] = ri, rd
         self.last_route = route
-        return idx, dist
+        return self._finish_nns(_lib.load().mgp_knn_finish_f32, "mgp_knn_finish_f32", q, best_i, overflow, exclude)
 
     FINISH_BUDGET_BYTES = 1 << 30  # the (rows, k, d) temporary of the torch finish step, where the kernel declines
 
@@ -452,14 +430,23 @@ class NN_Wrapper:
         if rc == _lib.EUNSUPPORTED:
             return None
         _lib.check(rc, "mgp_knn_scan_wide")
+        self.last_route = "long" if long_rows else "wide"
+        return self._finish_nns(_lib.load().mgp_knn_finish_wide, "mgp_knn_finish_wide", q, best_i, overflow, exclude)
+
+    def _finish_nns(self, finish, name, q, best_i, overflow, exclude):
+        """The step behind every scan: the winners ``best_i`` (m, k) re-measured in difference form, put in order and
+        mapped to the caller's row numbers in one launch of ``finish`` (csrc/mgp_knn_select.hip, csrc/mgp_knn_wide.hip) --
+        was gather (m, k, d) / subtract / square / sum / argsort / gather / gather -- and the queries flagged in
+        ``overflow`` answered again on the dense path."""
+        (m, k), d = best_i.shape, self._width
         idx = torch.empty((m, k), dtype=torch.int64, device=q.device)
         dist = torch.empty((m, k), dtype=q.dtype, device=q.device)
-        rc_fin = _lib.load().mgp_knn_finish_wide(_lib.ptr(q), _lib.ptr(self.train), d, _lib.ptr(best_i), m, k,
-                                                 None, _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr())
+        rc_fin = finish(_lib.ptr(q), _lib.ptr(self.train), d, _lib.ptr(best_i), m, k, None, _lib.ptr(idx), _lib.ptr(dist),
+                        _lib.stream_ptr())
         if rc_fin == _lib.EUNSUPPORTED:
             # rows per pass from a byte budget: the gathered (rows, k, d) block and its squares (at k = 1023, d = 40 a
-            # fixed 65 536 rows would be 10.7 GB)
-            rows = max(1, self.FINISH_BUDGET_BYTES // (2 * k * d * q.element_size()))
+            # fixed 65 536 rows would be 10.7 GB), 65 536 at most; the result does not depend on the block size
+            rows = max(1, min(65536, self.FINISH_BUDGET_BYTES // (2 * k * d * q.element_size())))
             for s in range(0, m, rows):
                 c = best_i[s:s + rows].to(torch.int64)
                 diff = q[s:s + rows, None, :] - self.train[c]
@@ -468,13 +455,12 @@ class NN_Wrapper:
                 idx[s:s + rows] = c.gather(1, order)
                 dist[s:s + rows] = dd.gather(1, order)
         else:
-            _lib.check(rc_fin, "mgp_knn_finish_wide")
+            _lib.check(rc_fin, name)
         self.last_overflow = overflow
         redo = overflow.nonzero().reshape(-1)
-        if redo.numel():  # (the contract of the narrow scans; the wide scan's queues cannot overflow)
+        if redo.numel():  # queues overflowed (adversarial row order; the wide scans' cannot): those queries go dense
             ri, rd = self._dense_nns(q[redo], k, None if exclude is None else exclude[redo])
             idx[redo], dist[redo] = ri, rd
-        self.last_route = "long" if long_rows else "wide"
         return idx, dist
 
     DENSE_BUDGET_BYTES = 4 << 30  # (chunk x train_count) distance matrix + topk temporaries
