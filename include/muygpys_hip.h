@@ -752,6 +752,26 @@ int mgp_knn_cells_scan_wide(const float* table, int64_t n, int d, const int64_t*
                             const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
                             void* stream);
 
+/* The same per-query scan for LONG rows (csrc/mgp_knn_cells_long.hip): the reference's approximate branch takes any
+ * feature count (its torch tutorial searches a 100-dimensional embedding), and the exact scans serve 68 to 256 features
+ * through mgp_knn_scan_long.  Opt-in (NN_Wrapper.cell_scan = "long").
+ *   mgp_knn_cells_scan_long   the parameters and the whole contract of mgp_knn_cells_scan_wide -- table, cell_start,
+ *       probes (entries outside [0, nlist) are skipped), self_pos, best_d / best_i (m, k) UNORDERED with -1 / +inf for
+ *       missing entries, short_flag; fp32 difference-form distances, four partial sums added as (s0 + s1) + (s2 + s3);
+ *       the k smallest by (distance, stored position) of the candidate set -- for d % 4 == 0,
+ *       68 <= d <= mgp_knn_long_max_features() and 1 <= k <= 1024.  One wave per query; a row is met in chunks of 32
+ *       features and a 64-row step is left as soon as no lane's partial sum can still enter the list, which changes no
+ *       bit of the result (a partial sum never exceeds the full one).  The list is mgp_knn_cells_scan's up to k = 64
+ *       and mgp_knn_cells_scan_wide's beyond (dynamic LDS, at most 52 KiB per workgroup with the query rows).
+ *       mgp_knn_finish_f32 / mgp_knn_finish_wide re-measure and sort.
+ * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), nothing to do (m == 0: MGP_OK, pointers not looked
+ * at), NULL pointers (MGP_EINVAL; self_pos and the stream are optional), then MGP_EUNSUPPORTED for k > 1024, d outside
+ * {68, 72, .. 256} (d <= 64 belongs to the two entries above), n >= 2^31 and alignment.  Nothing synchronises. */
+int mgp_knn_cells_scan_long(const float* table, int64_t n, int d, const int64_t* cell_start, int nlist,
+                            const float* queries, int64_t m, const int32_t* probes, int nprobe,
+                            const int64_t* self_pos, int k, float* best_d, int32_t* best_i, int32_t* short_flag,
+                            void* stream);
+
 /* The same search with a BLOCK of queries per workgroup on the matrix cores (csrc/mgp_knn_cells_block.hip): 128
  * consecutive queries walk the union of their probed cells in ascending cell order, the cells staged through LDS in
  * 64-row tiles, distances by v_mfma_f32_32x32x2_f32 in the Gram form of mgp_knn_scan_f32; a (query, row) pair counts

@@ -58,6 +58,8 @@ PER_FILE_FLAGS = {
     "mgp_knn_cells.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and its wide-list form, up to 1024 entries in LDS: tests/test_knn_cells_wide_status_cpu.py reads the record)
     "mgp_knn_cells_wide.hip": ["-Rpass-analysis=kernel-resource-usage"],
+    # (... and its long-row form, 68 to 256 features in chunks: tests/test_knn_cells_long_status_cpu.py reads the record)
+    "mgp_knn_cells_long.hip": ["-Rpass-analysis=kernel-resource-usage"],
     # (... and its block form on the matrix cores: the accumulators are compared right away, as in mgp_knn.hip)
     "mgp_knn_cells_block.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
     # (... and the grid walk of the exact search at 1 to 3 features: tests/test_knn_grid_resources.py reads its record)

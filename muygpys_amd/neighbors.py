@@ -48,7 +48,11 @@ after a per-query scan of each query's nearest cell has seeded the lists.  Same 
 ``last_overflow`` then holds the block launch's per-query flags, and a flagged query is rescanned by the per-query
 kernel over all its probes.  ``"wide"`` (opt-in) is ``mgp_knn_cells_scan_wide`` (``csrc/mgp_knn_cells_wide.hip``): the
 per-query scan with its list in LDS, ``1 <= k <= 1024`` -- the only cell scan past ``k = 64``; its winners are ordered
-by ``mgp_knn_finish_wide`` there.  Any other value is a ``ValueError``.
+by ``mgp_knn_finish_wide`` there.  ``"long"`` (opt-in) is ``mgp_knn_cells_scan_long``
+(``csrc/mgp_knn_cells_long.hip``): the per-query scan for rows of ``65 <= d <= 256`` features (stored zero-padded to a
+multiple of four) and ``1 <= k <= 1024`` -- the only cell scan past ``d = 64``, and it serves no other width.  A row is
+met in chunks of 32 features, and a 64-row step is left as soon as no partial sum can still enter the list: the same
+result bit for bit, fewer bytes read.  Any other value is a ``ValueError``.
 
 ``nn_method="exact", algorithm="grid"`` is the exact search for tables of 1 to 3 features (the role of the reference's
 ``algorithm="kd_tree"`` / ``"ball_tree"``, which it hands to scikit-learn; every other value of ``algorithm`` is
@@ -83,8 +87,9 @@ WIDE_MAX_K = 1024      # mgp_knn_wide_max_nn_count(): the longest list of the wi
 LONG_MAX_D = 256       # mgp_knn_long_max_features(): the widest row of the long-row scans (64 < d: csrc/mgp_knn_long.hip)
 CELLS_MAX = 4096       # most cells of the inverted-cell index: mgp_topk_rows_f32's column limit (probe selection)
 CELLS_SAMPLE = 256     # k-means runs on at most this many rows per cell
-# the cell scans of nn_method="ivf": mgp_knn_cells_scan | mgp_knn_cells_scan_block | mgp_knn_cells_scan_wide
-CELL_SCANS = ("query", "block", "wide")
+# the cell scans of nn_method="ivf": mgp_knn_cells_scan | mgp_knn_cells_scan_block | mgp_knn_cells_scan_wide |
+# mgp_knn_cells_scan_long (the only one for 64 < d <= LONG_MAX_D, and for those widths only)
+CELL_SCANS = ("query", "block", "wide", "long")
 CELLS_WIDE_MAX_K = 1024  # mgp_knn_cells_wide_max_nn_count(): the longest list of cell_scan="wide"; the others stop at 64
 GRID_MAX_D = 3         # most features of the grid walk (3^d cells around a query: csrc/mgp_knn_grid.hip)
 GRID_MAX_CELLS = 1 << 24  # most cells of a grid (mgp_knn_grid_scan's limit): beyond that the cells grow
@@ -510,8 +515,7 @@ class NN_Wrapper:
         # the cell scan's contract (include/muygpys_hip.h: mgp_knn_cells_scan); no other algorithm steps in
         if table.dtype != torch.float32:
             raise ValueError(f"nn_method='ivf' serves float32 tables only (fp32 only), got {table.dtype}")
-        if d > 64:
-            raise ValueError(f"nn_method='ivf' serves at most 64 features (d <= 64), got d = {d}")
+        self._check_cells_d(d, self.cell_scan)
         self._check_cells_k(k, self.cell_scan)
         if not 1 <= n < 2**31:
             raise ValueError(f"nn_method='ivf' serves 1 <= n < 2^31 table rows, got n = {n}")
@@ -519,7 +523,7 @@ class NN_Wrapper:
         self.nn_count, self.nn_method, self.chunk = k, "ivf", int(chunk)
         self.use_scan, self.scan_kind, self.last_overflow, self.last_route = False, None, None, None
         self.last_short = None  # per query: 1 where the probed cells held fewer than k rows (recomputed exactly)
-        self.last_cell_scan = None  # "query" | "block" | "wide": the cell scan of the most recent search
+        self.last_cell_scan = None  # "query" | "block" | "wide" | "long": the cell scan of the most recent search
         self._sq_block = None  # the block scan's norms (n + 1: made on its first search)
         self._width = max(4, -(-d // 4) * 4)
         self._mean = table.double().mean(0).to(table.dtype)
@@ -614,23 +618,35 @@ class NN_Wrapper:
         return cell_scan
 
     @staticmethod
+    def _check_cells_d(d, cell_scan):
+        """The feature count the cell scan ``cell_scan`` serves: up to 64 -- 65 to LONG_MAX_D under "long", and only
+        those."""
+        if cell_scan == "long":
+            if not 64 < d <= LONG_MAX_D:
+                raise ValueError(f"nn_method='ivf' with cell_scan='long' serves 65 to {LONG_MAX_D} features "
+                                 f"(65 <= d <= {LONG_MAX_D}), got d = {d}")
+        elif d > 64:
+            raise ValueError(f"nn_method='ivf' serves at most 64 features (d <= 64), got d = {d}")
+
+    @staticmethod
     def _check_cells_k(k, cell_scan):
-        """The list length the cell scan ``cell_scan`` serves: 64, the width of a wave -- 1024 under "wide"."""
-        if cell_scan == "wide":
+        """The list length the cell scan ``cell_scan`` serves: 64, the width of a wave -- 1024 under "wide" and "long"."""
+        if cell_scan in ("wide", "long"):
             if not 1 <= k <= CELLS_WIDE_MAX_K:
-                raise ValueError(f"nn_method='ivf' with cell_scan='wide' serves 1 <= nn_count <= {CELLS_WIDE_MAX_K} "
+                raise ValueError(f"nn_method='ivf' with cell_scan='{cell_scan}' serves 1 <= nn_count <= {CELLS_WIDE_MAX_K} "
                                  f"(k <= {CELLS_WIDE_MAX_K}), got k = {k}")
         elif not 1 <= k <= 64:
             raise ValueError(f"nn_method='ivf' serves 1 <= nn_count <= 64 (k <= 64), got k = {k}")
 
-    def _cell_scan_query(self, qs, ps, ex, k, wide=False):
-        """mgp_knn_cells_scan (``wide``: mgp_knn_cells_scan_wide, the same contract up to k = 1024): one wave per query
-        over the cells ``ps`` (m, p) int32 -> (best_d, best_i, short)."""
+    def _cell_scan_query(self, qs, ps, ex, k, scan="query"):
+        """mgp_knn_cells_scan (``scan`` "wide": mgp_knn_cells_scan_wide, the same contract up to k = 1024; "long":
+        mgp_knn_cells_scan_long, the same for rows of 68 to 256 stored features): one wave per query over the cells
+        ``ps`` (m, p) int32 -> (best_d, best_i, short)."""
         m, dev = qs.shape[0], qs.device
         best_d = torch.empty((m, k), device=dev, dtype=torch.float32)
         best_i = torch.empty((m, k), device=dev, dtype=torch.int32)
         short = torch.empty((m,), device=dev, dtype=torch.int32)
-        name = "mgp_knn_cells_scan_wide" if wide else "mgp_knn_cells_scan"
+        name = {"query": "mgp_knn_cells_scan", "wide": "mgp_knn_cells_scan_wide", "long": "mgp_knn_cells_scan_long"}[scan]
         _lib.check(getattr(_lib.load(), name)(
             _lib.ptr(self.train), self.train_count, self._width, _lib.ptr(self.cell_start), self.nlist, _lib.ptr(qs), m,
             _lib.ptr(ps), ps.shape[1], _lib.ptr(ex), k, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(short),
@@ -666,10 +682,11 @@ class NN_Wrapper:
         return best_i, short, overflow
 
     def _cells_nns(self, samples, nn_count, exclude=None):
-        """Probe selection, the cell scan (``cell_scan``: per query, per block of queries on the matrix cores, or per query
-        with a list of up to 1024 entries), the finish kernel; queries with too few candidates go dense.  Returns the
-        caller's row numbers."""
+        """Probe selection, the cell scan (``cell_scan``: per query, per block of queries on the matrix cores, per query
+        with a list of up to 1024 entries, or per query over rows of 65 to 256 features), the finish kernel; queries with
+        too few candidates go dense.  Returns the caller's row numbers."""
         scan = self._check_cell_scan(self.cell_scan)
+        self._check_cells_d(self.feature_count, scan)  # (the attribute may have changed since the index was built)
         self.last_cell_scan, self.last_overflow = scan, None
         q = self._pad_features(samples)
         m, k, dev = q.shape[0], int(nn_count), q.device
@@ -689,7 +706,7 @@ class NN_Wrapper:
             self.last_overflow = torch.empty_like(overflow)
             self.last_overflow[order] = overflow
         else:
-            _, best_i, short = self._cell_scan_query(qs, ps, ex, k, wide=scan == "wide")
+            _, best_i, short = self._cell_scan_query(qs, ps, ex, k, scan=scan)
         best_i.clamp_(min=0)  # (the -1 of a short list: that query is recomputed below, the finish kernel reads rows)
         si = torch.empty((m, k), dtype=torch.int64, device=dev)
         sd = torch.empty((m, k), dtype=q.dtype, device=dev)

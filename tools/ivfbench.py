@@ -24,6 +24,11 @@ exact wide scan (``last_route == "wide"``) of the same table: per shape, K and n
 for ``--repeats`` rounds after a warm-up round; medians, the exact / index ratio with the exact side's
 (max - min) / median next to it, recall@K on 4 000 sampled queries, the index build time.  Writes
 profiles/knn_ivf_wide_bench.json.
+
+``--cell-scan long --nn-count K [K ...]`` measures the long-row cell scan (``cell_scan="long"``, 65 <= d <= 256) the same
+way against the exact long-row scan (``last_route == "long"``) on the d = 100 and d = 256 shapes ->
+profiles/knn_ivf_long_bench.json.  ``MUYGPYS_HIP_LIB`` selects an A/B build of the library (tools/mkvariant.sh), as for
+every tool: the scan without its prune test is measured by the same command under ``--out``.
 """
 import argparse
 import json
@@ -45,6 +50,14 @@ SHAPES = {
     "d40_mixture": (1_000_000, 1_000_000, 40, 30, "mixture", 420),
     "d40_gaussian": (1_000_000, 1_000_000, 40, 30, "gaussian", 420),
 }
+# --cell-scan long (nn_count comes from --nn-count)
+LONG_SHAPES = {
+    "d100_mixture": (1_000_000, 1_000_000, 100, 30, "mixture", 540),
+    "d100_gaussian": (1_000_000, 1_000_000, 100, 30, "gaussian", 540),
+    "d256_mixture": (1_000_000, 1_000_000, 256, 30, "mixture", 900),
+    "d256_gaussian": (1_000_000, 1_000_000, 256, 30, "gaussian", 900),
+}
+SHAPES.update(LONG_SHAPES)
 
 
 def make_table(n, d, data, gen):
@@ -216,10 +229,10 @@ def child_block(name, rounds):
     print("RESULT " + json.dumps(rec), flush=True)
 
 
-def child_wide(name, rounds, k):
-    """The wide cell scan (cell_scan="wide") at nn_count = k and the exact wide scan, alternating in one process: per
-    nprobe the medians over `rounds` rounds (one warm-up round first), exact / index ratio next to the exact side's
-    spread, recall against the exact result."""
+def child_wide(name, rounds, k, scan="wide"):
+    """The wide cell scan (cell_scan="wide") at nn_count = k and the exact wide scan -- or (`scan` = "long") the long-row
+    cell scan and the exact long-row scan -- alternating in one process: per nprobe the medians over `rounds` rounds
+    (one warm-up round first), exact / index ratio next to the exact side's spread, recall against the exact result."""
     import torch
 
     from muygpys_amd.neighbors import NN_Wrapper
@@ -234,11 +247,11 @@ def child_wide(name, rounds, k):
     exact = NN_Wrapper(X, k)
     want = exact.get_batch_nns(bi)[0][rows].clone()
     rec["exact_route"] = exact.last_route
-    if k > 64 and exact.last_route != "wide":
-        raise RuntimeError(f"the yardstick is the exact wide scan, got last_route = {exact.last_route!r}")
+    if (scan == "long" or k > 64) and exact.last_route != scan:
+        raise RuntimeError(f"the yardstick is the exact {scan} scan, got last_route = {exact.last_route!r}")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    nn = NN_Wrapper(X, k, nn_method="ivf", nlist=None, nprobe=1, cell_scan="wide")
+    nn = NN_Wrapper(X, k, nn_method="ivf", nlist=None, nprobe=1, cell_scan=scan)
     torch.cuda.synchronize()
     rec["ivf_build_ms"] = round(1e3 * (time.perf_counter() - t0), 3)
     rec["nlist"] = nn.nlist
@@ -251,17 +264,17 @@ def child_wide(name, rounds, k):
         if nprobe > nn.nlist:
             continue
         nn.nprobe = nprobe
-        ms = {"wide": [], "exact": []}
+        ms = {scan: [], "exact": []}
         for rnd in range(rounds + 1):  # (round 0 warms up)
             (got, _), t = event_ms(lambda: nn.get_batch_nns(bi))
             got = got[rows].clone()
             _, te = event_ms(lambda: exact.get_batch_nns(bi))
             if rnd:
-                ms["wide"].append(t)
+                ms[scan].append(t)
                 ms["exact"].append(te)
-        ws, es = stats(ms["wide"]), stats(ms["exact"])
-        row = {"nprobe": nprobe, "wide": ws, "exact": es,
-               "wide_over_exact_speedup": round(es["median_ms"] / ws["median_ms"], 3),
+        ws, es = stats(ms[scan]), stats(ms["exact"])
+        row = {"nprobe": nprobe, scan: ws, "exact": es,
+               f"{scan}_over_exact_speedup": round(es["median_ms"] / ws["median_ms"], 3),
                "exact_spread": round((es["max_ms"] - es["min_ms"]) / es["median_ms"], 4),
                # (in slices of 256 queries: the (queries, k, k) comparison is 4 GB at k = 1023)
                "recall_at_k": round(sum(float((got[s:s + 256, :, None] == want[s:s + 256, None, :]).any(2).sum())
@@ -274,25 +287,31 @@ def child_wide(name, rounds, k):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="*", default=list(SHAPES), choices=list(SHAPES))
+    ap.add_argument("--shapes", nargs="*", default=None, choices=list(SHAPES),
+                    help="default: the d = 100 and d = 256 shapes under --cell-scan long, every other shape otherwise")
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--cell-scan", default="query", choices=["query", "block", "wide"],
+    ap.add_argument("--cell-scan", default="query", choices=["query", "block", "wide", "long"],
                     help="block: the block cell scan against the per-query one and the exact scan, alternating "
                          "(--repeats rounds) -> profiles/knn_ivf_block_bench.json; wide: the wide cell scan at "
-                         "--nn-count against the exact wide scan, alternating -> profiles/knn_ivf_wide_bench.json")
-    ap.add_argument("--nn-count", type=int, nargs="+", default=[100], help="--cell-scan wide: the list lengths (1 .. 1024)")
+                         "--nn-count against the exact wide scan, alternating -> profiles/knn_ivf_wide_bench.json; long: "
+                         "the long-row cell scan against the exact long-row scan -> profiles/knn_ivf_long_bench.json")
+    ap.add_argument("--nn-count", type=int, nargs="+", default=[100], help="--cell-scan wide | long: the list lengths (1 .. 1024)")
     ap.add_argument("--out", default="")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.child and args.cell_scan == "wide":
-        return child_wide(args.child, args.repeats, args.nn_count[0])
+    lists = args.cell_scan in ("wide", "long")  # (one child per shape and list length)
+    if args.shapes is None:
+        args.shapes = [name for name in SHAPES if (name in LONG_SHAPES) == (args.cell_scan == "long")]
+    if args.child and lists:
+        return child_wide(args.child, args.repeats, args.nn_count[0], args.cell_scan)
     if args.child:
         return (child_block if args.cell_scan == "block" else child)(args.child, args.repeats)
     if not args.out:
-        args.out = os.path.join(ROOT, "profiles", {"block": "knn_ivf_block_bench.json", "wide": "knn_ivf_wide_bench.json"}
+        args.out = os.path.join(ROOT, "profiles", {"block": "knn_ivf_block_bench.json", "wide": "knn_ivf_wide_bench.json",
+                                                      "long": "knn_ivf_long_bench.json"}
                                 .get(args.cell_scan, "knn_ivf_bench.json"))
     results = []
-    runs = [(name, k) for name in args.shapes for k in (args.nn_count if args.cell_scan == "wide" else [None])]
+    runs = [(name, k) for name in args.shapes for k in (args.nn_count if lists else [None])]
     for name, k in runs:  # chained: a child that fails, faults or runs out of time ends the run
         cmd = ["timeout", "-k", "10", str(SHAPES[name][5]), sys.executable, os.path.abspath(__file__), "--child", name,
                "--repeats", str(args.repeats), "--cell-scan", args.cell_scan]
@@ -306,7 +325,8 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         tool = "tools/ivfbench.py" + (f" --cell-scan {args.cell_scan}" if args.cell_scan != "query" else "")
-        json.dump({"tool": tool, "nprobes": NPROBES, "shapes": results}, f, indent=1)
+        json.dump({"tool": tool, "library": os.environ.get("MUYGPYS_HIP_LIB", "") or "the regular build",
+                   "nprobes": NPROBES, "shapes": results}, f, indent=1)
         f.write("\n")
     return 0 if len(results) == len(runs) else 1
 
