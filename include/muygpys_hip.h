@@ -711,6 +711,23 @@ int mgp_knn_scan_bf16x2_d8(const float* train, const void* packed_train, const f
                            const float* queries, const void* packed_queries, const float* query_sqn,
                            const int64_t* self_idx, int64_t m, int k, int64_t start,
                            float* best_d, int32_t* best_i, int32_t* overflow, void* stream);
+/* The split-bf16 pre-filter for LONG rows (csrc/mgp_knn_long_bf16.hip): the parameters and the whole contract of
+ * mgp_knn_scan_bf16x3 -- packed rows [hi(KP) | lo(KP)], KP = 16 ceil((d + 2) / 16) = 80 .. 272, slots KP - 2, KP - 1 the
+ * split of (c, 1) in a table row and of (1, 0) in a query row, best_d IN / OUT exact difference-form distances, k <= 64,
+ * the 16-entry queues and the `overflow` flag -- for d % 4 == 0, 68 <= d <= 256 (no type suffix: there is no fp64 twin).
+ * The table side is staged in chunks of at most four matrix steps and the accumulators carry across them.  One
+ * accumulator sums 3 KP products, so the error of the computed q.x is bounded by E(KP) |q| |x|,
+ * E(KP) = 3.1 x 2^-16 + 1.01 x 3 KP x 2^-23 (not the 2^-14 of the short rows), and the caller builds
+ *   c = -|x|^2/2 + E(KP) QMAX |x|, raised by R(KP) |c|, R(KP) = 2^-16 + 1.01 x 3 KP x 2^-23
+ * (muygpys_amd.neighbors.prefilter_margin / prefilter_raise); query_sqn is |q|^2 rounded once to fp32.
+ * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), nothing to do (m == 0 or start >= n: MGP_OK, pointers
+ * not looked at), NULL pointers (MGP_EINVAL; self_idx and the stream are optional), then MGP_EUNSUPPORTED for k > 64,
+ * d outside {68, 72, .. 256}, alignment and n >= 2^31.  Any start is accepted: rows past n are masked by position.
+ * d <= 64 is MGP_EUNSUPPORTED here, and mgp_knn_scan_bf16x3 keeps refusing d > 64. */
+int mgp_knn_scan_long_bf16x3(const float* train, const void* packed_train, const float* train_sqn, int64_t n, int d,
+                             const float* queries, const void* packed_queries, const float* query_sqn,
+                             const int64_t* self_idx, int64_t m, int k, int64_t start,
+                             float* best_d, int32_t* best_i, int32_t* overflow, void* stream);
 
 /* Approximate search over an inverted-cell (IVF) index: every query scans only the rows of its probed cells.  Replaces
  * the reference's approximate branch (hnswlib behind NN_Wrapper, src/MuyGPyS/neighbors.py:109-127 build, :213-262

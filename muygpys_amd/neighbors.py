@@ -24,6 +24,11 @@ squared-l2 distances)`` with the self-match dropped for batch queries (neighbors
   a 64-row tile staged in ceil(d / 64) feature chunks with the accumulators carried across them -- from
   ``SCAN_INIT_ROWS`` head rows, then the same finish entries.  4 to 10 times the dense path at 1 M x 1 M
   (``profiles/knn_long_bench.json``); ``MUYGPYS_HIP_KNN_LONG=0`` keeps these searches on the dense path.
+  ``scan_kind="prefilter"`` (opt-in) serves ``k <= 64`` there through ``mgp_knn_scan_long_bf16x3``
+  (``csrc/mgp_knn_long_bf16.hip``): the split-bf16 pre-filter of the short rows, the table side staged in chunks of at most
+  four matrix steps, every survivor re-measured exactly.  Its margin is derived for the packed row length
+  (``prefilter_margin``: one accumulator sums up to 816 products, not 240); ``k > 64`` stays on the wide long scan.  At any
+  other width ``"prefilter"`` is ``"bf16x3"``.  A/B against the default: ``profiles/knn_long_bf16_bench.json``.
 * anything else (fp64 tables, tables of up to 8 192 rows, ``use_scan=False``, d > 256): the dense path, in row chunks,
   ``|q|^2 + |x|^2 - 2 q.x`` through ``torch.matmul`` (rocBLAS) followed by ``topk``.
 
@@ -99,6 +104,27 @@ GRID_CELL_ROWS = 16    # mean rows per cell of a grid where the caller names non
 def stored_width(d: int) -> int:
     """The row width the scan kernels see: the next multiple of four, four at least (rows are zero-padded to it)."""
     return max(4, -(-int(d) // 4) * 4)
+
+
+def packed_width(width: int) -> int:
+    """KP of the packed rows [hi(KP) | lo(KP)]: the stored width and the two threshold slots, in whole matrix steps of 16."""
+    return (int(width) + 2 + 15) // 16 * 16
+
+
+def prefilter_margin(kp: int) -> float:
+    """E(KP): |computed q.x - q.x| <= E(KP) |q| |x| for the three split-bf16 chains of ``mgp_knn_scan_long_bf16x3`` over
+    packed rows of ``kp`` slots (csrc/mgp_knn_long_bf16.hip).  The dropped lo.lo and split-residual
+    terms, 3.1 x 2^-16 sum |q_i x_i|, plus the accumulation of N = 3 kp products at a unit roundoff of 2^-23 per addition
+    (the matrix unit's rounding is not specified), N 2^-23 over terms that sum to at most 1.01 sum |q_i x_i|; then
+    Cauchy-Schwarz.  2^-14, the constant of the rows of up to 64 features, was derived for 240 products and is below this
+    at every long row (kp = 272: 2.4 x 2^-14)."""
+    return 3.1 * 2.0**-16 + 1.01 * 3 * int(kp) * 2.0**-23
+
+
+def prefilter_raise(kp: int) -> float:
+    """R(KP): the relative amount the threshold term c is raised by (and the kernel lowers thr by): the accumulation
+    error of 3 kp additions on the term itself, its bf16 x 2 split (2^-18) and the rounding of the norm to fp32."""
+    return 2.0**-16 + 1.01 * 3 * int(kp) * 2.0**-23
 
 
 def _switch(name: str) -> bool:
@@ -243,10 +269,11 @@ class NN_Wrapper:
         self.nn_method = "exact"
         self.chunk = int(chunk)
         self.use_scan = bool(use_scan)
-        if scan_kind not in ("auto", "bf16x3", "f32"):
-            raise ValueError("scan_kind must be 'auto', 'bf16x3' or 'f32'")
+        if scan_kind not in ("auto", "bf16x3", "f32", "prefilter"):
+            raise ValueError("scan_kind must be 'auto', 'bf16x3', 'f32' or 'prefilter'")
         # measured (1 M x 1 M, end to end): split-bf16 pre-filter 0.47 s (d = 40) / 0.36 s (d = 8),
         # plain fp32 scan 0.90 s / 0.43 s
+        # "prefilter" (opt-in): the split-bf16 pre-filter on the long rows too (k <= 64); "bf16x3" at every other width
         self.scan_kind = "bf16x3" if scan_kind == "auto" else scan_kind
         self._packed_train, self._packed_qmax, self._packed_layout = None, None, None
         self.last_overflow = None  # per-query overflow flags of the most recent scan (device int32)
@@ -349,7 +376,8 @@ class NN_Wrapper:
         # survivor per tile
         wide = k > 64 or force_wide
         long_rows = route == "long"
-        tile_rows = 128 if (self.scan_kind == "bf16x3" and self._width + 2 <= 16) else 64
+        packed = self.scan_kind in ("bf16x3", "prefilter")
+        tile_rows = 128 if (packed and self._width + 2 <= 16) else 64
         init_rows = SCAN_INIT_ROWS if wide or long_rows else min(SCAN_INIT_ROWS, max(1024, -(-(tile_rows * k // 2) // 1024) * 1024))
         head = self.train[:init_rows]
         best_d = torch.empty((m, k), device=q.device, dtype=torch.float32)
@@ -379,7 +407,9 @@ class NN_Wrapper:
         ex64 = None if exclude is None else exclude.to(torch.int64).contiguous()
         if wide:
             return self._wide_nns(q, qn, ex64, exclude, init_rows, best_d, best_i, overflow, long_rows)
-        if self.scan_kind == "bf16x3" and not long_rows:  # (the long rows have no split-bf16 pre-filter)
+        if long_rows and self.scan_kind == "prefilter":
+            rc = self._prefilter_long_scan(q, qn, ex64, init_rows, best_d, best_i, overflow)
+        elif packed and not long_rows:  # (the long rows' pre-filter is opt-in: scan_kind="prefilter")
             # the split-bf16 kernel keeps exact (difference-form) distances in the lists
             for s in range(0, m, 65536):
                 diff = q[s:s + 65536, None, :] - self.train[best_i[s:s + 65536].to(torch.int64)]
@@ -419,6 +449,36 @@ class NN_Wrapper:
         _lib.check(rc, "mgp_knn_scan_f32")
         self.last_route = route
         return self._finish_nns(_lib.load().mgp_knn_finish_f32, "mgp_knn_finish_f32", q, best_i, overflow, exclude)
+
+    def _prefilter_long_scan(self, q, qn, ex64, init_rows, best_d, best_i, overflow):
+        """mgp_knn_scan_long_bf16x3 (stored widths 68 to 256, k <= 64) on lists that hold the k-best of the head rows;
+        returns its status."""
+        (m, k), d = best_d.shape, self._width
+        kp = packed_width(d)
+        # the kernel keeps exact (difference-form) distances in the lists: the head lists re-measured, the (rows, k, d)
+        # temporary and its squares sized from a byte budget (a fixed 65 536 rows would be 4.3 GB at k = 64, d = 256);
+        # |q|^2 rounded once from fp64 in the same pass (the kernel's threshold allows 2^-23 |q|^2 for it)
+        rows = max(1, min(65536, self.FINISH_BUDGET_BYTES // (2 * k * d * q.element_size())))
+        qn = torch.empty_like(qn)
+        for s in range(0, m, rows):
+            diff = q[s:s + rows, None, :] - self.train[best_i[s:s + rows].to(torch.int64)]
+            best_d[s:s + rows] = (diff * diff).sum(-1)
+            qn[s:s + rows] = (q[s:s + rows].double() ** 2).sum(1).to(q.dtype)
+        # table rows carry c = -|x|^2/2 + E(KP) QMAX |x| (raised by R(KP) |c|) and a 1; the QMAX head-room rule and the
+        # cache are those of the short rows (layout "long": the two never share a table)
+        qmax = float(qn.max().sqrt())
+        if self._packed_train is None or self._packed_layout != "long" or qmax > self._packed_qmax:
+            self._packed_layout = "long"
+            self._packed_qmax = 1.25 * qmax
+            c = -0.5 * self._sq + (prefilter_margin(kp) * self._packed_qmax) * self._sq.sqrt()
+            c = c + prefilter_raise(kp) * c.abs()
+            self._packed_train = self._pack_bf16(self.train, c, 1.0)
+        packed_q = self._pack_bf16(q, 1.0, 0.0)
+        return _lib.load().mgp_knn_scan_long_bf16x3(
+            _lib.ptr(self.train), _lib.ptr(self._packed_train), _lib.ptr(self._sq_scan), self.train_count, d,
+            _lib.ptr(q), _lib.ptr(packed_q), _lib.ptr(qn), _lib.ptr(ex64), m, k, init_rows,
+            _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
+        )
 
     FINISH_BUDGET_BYTES = 1 << 30  # the (rows, k, d) temporary of the torch finish step, where the kernel declines
 

@@ -20,7 +20,16 @@ does not end cleanly.  Per line, one table of --n Gaussian rows and --queries te
 Every figure is a host clock around work that ends in a device synchronise.  On the slice the dense leg answers, the two
 routes' distances are compared (the largest relative difference is in the entry).
 
-An existing --out file is updated entry by entry, so the shapes can be measured over several runs."""
+An existing --out file is updated entry by entry, so the shapes can be measured over several runs.
+
+    python tools/knnlongbench.py --prefilter [--d 68 100 128 256] [--k 30] [--rounds 3]
+                                 [--out profiles/knn_long_bf16_bench.json]
+
+The split-bf16 pre-filter of the long rows (scan_kind="prefilter": mgp_knn_scan_long_bf16x3) against the default route
+(scan_kind="auto": mgp_knn_scan_long) on the same table and queries, one process per line: both objects warmed up on
+--probe queries, then --rounds rounds (3 at least) that alternate baseline and pre-filter, all queries in one call each.
+Reported: the two medians, every round, the spread of the baseline side ((max - min) / median), the ratio of the medians
+and whether the pre-filter is ahead by more than that spread; the share of ranks at which the two name the same row."""
 import argparse
 import json
 import os
@@ -80,24 +89,62 @@ def bench_line(d, k, args):
     }
 
 
+def prefilter_line(d, k, args):
+    import torch
+
+    from muygpys_amd.neighbors import NN_Wrapper
+
+    g = torch.Generator(device="cuda").manual_seed(d)
+    X = torch.randn(args.n, d, device="cuda", generator=g)
+    Q = torch.randn(args.queries, d, device="cuda", generator=g)
+    base, pre = NN_Wrapper(X, k), NN_Wrapper(X, k, scan_kind="prefilter")
+    for nn in (base, pre):  # warm-up: code objects, the packed table, rocBLAS's choice for the head rows
+        nn.get_nns(Q[:min(Q.shape[0], args.probe)])
+        assert nn.last_route == "long", nn.last_route
+    t_base, t_pre = [], []
+    for _ in range(max(3, args.rounds)):
+        tb, (bi, bd) = timed(lambda: base.get_nns(Q))
+        tp, (pi, pd) = timed(lambda: pre.get_nns(Q))
+        t_base.append(tb)
+        t_pre.append(tp)
+    base_ms, pre_ms = 1e3 * statistics.median(t_base), 1e3 * statistics.median(t_pre)
+    spread = (max(t_base) - min(t_base)) * 1e3 / base_ms
+    return {
+        "n": args.n, "queries": Q.shape[0], "d": d, "stored_width": pre.train.shape[1], "k": k,
+        "baseline_ms": round(base_ms, 1), "baseline_ms_rounds": [round(1e3 * t, 1) for t in t_base],
+        "prefilter_ms": round(pre_ms, 1), "prefilter_ms_rounds": [round(1e3 * t, 1) for t in t_pre],
+        "baseline_spread": round(spread, 4), "ratio_baseline_over_prefilter": round(base_ms / pre_ms, 3),
+        "ahead_by_more_than_the_spread": bool(base_ms / pre_ms > 1.0 + spread),
+        "share_of_ranks_with_the_same_row": round(float((bi == pi).double().mean()), 6),
+        "largest_relative_distance_difference": float(((bd.double() - pd.double()).abs() / bd.double().clamp(min=1e-30)).max()),
+        "flagged": int(pre.last_overflow.sum()), "baseline_flagged": int(base.last_overflow.sum()),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=1_000_000)
-    ap.add_argument("--d", type=int, nargs="+", default=[2, 3, 10, 30, 68, 100, 128, 192, 256])
-    ap.add_argument("--k", type=int, nargs="+", default=[30, 100])
+    ap.add_argument("--d", type=int, nargs="+", help="default: 2 3 10 30 68 100 128 192 256 (--prefilter: 68 100 128 256)")
+    ap.add_argument("--k", type=int, nargs="+", help="default: 30 100 (--prefilter: 30)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--dense-passes", type=int, default=4)
     ap.add_argument("--probe", type=int, default=65536)
     ap.add_argument("--line-timeout", type=float, default=240.0, help="seconds one (d, k) process may take")
     ap.add_argument("--line", type=int, nargs=2, metavar=("D", "K"), help="measure this one line and print it (the child)")
-    ap.add_argument("--out", default=os.path.join("profiles", "knn_long_bench.json"))
+    ap.add_argument("--prefilter", action="store_true", help="scan_kind='prefilter' against the default route (long rows, k <= 64)")
+    ap.add_argument("--rounds", type=int, default=3, help="--prefilter: alternating rounds (3 at least)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "knn_long_bf16_bench.json" if args.prefilter else "knn_long_bench.json")
+    args.d = args.d or ([68, 100, 128, 256] if args.prefilter else [2, 3, 10, 30, 68, 100, 128, 192, 256])
+    args.k = args.k or ([30] if args.prefilter else [30, 100])
     if args.line:
         import torch
 
         assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
-        entry = bench_line(args.line[0], args.line[1], args)
+        entry = (prefilter_line if args.prefilter else bench_line)(args.line[0], args.line[1], args)
         entry["device"] = torch.cuda.get_device_name(0)
         print("LINE " + json.dumps(entry), flush=True)
         return 0
@@ -105,14 +152,19 @@ def main():
     if os.path.exists(args.out):
         with open(args.out) as f:
             result = json.load(f)
-    result["what"] = ("NN_Wrapper.get_nns, Gaussian table and queries, fp32; ms for all queries, the median of the repeats; "
-                      "new = the default route on all queries, dense = use_scan=False on a slice of whole passes, scaled "
-                      "(dense_scaled_from_slice); one process per line; speedup = dense over new")
+    if args.prefilter:
+        result["what"] = ("NN_Wrapper.get_nns, Gaussian table and queries, fp32; ms for all queries; baseline = scan_kind='auto' "
+                          "(mgp_knn_scan_long), prefilter = scan_kind='prefilter' (mgp_knn_scan_long_bf16x3), alternating in one "
+                          "process per line, medians over the rounds; baseline_spread = (max - min) / median of the baseline")
+    else:
+        result["what"] = ("NN_Wrapper.get_nns, Gaussian table and queries, fp32; ms for all queries, the median of the repeats; "
+                          "new = the default route on all queries, dense = use_scan=False on a slice of whole passes, scaled "
+                          "(dense_scaled_from_slice); one process per line; speedup = dense over new")
     for d in args.d:
         for k in args.k:
             cmd = [sys.executable, os.path.abspath(__file__), "--line", str(d), str(k), "--n", str(args.n), "--queries",
                    str(args.queries), "--repeats", str(args.repeats), "--dense-passes", str(args.dense_passes), "--probe",
-                   str(args.probe)]
+                   str(args.probe)] + (["--prefilter", "--rounds", str(args.rounds)] if args.prefilter else [])
             try:
                 p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=args.line_timeout)
             except subprocess.TimeoutExpired:
