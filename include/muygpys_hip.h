@@ -728,6 +728,24 @@ int mgp_knn_scan_long_bf16x3(const float* train, const void* packed_train, const
                              const float* queries, const void* packed_queries, const float* query_sqn,
                              const int64_t* self_idx, int64_t m, int k, int64_t start,
                              float* best_d, int32_t* best_i, int32_t* overflow, void* stream);
+/* The split-bf16 pre-filter for the WIDE lists (csrc/mgp_knn_wide_bf16.hip): the parameters, the packed rows and the
+ * margin of mgp_knn_scan_bf16x3 (three-chain layout at every d, KP = 16 ceil((d + 2) / 16) = 16 .. 80, at most 240 products
+ * per accumulator: c = -|x|^2/2 + 2^-14 QMAX |x|, raised by 2^-15 |c|) under the contract of mgp_knn_scan_wide: 1 <= k <=
+ * 1024, the lists unordered in global memory, whole IN lists (start >= k, + 1 with self_idx), `overflow` accepted, not
+ * NULL, never written -- with best_d IN / OUT exact difference-form distances, as in mgp_knn_scan_bf16x3.  Survivors are
+ * kept as one bit per (tile of the window, column) and query, a window of mgp_knn_wide_bf16_window() = 8 tiles, and are
+ * re-measured exactly when the window is drained: when it is full, at the last tile, and otherwise every
+ * clamp(rows seen / 64, one tile, the window) rows.  A window cannot hold more survivors than it has bits.
+ * Order of the checks, all before any HIP call: sizes (MGP_EINVAL), nothing to do (m == 0 or start >= n: MGP_OK, pointers
+ * not looked at), NULL pointers (MGP_EINVAL; self_idx and the stream are optional), then MGP_EUNSUPPORTED for k > 1024,
+ * d outside {4, 8, .. 64}, alignment of train / queries / packed_train / packed_queries, n >= 2^31, and k + 1 > start with
+ * self_idx (k > start without).  Any start that passes is accepted: rows past n are masked by position.  (No type
+ * suffix: there is no fp64 twin.) */
+int mgp_knn_wide_bf16_window(void);
+int mgp_knn_scan_wide_bf16x3(const float* train, const void* packed_train, const float* train_sqn, int64_t n, int d,
+                             const float* queries, const void* packed_queries, const float* query_sqn,
+                             const int64_t* self_idx, int64_t m, int k, int64_t start,
+                             float* best_d, int32_t* best_i, int32_t* overflow, void* stream);
 
 /* Approximate search over an inverted-cell (IVF) index: every query scans only the rows of its probed cells.  Replaces
  * the reference's approximate branch (hnswlib behind NN_Wrapper, src/MuyGPyS/neighbors.py:109-127 build, :213-262

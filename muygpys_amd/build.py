@@ -35,6 +35,8 @@ PER_FILE_FLAGS = {
     "mgp_knn_long.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
     # (... and their split-bf16 pre-filter form: tests/test_knn_long_bf16_status_cpu.py reads its records)
     "mgp_knn_long_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
+    # (... and the wide lists' pre-filter: tests/test_knn_wide_bf16_status_cpu.py reads its records)
+    "mgp_knn_wide_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Rpass-analysis=kernel-resource-usage"],
     # the 64-step elimination must unroll completely (the fp64 / 16-response body exceeds the default
     # pragma-unroll budget, and a rolled loop indexes the 128-register row at run time = in scratch)
     "mgp_fused_rhs.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],

@@ -133,6 +133,10 @@ constexpr int KNN_WIDE_MAX_K = 1024;
 int launch_knn_scan_wide(const KnnArgs&, hipStream_t);
 int launch_knn_finish_wide(const float* queries, const float* train, int d, const int* cand, int64_t m, int k,
                            const int64_t* perm, int64_t* out_idx, float* out_dist, hipStream_t);
+// the wide lists behind the split-bf16 pre-filter (mgp_knn_wide_bf16.hip): packed operands as for launch_knn_scan_packed
+// (layout 0), survivors in a ring of bit masks over KNN_PW_WINDOW tiles, re-measured exactly when the window drains
+constexpr int KNN_PW_WINDOW = 8;
+int launch_knn_prefilter_wide(const KnnPackedArgs&, hipStream_t);
 // the two scans for rows of 68 to KNN_LONG_MAX_D features (mgp_knn_long.hip): the tile staged chunk by chunk, the
 // accumulators carried across the chunks; the finish steps above serve these rows as they are
 constexpr int KNN_LONG_MAX_D = 256;

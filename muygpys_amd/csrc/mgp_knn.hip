@@ -276,8 +276,6 @@ namespace mgp {
 #define MGP_KNN_T(slot)
 #endif
 
-typedef __bf16 bf8x __attribute__((ext_vector_type(8)));
-
 constexpr int KB_RB = 32;     // queries per row block (one 32 x 32 matrix tile's rows)
 constexpr int KB_CAP = 16;    // queue entries per query
 #ifndef MGP_KNN_STAGGER
@@ -286,9 +284,7 @@ constexpr int KB_CAP = 16;    // queue entries per query
 #ifndef MGP_KNN_SCAN_BLOCK
 #define MGP_KNN_SCAN_BLOCK 16   // list entries loaded together when a survivor is inserted (32: the drain spills more, slower)
 #endif
-#ifndef MGP_KNN_CADENCE
-#define MGP_KNN_CADENCE 64      // drain interval = rows seen / this (0: the fixed schedule of rounds 1-4)
-#endif
+// (MGP_KNN_CADENCE, the drain interval, and neg_thr_split: mgp_knn_common.h -- mgp_knn_wide_bf16.hip uses them too)
 #ifndef MGP_KNN_REGSTAGE
 #define MGP_KNN_REGSTAGE 1
 #endif
@@ -301,19 +297,6 @@ constexpr int KB_CAP = 16;    // queue entries per query
 #ifndef MGP_KNN_CADENCE_MAX
 #define MGP_KNN_CADENCE_MAX 16384
 #endif
-
-__device__ __forceinline__ unsigned bf16_rne(float x) {  // bits of bf16(x), round to nearest even
-  const unsigned u = __float_as_uint(x);
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-// -thr as (hi, lo) bf16 bits, with thr first lowered by 2^-14 |thr| (covers the split's own error)
-__device__ __forceinline__ void neg_thr_split(float qn, float tau, unsigned& hi, unsigned& lo) {
-  float thr = fminf(0.5f * (qn - tau), 1e38f);  // tau = -inf (rows past the end): nothing ever passes
-  thr -= 6.103515625e-05f * fabsf(thr);
-  const float v = -thr;
-  hi = bf16_rne(v);
-  lo = bf16_rne(v - __uint_as_float(hi << 16));
-}
 
 // TN: training rows per staged tile.  64 for the wider rows; 128 at KP = 16 (d <= 14: BASELINE config 4's d = 8), where a
 // 64-row tile is only 12 MFMAs per wave between two workgroup barriers (round 4: the 10 M-point search of config 4 ran at

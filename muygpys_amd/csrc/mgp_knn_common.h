@@ -69,6 +69,25 @@ __device__ __forceinline__ float cell_unkey(unsigned key) {
   return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
 }
 
+// the split-bf16 pre-filters (mgp_knn.hip, mgp_knn_long_bf16.hip, mgp_knn_wide_bf16.hip): eight packed slots of an operand
+typedef __bf16 bf8x __attribute__((ext_vector_type(8)));
+#ifndef MGP_KNN_CADENCE
+#define MGP_KNN_CADENCE 64      // drain interval = rows seen / this (0: the fixed schedule of rounds 1-4)
+#endif
+__device__ __forceinline__ unsigned bf16_rne(float x) {  // bits of bf16(x), round to nearest even
+  const unsigned u = __float_as_uint(x);
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+// -thr as (hi, lo) bf16 bits, with thr first lowered by 2^-14 |thr| (covers the split's own error): packed rows of up
+// to 80 slots, at most 240 products per accumulator
+__device__ __forceinline__ void neg_thr_split(float qn, float tau, unsigned& hi, unsigned& lo) {
+  float thr = fminf(0.5f * (qn - tau), 1e38f);  // tau = -inf (rows past the end): nothing ever passes
+  thr -= 6.103515625e-05f * fabsf(thr);
+  const float v = -thr;
+  hi = bf16_rne(v);
+  lo = bf16_rne(v - __uint_as_float(hi << 16));
+}
+
 // a list wider than a wave, held by the draining wave (mgp_knn_wide.hip, mgp_knn_long.hip): the distances of query q's
 // list, entry e * 64 + lane in v[e]; -inf where the list has no such entry
 __device__ __forceinline__ void load_list(const float* best_d, int64_t q, int k, int lane, float (&v)[KNN_EPL]) {

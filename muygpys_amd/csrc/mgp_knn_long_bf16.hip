@@ -70,8 +70,6 @@
 namespace mgp {
 namespace {
 
-typedef __bf16 bf8x __attribute__((ext_vector_type(8)));
-
 constexpr int PL_SC = 4;                                  // matrix steps per chunk, at most
 constexpr int PL_BUF = KNN_TN * (4 * PL_SC + 1) * 16;     // bytes of one staging buffer: 64 rows x 17 slots
 constexpr int PL_RB2_MAX_NQ = 6;                          // two row blocks per wave up to this many steps (the register report)

@@ -19,6 +19,11 @@ squared-l2 distances)`` with the self-match dropped for batch queries (neighbors
   the draining wave as ceil(k / 64) entries per lane, a queue slot per column of the tile, so no queue can overflow;
   the lists start from ``SCAN_INIT_ROWS`` head rows.  3 to 24 times the dense path at 1 M x 1 M
   (``profiles/knn_wide_bench.json``); ``MUYGPYS_HIP_KNN_WIDE=0`` keeps these searches on the dense path.
+  ``scan_kind="prefilter"`` (opt-in) runs them through ``mgp_knn_scan_wide_bf16x3`` (``csrc/mgp_knn_wide_bf16.hip``)
+  instead: the narrow scan's packed table (three-chain layout at every width) and its split-bf16 pre-filter, the
+  survivors kept as one bit per (tile, column) over a window of eight tiles and re-measured exactly when the window
+  drains, the same lists and finish step; where the entry declines, the fp32 wide scan serves the call.  ``last_route``
+  stays "wide".  A/B against the default: ``profiles/knn_wide_bf16_bench.json``.
 * fp32, ``64 < d <= 256`` (the reference torch tutorial's 100-dimensional embedding), ``k <= 1024``: the long-row scans
   ``mgp_knn_scan_long`` (k <= 64) / ``mgp_knn_scan_long_wide`` (``csrc/mgp_knn_long.hip``) -- the same arithmetic,
   a 64-row tile staged in ceil(d / 64) feature chunks with the accumulators carried across them -- from
@@ -27,8 +32,9 @@ squared-l2 distances)`` with the self-match dropped for batch queries (neighbors
   ``scan_kind="prefilter"`` (opt-in) serves ``k <= 64`` there through ``mgp_knn_scan_long_bf16x3``
   (``csrc/mgp_knn_long_bf16.hip``): the split-bf16 pre-filter of the short rows, the table side staged in chunks of at most
   four matrix steps, every survivor re-measured exactly.  Its margin is derived for the packed row length
-  (``prefilter_margin``: one accumulator sums up to 816 products, not 240); ``k > 64`` stays on the wide long scan.  At any
-  other width ``"prefilter"`` is ``"bf16x3"``.  A/B against the default: ``profiles/knn_long_bf16_bench.json``.
+  (``prefilter_margin``: one accumulator sums up to 816 products, not 240); ``k > 64`` stays on the wide long scan.  At a
+  stored width of up to 64 and ``k <= 64`` ``"prefilter"`` is ``"bf16x3"``.  A/B against the default:
+  ``profiles/knn_long_bf16_bench.json``.
 * anything else (fp64 tables, tables of up to 8 192 rows, ``use_scan=False``, d > 256): the dense path, in row chunks,
   ``|q|^2 + |x|^2 - 2 q.x`` through ``torch.matmul`` (rocBLAS) followed by ``topk``.
 
@@ -273,7 +279,8 @@ class NN_Wrapper:
             raise ValueError("scan_kind must be 'auto', 'bf16x3', 'f32' or 'prefilter'")
         # measured (1 M x 1 M, end to end): split-bf16 pre-filter 0.47 s (d = 40) / 0.36 s (d = 8),
         # plain fp32 scan 0.90 s / 0.43 s
-        # "prefilter" (opt-in): the split-bf16 pre-filter on the long rows too (k <= 64); "bf16x3" at every other width
+        # "prefilter" (opt-in): the split-bf16 pre-filter on the long rows too (k <= 64) and in front of the wide lists
+        # (k > 64 at a stored width of up to 64); "bf16x3" everywhere else
         self.scan_kind = "bf16x3" if scan_kind == "auto" else scan_kind
         self._packed_train, self._packed_qmax, self._packed_layout = None, None, None
         self.last_overflow = None  # per-query overflow flags of the most recent scan (device int32)
@@ -406,6 +413,10 @@ class NN_Wrapper:
         overflow = torch.zeros((m,), device=q.device, dtype=torch.int32)
         ex64 = None if exclude is None else exclude.to(torch.int64).contiguous()
         if wide:
+            if self.scan_kind == "prefilter" and k > 64 and not long_rows:  # (opt-in; declined: the fp32 wide scan)
+                out = self._prefilter_wide_nns(q, qn, ex64, exclude, init_rows, best_d, best_i, overflow)
+                if out is not None:
+                    return out
             return self._wide_nns(q, qn, ex64, exclude, init_rows, best_d, best_i, overflow, long_rows)
         if long_rows and self.scan_kind == "prefilter":
             rc = self._prefilter_long_scan(q, qn, ex64, init_rows, best_d, best_i, overflow)
@@ -425,15 +436,10 @@ class NN_Wrapper:
             pack = self._pack_bf16_d8 if d8 else self._pack_bf16
             scan = _lib.load().mgp_knn_scan_bf16x2_d8 if d8 else _lib.load().mgp_knn_scan_bf16x3
             # (the cache remembers WHICH layout it holds: the A/B switch may be flipped on a live object)
-            if self._packed_train is None or self._packed_layout != d8 or qmax > self._packed_qmax:
-                self._packed_layout = d8
-                self._packed_qmax = 1.25 * qmax
-                c = -0.5 * self._sq + (2.0**-14 * self._packed_qmax) * self._sq.sqrt()
-                c = c + 2.0**-15 * c.abs()
-                self._packed_train = pack(self.train, c, 1.0)
+            packed_train = self._short_packed_table(qmax, d8)
             packed_q = pack(q, 1.0, 0.0)
             rc = scan(
-                _lib.ptr(self.train), _lib.ptr(self._packed_train), _lib.ptr(self._sq_scan), self.train_count,
+                _lib.ptr(self.train), _lib.ptr(packed_train), _lib.ptr(self._sq_scan), self.train_count,
                 self._width, _lib.ptr(q), _lib.ptr(packed_q), _lib.ptr(qn), _lib.ptr(ex64), m, k,
                 init_rows, _lib.ptr(best_d), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
             )
@@ -449,6 +455,43 @@ class NN_Wrapper:
         _lib.check(rc, "mgp_knn_scan_f32")
         self.last_route = route
         return self._finish_nns(_lib.load().mgp_knn_finish_f32, "mgp_knn_finish_f32", q, best_i, overflow, exclude)
+
+    def _short_packed_table(self, qmax, d8):
+        """The packed table of the stored widths up to 64 (``d8``: the 24-slot rows of the two-chain kernel), rebuilt
+        only where the cache holds another layout or was packed for a smaller QMAX."""
+        if self._packed_train is None or self._packed_layout != d8 or qmax > self._packed_qmax:
+            self._packed_layout = d8
+            self._packed_qmax = 1.25 * qmax
+            c = -0.5 * self._sq + (2.0**-14 * self._packed_qmax) * self._sq.sqrt()
+            c = c + 2.0**-15 * c.abs()
+            self._packed_train = (self._pack_bf16_d8 if d8 else self._pack_bf16)(self.train, c, 1.0)
+        return self._packed_train
+
+    def _prefilter_wide_nns(self, q, qn, ex64, exclude, init_rows, best_d, best_i, overflow):
+        """mgp_knn_scan_wide_bf16x3 (64 < k <= WIDE_MAX_K at a stored width of up to 64; csrc/mgp_knn_wide_bf16.hip) and
+        the wide finish step, on lists that hold the k-best of the head rows; None where the entry declines -- ``best_d``
+        keeps its Gram-form lists for the fp32 wide scan then.  The packed table is the narrow scan's, three-chain layout
+        at every width, with its QMAX head-room and rebuild rule."""
+        (m, k), d = best_d.shape, self._width
+        # the kernel keeps exact (difference-form) distances in the lists: the head lists re-measured in passes sized
+        # from a byte budget, as in _prefilter_long_scan
+        rows = max(1, min(65536, self.FINISH_BUDGET_BYTES // (2 * k * d * q.element_size())))
+        exact = torch.empty_like(best_d)
+        for s in range(0, m, rows):
+            diff = q[s:s + rows, None, :] - self.train[best_i[s:s + rows].to(torch.int64)]
+            exact[s:s + rows] = (diff * diff).sum(-1)
+        packed_train = self._short_packed_table(float(qn.max().sqrt()), False)
+        packed_q = self._pack_bf16(q, 1.0, 0.0)
+        rc = _lib.load().mgp_knn_scan_wide_bf16x3(
+            _lib.ptr(self.train), _lib.ptr(packed_train), _lib.ptr(self._sq_scan), self.train_count, d,
+            _lib.ptr(q), _lib.ptr(packed_q), _lib.ptr(qn), _lib.ptr(ex64), m, k, init_rows,
+            _lib.ptr(exact), _lib.ptr(best_i), _lib.ptr(overflow), _lib.stream_ptr(),
+        )
+        if rc == _lib.EUNSUPPORTED:
+            return None
+        _lib.check(rc, "mgp_knn_scan_wide_bf16x3")
+        self.last_route = "wide"
+        return self._finish_nns(_lib.load().mgp_knn_finish_wide, "mgp_knn_finish_wide", q, best_i, overflow, exclude)
 
     def _prefilter_long_scan(self, q, qn, ex64, init_rows, best_d, best_i, overflow):
         """mgp_knn_scan_long_bf16x3 (stored widths 68 to 256, k <= 64) on lists that hold the k-best of the head rows;

@@ -21,10 +21,22 @@ routes' distances are compared (the largest relative difference is in the entry)
 The sanity line: k = 64, where nothing is routed to the wide pair -- the narrow scans (scan_kind "bf16x3", the default,
 and "f32", the wide kernel's arithmetic) beside the wide pair forced through `_scan_nns(force_wide=True)`.
 
-An existing --out file is updated entry by entry, so the shapes can be measured over several runs."""
+An existing --out file is updated entry by entry, so the shapes can be measured over several runs.
+
+    python tools/knnwidebench.py --prefilter [--d 8 40 64] [--k 65 100 256 1023] [--rounds 3]
+                                 [--out profiles/knn_wide_bf16_bench.json]
+
+The split-bf16 pre-filter of the wide lists (scan_kind="prefilter": mgp_knn_scan_wide_bf16x3) against the default route
+(scan_kind="auto": mgp_knn_scan_wide) on the same table and queries, the protocol of tools/knnlongbench.py --prefilter:
+both objects warmed up on --probe queries, then --rounds rounds (3 at least) that alternate baseline and pre-filter in one
+process, all queries in one call each.  Reported: the two medians, every round, the spread of the baseline side
+((max - min) / median), the ratio of the medians and whether the pre-filter is ahead by more than that spread (no ratio is
+fixed in advance; a cell where it is behind says so), the largest relative distance difference and the share of ranks at
+which the two name the same row."""
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -119,27 +131,68 @@ def bench_sanity(X, Q, args):
     return out
 
 
+def prefilter_shape(X, Q, k, args):
+    base, pre = NN_Wrapper(X, k), NN_Wrapper(X, k, scan_kind="prefilter")
+    for nn in (base, pre):  # warm-up: code objects, the packed table, rocBLAS's choice for the head rows
+        nn.get_nns(Q[:min(Q.shape[0], args.probe)])
+        assert nn.last_route == "wide", nn.last_route
+    t_base, t_pre = [], []
+    for _ in range(max(3, args.rounds)):
+        tb, (bi, bd) = timed(lambda: base.get_nns(Q))
+        tp, (pi, pd) = timed(lambda: pre.get_nns(Q))
+        t_base.append(tb)
+        t_pre.append(tp)
+    base_ms, pre_ms = 1e3 * statistics.median(t_base), 1e3 * statistics.median(t_pre)
+    spread = (max(t_base) - min(t_base)) * 1e3 / base_ms
+    rel, same, rows = 0.0, 0.0, 65536  # (in passes: the fp64 copies of two (m, k) results are 16 GB at k = 1023)
+    for s in range(0, Q.shape[0], rows):
+        b, p = bd[s:s + rows].double(), pd[s:s + rows].double()
+        rel = max(rel, float(((b - p).abs() / b.clamp(min=1e-30)).max()))
+        same += float((bi[s:s + rows] == pi[s:s + rows]).sum())
+    return {
+        "n": X.shape[0], "queries": Q.shape[0], "d": X.shape[1], "stored_width": pre.train.shape[1], "k": k,
+        "baseline_ms": round(base_ms, 1), "baseline_ms_rounds": [round(1e3 * t, 1) for t in t_base],
+        "prefilter_ms": round(pre_ms, 1), "prefilter_ms_rounds": [round(1e3 * t, 1) for t in t_pre],
+        "baseline_spread": round(spread, 4), "ratio_baseline_over_prefilter": round(base_ms / pre_ms, 3),
+        "ahead_by_more_than_the_spread": bool(base_ms / pre_ms > 1.0 + spread),
+        "behind_by_more_than_the_spread": bool(base_ms / pre_ms < 1.0 - spread),
+        "share_of_ranks_with_the_same_row": round(same / bi.numel(), 6), "largest_relative_distance_difference": rel,
+        "flagged": int(pre.last_overflow.sum()), "baseline_flagged": int(base.last_overflow.sum()),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--queries", type=int, default=1_000_000)
-    ap.add_argument("--d", type=int, nargs="+", default=[8, 40])
-    ap.add_argument("--k", type=int, nargs="+", default=[65, 100, 128, 256, 512, 1023])
+    ap.add_argument("--d", type=int, nargs="+", help="default: 8 40 (--prefilter: 8 40 64)")
+    ap.add_argument("--k", type=int, nargs="+", help="default: 65 100 128 256 512 1023 (--prefilter: 65 100 256 1023)")
+    ap.add_argument("--prefilter", action="store_true", help="scan_kind='prefilter' against the default route")
+    ap.add_argument("--rounds", type=int, default=3, help="--prefilter: alternating rounds (3 at least)")
     ap.add_argument("--dense-passes", type=int, default=4)
     ap.add_argument("--probe", type=int, default=65536)
     ap.add_argument("--wide-budget", type=float, default=20.0, help="seconds one full wide call may take")
     ap.add_argument("--wide-slice", type=int, default=262144)
     ap.add_argument("--no-sanity", action="store_true")
-    ap.add_argument("--out", default=os.path.join("profiles", "knn_wide_bench.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "knn_wide_bf16_bench.json" if args.prefilter else "knn_wide_bench.json")
+    args.d = args.d or ([8, 40, 64] if args.prefilter else [8, 40])
+    args.k = args.k or ([65, 100, 256, 1023] if args.prefilter else [65, 100, 128, 256, 512, 1023])
     assert torch.cuda.is_available(), "this is a measurement: it needs the GPU"
-    result = {"entries": {}, "sanity_k64": {}}
+    result = {"entries": {}} if args.prefilter else {"entries": {}, "sanity_k64": {}}
     if os.path.exists(args.out):
         with open(args.out) as f:
             result = json.load(f)
     result["device"] = torch.cuda.get_device_name(0)
-    result["what"] = ("NN_Wrapper.get_nns, Gaussian table and queries; ms for all queries (scaled where an entry says "
-                      "so), two repeats each, dense and wide alternating; speedup = best dense over best wide")
+    if args.prefilter:
+        result["what"] = ("NN_Wrapper.get_nns, Gaussian table and queries, fp32; ms for all queries; baseline = scan_kind='auto' "
+                          "(mgp_knn_scan_wide), prefilter = scan_kind='prefilter' (mgp_knn_scan_wide_bf16x3), alternating in one "
+                          "process, medians over the rounds; baseline_spread = (max - min) / median of the baseline")
+    else:
+        result["what"] = ("NN_Wrapper.get_nns, Gaussian table and queries; ms for all queries (scaled where an entry says "
+                          "so), two repeats each, dense and wide alternating; speedup = best dense over best wide")
 
     def save():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -150,6 +203,13 @@ def main():
         g = torch.Generator(device="cuda").manual_seed(d)
         X = torch.randn(args.n, d, device="cuda", generator=g)
         Q = torch.randn(args.queries, d, device="cuda", generator=g)
+        if args.prefilter:
+            for k in args.k:
+                result["entries"][f"d{d}_k{k}"] = prefilter_shape(X, Q, k, args)
+                print(json.dumps(result["entries"][f"d{d}_k{k}"]), flush=True)
+                save()
+                torch.cuda.empty_cache()
+            continue
         if not args.no_sanity:
             result["sanity_k64"][f"d{d}"] = bench_sanity(X, Q, args)
             print(json.dumps(result["sanity_k64"][f"d{d}"]), flush=True)
